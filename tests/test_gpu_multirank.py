@@ -69,8 +69,8 @@ def _bench(world, scaling, extra=(), bare=False, env_extra=None, steps=4):
     env.update(env_extra or {})
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    args = ["--gpus", str(world), "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline", "--no-dropin", "--scaling", scaling,
-            *extra]
+    args = ["--gpus", str(world), "--steps", str(steps), "--warmup", "2", "--full", "--no-cpu-baseline", "--no-dropin",
+            "--scaling", scaling, *extra]
     if not bare and "--no-strong-lines" not in args:
         args.append("--no-strong-lines")
     if world == 1 or bare:      # bare: `python bench.py --gpus N` -- bench.py launches torch.distributed.run itself

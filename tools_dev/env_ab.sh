@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 VAR=${VAR:?name of the switch}
 IFS=';' read -ra sets <<< "${SETS:-;--views-per-gpu 8}"
-b() { v=$1; shift; env $VAR=$v timeout 600 python bench.py --no-cpu-baseline --no-dropin "$@" 2>/dev/null | tail -1 | python3 -c "
+b() { v=$1; shift; env $VAR=$v timeout 600 python bench.py --full --no-cpu-baseline --no-dropin "$@" 2>/dev/null | tail -1 | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('$VAR=$v'.ljust(22), '$*'.ljust(34), d['ms_per_step'], d['ms_per_step_min'], d.get('launches_per_step'))"; }
 for args in "${sets[@]}"; do
   for i in 1 2 3; do b 0 $args; b 1 $args; done

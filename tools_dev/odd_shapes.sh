@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 while read -r a; do
   [ -z "$a" ] && continue
-  timeout 300 python bench.py --no-cpu-baseline --no-dropin --no-strong-lines --steps 10 --warmup 3 --repeats 3 $a 2>&1 | tail -1 | A="$a" python3 -c "
+  timeout 300 python bench.py --full --no-cpu-baseline --no-dropin --no-strong-lines --steps 10 --warmup 3 --repeats 3 $a 2>&1 | tail -1 | A="$a" python3 -c "
 import json,sys,os
 t=sys.stdin.read()
 try:

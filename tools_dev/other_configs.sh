@@ -4,7 +4,7 @@ R=${R:-r06}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/final; mkdir -p $O
 : > $O/${R}_bench_other_configs.jsonl
-run() { echo "# $1" >> $O/${R}_bench_other_configs.jsonl; shift; timeout 600 python bench.py --no-cpu-baseline "$@" 2>> $O/bench.err | tail -1 >> $O/${R}_bench_other_configs.jsonl; }
+run() { echo "# $1" >> $O/${R}_bench_other_configs.jsonl; shift; timeout 600 python bench.py --full --no-cpu-baseline "$@" 2>> $O/bench.err | tail -1 >> $O/${R}_bench_other_configs.jsonl; }
 run "config 2: 53138-triangle mesh @256x256 with anti-aliasing (S = 512), 1 view" --mesh-n 164 --image-size 256 --views-per-gpu 1 --anti-aliasing
 run "config 2 without anti-aliasing" --mesh-n 164 --image-size 256 --views-per-gpu 1
 run "config 4 per-GPU shard at 4 GPUs: 8 of the 32 cameras" --views-per-gpu 8
@@ -25,7 +25,7 @@ run "silhouettes mode, config 4's 4-view shard" --workload silhouettes --views-p
 run "the unmodified caller's step as the timed line: render() with nothing registered + loss operators (--materialise-images)" --materialise-images --no-dropin
 run "... with the losses in eager torch operators" --materialise-images --loss-form torch --no-dropin
 # the N > 1 step on ONE rank through RCCL (D3M_BENCH_FORCE_DIST: process group, the split exchange's two all-reduces per step)
-rccl() { echo "# $1" >> $O/${R}_bench_other_configs.jsonl; shift; D3M_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --no-cpu-baseline --no-dropin "$@" 2>> $O/bench.err | grep "^{" | tail -1 >> $O/${R}_bench_other_configs.jsonl; }
+rccl() { echo "# $1" >> $O/${R}_bench_other_configs.jsonl; shift; D3M_BENCH_FORCE_DIST=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --full --no-cpu-baseline --no-dropin "$@" 2>> $O/bench.err | grep "^{" | tail -1 >> $O/${R}_bench_other_configs.jsonl; }
 rccl "one rank through RCCL, split exchange (two graphs, two all-reduces): 32 views"
 D3M_SPLIT_EXCHANGE=force rccl "one rank through RCCL, split exchange (forced: the default keeps the one-graph step at this size): config 4's 8-view shard" --views-per-gpu 8
 D3M_SPLIT_EXCHANGE=0 rccl "one rank through RCCL, one all-reduce behind the step: 32 views"
@@ -37,6 +37,6 @@ for l in open("$O/${R}_bench_other_configs.jsonl"):
     d=json.loads(l); print("   ", d["value"], d["unit"], d["ms_per_step"], "ms")
 PY
 # config 5 (the bidding form of coverage): kernel stats of the 8-view line
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c5_stats -o stats -- python3 bench.py --no-cpu-baseline --no-dropin --mesh-n 709 --image-size 1024 --views-per-gpu 8 --steps 20 > $O/c5_stats.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c5_stats -o stats -- python3 bench.py --full --no-cpu-baseline --no-dropin --mesh-n 709 --image-size 1024 --views-per-gpu 8 --steps 20 > $O/c5_stats.log 2>&1
 cp $(find $O/c5_stats -name "*kernel_stats.csv" | head -1) $O/${R}_kernel_stats_config5.csv
 head -8 $O/${R}_kernel_stats_config5.csv | cut -c1-140

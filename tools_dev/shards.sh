@@ -3,7 +3,7 @@
 # DIRS = trees to compare (default: the working tree; ".ab_old ." alternates the committed copy and the working tree)
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 ROOT=$PWD
-line() { d=$1; shift; (cd $ROOT/$d && timeout 600 python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python3 -c "
+line() { d=$1; shift; (cd $ROOT/$d && timeout 600 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); k=d.get('kernel_ms_per_step',{}); dr=d.get('dropin') or {}
 print('$d'.ljust(8), '$*'.ljust(58), 'ms', d['ms_per_step'], 'min', d.get('ms_per_step_min'), 'launches', d.get('launches_per_step'), 'dropin', dr.get('ms_per_step'))"); }
 for rep in $(seq 1 ${REPS:-2}); do

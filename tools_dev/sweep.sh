@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 W=${WORKLOAD:-multiview}
 for v in ${VIEWS:-1 8}; do for s in ${SIZES:-128 512 1024}; do for n in ${MESHES:-3 6 12 20 36 64 100 164 225 450}; do
-  timeout 300 python bench.py --workload $W --no-cpu-baseline --no-dropin --no-strong-lines --steps 10 --warmup 3 --repeats 3 --mesh-n $n --image-size $s --views-per-gpu $v 2>/dev/null | tail -1 | python3 -c "
+  timeout 300 python bench.py --full --workload $W --no-cpu-baseline --no-dropin --no-strong-lines --steps 10 --warmup 3 --repeats 3 --mesh-n $n --image-size $s --views-per-gpu $v 2>/dev/null | tail -1 | python3 -c "
 import json,sys
 try:
     d=json.loads(sys.stdin.read()); k=d['kernel_ms_per_step']; top=list(k.items())[:3]

@@ -4,7 +4,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/trace; rm -rf $O; mkdir -p $O
 for v in 32 4; do
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/tr$v -o tr -- python3 bench.py --no-cpu-baseline --no-dropin --steps 6 --warmup 2 --repeats 1 --views-per-gpu $v > $O/log$v.txt 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/tr$v -o tr -- python3 bench.py --full --no-cpu-baseline --no-dropin --steps 6 --warmup 2 --repeats 1 --views-per-gpu $v > $O/log$v.txt 2>&1
 f=$(find $O/tr$v -name "*kernel_trace.csv" | head -1)
 python3 - "$f" $v <<'PY'
 import csv,sys
