@@ -118,7 +118,7 @@ class _FitLossOnLitImages(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rgb, depth, alpha, rgb_t, depth_t, alpha_t, mask, mask_sum, lit):
-        from ..neural_renderer.rasterize import LitImagesLink, _RasterizeLit
+        from ..neural_renderer.rasterize import LitImagesLink, _FitState, _pixel_records
         if any(ctx.needs_input_grad[3:8]):
             raise NotImplementedError("multiview_fit_loss: targets, mask and mask_sum are constants (detach them)")
         L = _lib.lib()
@@ -128,19 +128,15 @@ class _FitLossOnLitImages(torch.autograd.Function):
         mask_sum = f32c(mask_sum).reshape(1) if mask_sum is not None else mask.sum().reshape(1)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         scratch = [torch.empty(int(L.d3m_render_fit_scratch_floats(B, S)), dtype=torch.float32, device=dev)]
-        g_maps = (torch.empty(B, S, S, 4, dtype=torch.float32, device=dev),        # edge_grad
-                  torch.empty(B, S, S, 2, dtype=torch.float32, device=dev),        # edge_dot
-                  tuple(torch.zeros(2, B, 2, S, dtype=torch.int32, device=dev).unbind(0)),   # nz_lo_inv, nz_hi1
-                  torch.empty(B, S, S, dtype=torch.float32, device=dev))           # grad_depth_map
-        fit_state = (rgb_t, depth_t, alpha_t, mask, scratch, loss, g_maps, mask_sum, False)
-        fit_c = _RasterizeLit._fit_struct(fit_state, 0, 0, B, None)
+        # (the lines' extents zero-filled here: no first launch of the render node clears them for this pass)
+        fit_state = _FitState(rgb_t, depth_t, alpha_t, mask, scratch, loss, mask_sum, False,
+                              _pixel_records(B, S, dev, grad_depth=True, zero_extents=True))
+        fit_c = fit_state.struct(0, 0, B)
         import ctypes
         _lib.check(L.d3m_fit_loss_records(_lib.ptr(rgb), _lib.ptr(depth), _lib.ptr(alpha), _lib.ptr(lit.maps["face_index_map"]),
                                           ctypes.byref(fit_c), B, S, _lib.stream_ptr()), "d3m_fit_loss_records")
-        link = LitImagesLink(fit_state, (tuple(rgb.shape), tuple(depth.shape), tuple(alpha.shape)),
-                             torch.zeros(1, dtype=torch.float32, device=dev))
-        lit.linked_fit = link
-        ctx.link = link
+        ctx.link = LitImagesLink(lit.state, fit_state, (tuple(rgb.shape), tuple(depth.shape), tuple(alpha.shape)),
+                                 torch.zeros(1, dtype=torch.float32, device=dev))
         ctx.save_for_backward(rgb, depth, alpha)
         return loss.reshape(())
 
@@ -175,14 +171,13 @@ class _FitLossFromRenderNode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb, depth, alpha, lit):
         from ..neural_renderer.rasterize import LitImagesLink
-        hs = lit.hint_state
-        link = LitImagesLink(hs, (tuple(rgb.shape), tuple(depth.shape), tuple(alpha.shape)),
+        hs = lit.state.hint
+        link = LitImagesLink(lit.state, hs, (tuple(rgb.shape), tuple(depth.shape), tuple(alpha.shape)),
                              torch.zeros(1, dtype=torch.float32, device=rgb.device))
-        link.finish_pending = bool(getattr(lit, "fit_flags", 0))      # the value is complete behind the render node's backward
-        lit.linked_fit = link
+        link.finish_pending = lit.state.finish_deferred      # the value is complete behind the render node's backward
         ctx.link = link
         ctx.save_for_backward(rgb, depth, alpha)
-        return hs[5].reshape(())
+        return hs.loss.reshape(())
 
     backward = staticmethod(_FitLossOnLitImages.backward)
 
@@ -219,16 +214,15 @@ def multiview_fit_loss(rgb, depth, alpha, rgb_target, depth_target, alpha_target
         if lit is not None and rgb.dim() == 4 and rgb.shape[1] == 3 and rgb.shape[2] == rgb.shape[3] and all(
                 tuple(x.shape) == (B,) + tuple(rgb.shape[2:]) for x in (depth, alpha, depth_target, alpha_target, mask)) \
                 and tuple(rgb_target.shape) == tuple(rgb.shape):
-            hs = getattr(lit, "hint_state", None)
+            hs, given = lit.state.hint, lit.state.hint_mask_sum_given
             # ... and the same NORMALISER: a registered objective that carried a (global) mask_sum is only this call's when
             # this call passes that very tensor, one that did not only when this call does not either (sum(mask) both times)
-            given = getattr(lit, "hint_mask_sum_given", False)
             same_norm = (mask_sum is None and not given) or \
-                (mask_sum is not None and given and hs is not None and _same(hs[7], mask_sum.reshape(1)))
-            if hs is not None and _same(hs[0], rgb_target) and _same(hs[1], depth_target) and _same(hs[2], alpha_target) \
-                    and _same(hs[3], mask) and same_norm:
+                (mask_sum is not None and given and hs is not None and _same(hs.mask_sum, mask_sum.reshape(1)))
+            if hs is not None and _same(hs.rgb_t, rgb_target) and _same(hs.depth_t, depth_target) and \
+                    _same(hs.alpha_t, alpha_target) and _same(hs.mask, mask) and same_norm:
                 return _FitLossFromRenderNode.apply(rgb, depth, alpha, lit)
-            if not lit.cfg[2]:      # (the objective on FINISHED images takes them at the internal size: no anti-aliasing)
+            if not lit.state.aa:    # (the objective on FINISHED images takes them at the internal size: no anti-aliasing)
                 return _FitLossOnLitImages.apply(rgb, depth, alpha, rgb_target, depth_target, alpha_target, mask, mask_sum, lit)
     return _MultiViewFitLoss.apply(rgb, depth, alpha, rgb_target, depth_target, alpha_target, mask, mask_sum)
 

@@ -1,8 +1,11 @@
 """Differentiable rasterization: RasterizeFunction / Rasterize / rasterize_rgbad and friends, same
 signatures and semantics as pnpmodules/neural_renderer/neural_renderer/rasterize.py (NR/rasterize.py),
 running on the HIP operators of libd3m_raster.so.  CUDA(=HIP)-device tensors only, like the reference."""
+import collections
 import ctypes
+import dataclasses
 import os
+from typing import Any, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -284,14 +287,92 @@ def _bslice(t, lo, hi):
     return t if t.shape[0] == 1 else t[lo:hi]
 
 
+class _Records(NamedTuple):
+    """A gradient as the edge gradient reads it: per-pixel records at the internal size S (what d3m_backward_pixel_map
+    would pack from gradient maps), the lines' non-zero extents and, for a fused objective, its depth gradient as a map."""
+    edge_grad: torch.Tensor                 # [B,S,S,4]
+    edge_dot: torch.Tensor                  # [B,S,S,2]
+    extents: Any                            # (nz_lo_inv, nz_hi1), each [B,2,S] int32: a [2,B,2,S] tensor or two views
+    grad_depth: Optional[torch.Tensor]      # [B,S,S] (a fused objective's records only)
+
+    def fields(self, lo, hi):
+        """the records' fields of d3m_fit_targets for views lo..hi"""
+        p = lambda t: _lib.ptr(None if t is None else t[lo:hi])     # noqa: E731
+        return dict(grad_depth_map=p(self.grad_depth), edge_grad=p(self.edge_grad), edge_dot=p(self.edge_dot),
+                    edge_nz_lo_inv=p(self.extents[0]), edge_nz_hi1=p(self.extents[1]))
+
+    def struct(self, lo, hi):
+        """d3m_fit_targets of final records (views lo..hi): no scratch, no scalars to apply"""
+        return _lib.D3MFitTargets(**self.fields(lo, hi), flags=0)
+
+
+def _pixel_records(B, S, dev, grad_depth=False, extents=None, zero_extents=False):
+    """The records' buffers.  `extents`: where the caller keeps them (inside the edge plan's blob); else a [2,B,2,S] tensor,
+    UNINITIALISED (the lit node zeroes it in its first launch; the epilogue's adjoint writes it) or zeroed (zero_extents)."""
+    eg = torch.empty(B, S, S, 4, dtype=torch.float32, device=dev)
+    ed = torch.empty(B, S, S, 2, dtype=torch.float32, device=dev)
+    if extents is None:
+        extents = (torch.zeros if zero_extents else torch.empty)(2, B, 2, S, dtype=torch.int32, device=dev)
+    gd = torch.empty(B, S, S, dtype=torch.float32, device=dev) if grad_depth else None
+    return _Records(eg, ed, extents, gd)
+
+
+def _image_grad_struct(g_img, pooled):
+    """d3m_fit_targets of the DIRECT read: the edge gradient reads the output (alpha) image's gradient in place"""
+    return _lib.D3MFitTargets(grad_alpha_map=_lib.ptr(g_img), flags=_lib.GRAD_OF_OUTPUT_IMAGE | (_lib.FIT_POOLED if pooled else 0))
+
+
+class _FitState(NamedTuple):
+    """A fit objective evaluated in the lit render node's pass (or on its finished images, core.losses): targets, scratch
+    and value per view group and, with a backward pass to come, its gradient (minus the loss's gradient) as records."""
+    rgb_t: torch.Tensor                     # [B,3,s,s]
+    depth_t: torch.Tensor                   # [B,s,s]
+    alpha_t: torch.Tensor                   # [B,s,s]
+    mask: torch.Tensor                      # [B,s,s]
+    scratch: list                           # per view group: d3m_render_fit_scratch_floats
+    loss: torch.Tensor                      # [G]: the value of each view group
+    mask_sum: Optional[torch.Tensor]        # [1]: the photometric normaliser (None: sum(mask), no gradient wanted)
+    pooled: bool                            # an objective on the 2x2-pooled images (anti-aliasing)
+    records: Optional[_Records]
+
+    def struct(self, k, lo, hi, grad_loss=None, flags=0):
+        """d3m_fit_targets of view group k (views lo..hi): forward's `fit` (grad_loss None) / backward's `unscaled`."""
+        rec = self.records.fields(lo, hi) if self.records is not None else {}   # (the gradient as per-pixel records)
+        if self.records is not None and self.pooled:
+            flags = int(flags) | _lib.FIT_POOLED
+        return _lib.D3MFitTargets(
+            rgb_target=_lib.ptr(self.rgb_t[lo:hi]), depth_target=_lib.ptr(self.depth_t[lo:hi]),
+            alpha_target=_lib.ptr(self.alpha_t[lo:hi]), mask=_lib.ptr(self.mask[lo:hi]), scratch=_lib.ptr(self.scratch[k]),
+            loss=_lib.ptr(self.loss[k:k + 1]), grad_loss=_lib.ptr(grad_loss), mask_sum=_lib.ptr(self.mask_sum), **rec,
+            flags=int(flags))
+
+
+def _front_clears(clears):
+    """[(device pointer, bytes)] -> the (pointers, sizes, count) arguments of d3m_lit_front"""
+    assert len(clears) <= _lib.FRONT_RANGES
+    n = max(1, len(clears))
+    return (ctypes.c_void_p * n)(*[c[0] for c in clears]), (ctypes.c_size_t * n)(*[c[1] for c in clears]), len(clears)
+
+
+def _check_deterministic(det):
+    """The deterministic switch a node's forward pass ran with (`det`) must hold for its backward pass too: forward has
+    built the ascending visibility list and the CSR adjacency for it (or not), and the library reads the switch again at
+    launch time (the large-face fallback), so following either one alone would give a half-deterministic pass."""
+    if _deterministic() != det:
+        raise RuntimeError("the deterministic mode (D3M_DETERMINISTIC, d3m_set_deterministic) was %s for this render node's "
+                           "forward pass and is %s for its backward pass: the deterministic() block must enclose backward "
+                           "as well as forward" % (("on", "off") if det else ("off", "on")))
+
+
 class LitImagesLink:
     """What a fit objective evaluated on the finished images of ONE lit render node (core.losses.multiview_fit_loss on
     the outputs of Renderer.render) shares with that node's backward: the objective's gradient as the edge gradient's
-    per-pixel records (`fit_state`, the tuple _RasterizeLit keeps for its own fused objective), the scalar gradient of the
-    loss, and the zero-stride zero images the loss node returns instead of gradient images."""
+    per-pixel records (`fit_state`, a _FitState as _RasterizeLit keeps for its own fused objective), the scalar gradient of
+    the loss, and the zero-stride zero images the loss node returns instead of gradient images.  Created on the node's state."""
 
-    def __init__(self, fit_state, shapes, zero):
+    def __init__(self, state, fit_state, shapes, zero):
         self.fit_state, self.shapes, self.zero = fit_state, shapes, zero
+        state.link = self
         self.grad_loss = None
         self.finish_pending = False     # the objective's totals are still partial sums (D3M_FIT_FINISH_DEFERRED)
         self.pending = False            # the loss node's backward ran and the render node's has not consumed it yet
@@ -322,17 +403,17 @@ class LitImagesLink:
         """other consumers of the images sent gradients too: the objective's own gradient images after all
         (d3m_fit_loss_backward), added to what arrived"""
         rgb, depth, alpha = self.images
-        rgb_t, depth_t, alpha_t, mask, scratch = self.fit_state[:5]
+        fs = self.fit_state
         B, _, H, W = rgb.shape
         if self.finish_pending:         # (a registered objective whose finish was left to the records route: do it now)
             self.finish_pending = False
-            fit_c = _RasterizeLit._fit_struct(self.fit_state, 0, 0, B, None)
+            fit_c = fs.struct(0, 0, B)
             # (the pass ran at the INTERNAL size: twice the images' with anti-aliasing)
-            _lib.check(_lib.lib().d3m_fit_finish(ctypes.byref(fit_c), B, H * (2 if self.fit_state[8] else 1),
+            _lib.check(_lib.lib().d3m_fit_finish(ctypes.byref(fit_c), B, H * (2 if fs.pooled else 1),
                                                  _lib.stream_ptr()), "d3m_fit_finish")
         own = [torch.empty_like(t) for t in (rgb, depth, alpha)]
-        t = (rgb, rgb_t, depth, depth_t, alpha, alpha_t, mask)
-        _lib.check(_lib.lib().d3m_fit_loss_backward(*[_lib.ptr(x) for x in t], _lib.ptr(scratch[0]), _lib.ptr(self.grad_loss),
+        t = (rgb, fs.rgb_t, depth, fs.depth_t, alpha, fs.alpha_t, fs.mask)
+        _lib.check(_lib.lib().d3m_fit_loss_backward(*[_lib.ptr(x) for x in t], _lib.ptr(fs.scratch[0]), _lib.ptr(self.grad_loss),
                                                     _lib.ptr(own[0]), _lib.ptr(own[1]), _lib.ptr(own[2]), B, H, W,
                                                     _lib.stream_ptr()), "d3m_fit_loss_backward")
         add = lambda g, o: o if (g is None or self.is_dummy(g)) else g + o
@@ -348,23 +429,12 @@ def lit_images_link(rgb, depth, alpha):
         return None
     if (rgb.output_nr, alpha.output_nr, depth.output_nr) != (0, 1, 2):
         return None
-    cfg = getattr(fn, "cfg", None)
-    if cfg is None or fn.fit is not None or getattr(fn, "linked_fit", None) is not None:
+    st = fn.state
+    if st.fit is not None or st.link is not None:
         return None
-    S, _eps, aa, ra, rd, _fb, _light, _Bl, groups = cfg
-    if (aa and getattr(fn, "hint_state", None) is None) or not (ra and rd) or len(groups) != 1 or \
-            fn.maps.get("visibility") is None:
+    if (st.aa and st.hint is None) or not (st.ra and st.rd) or len(st.groups) != 1 or fn.maps.get("visibility") is None:
         return None
     return fn
-
-
-def _lit_clear_ranges(L, grad_textures, textures_batch, grad_light, light_batch, B, Ft, fill_back, ts, workspace):
-    """[(device pointer, bytes)]: what d3m_backward_textures_lit (with a visibility blob) zeroes in front of its kernels"""
-    ptrs, sizes = (ctypes.c_void_p * 4)(), (ctypes.c_size_t * 4)()
-    n = L.d3m_backward_textures_lit_clear_ranges(_lib.ptr(grad_textures), int(textures_batch), _lib.ptr(grad_light),
-                                                 int(light_batch), B, Ft, int(bool(fill_back)), ts, _lib.ptr(workspace), 1,
-                                                 ptrs, sizes)
-    return [(ptrs[i], sizes[i]) for i in range(n)]
 
 
 def _checked_sink(grad_sink, vertices, textures):
@@ -385,6 +455,101 @@ def _checked_sink(grad_sink, vertices, textures):
     if not (torch.is_tensor(loss) and loss.dtype == torch.float32 and loss.numel() == 1 and loss.device == vertices.device):
         return None
     return grad_sink
+
+
+@dataclasses.dataclass(eq=False)
+class _LitState:
+    """What the lit render node's forward pass decided, kept on its context for backward -- which decides none of it again
+    -- and for the fit objectives linked to the node (core.losses)."""
+    S: int                                  # the internal size (twice the output's with anti-aliasing)
+    eps: float
+    aa: bool
+    ra: bool                                # alpha and depth returned (rgb always is)
+    rd: bool
+    fill_back: bool
+    light: tuple                            # (ia, idr, colour_ambient, colour_directional, direction)
+    Bl: int                                 # batch of the per-face light (1: one shared mesh)
+    groups: list                            # the view groups' (lo, hi)
+    need_grad: bool
+    need_geom: bool                         # a gradient for the mesh: edge gradient, depth gradient, light / camera adjoints
+    need_tex: bool
+    need_vert: bool                         # the light's adjoint reaches the world-space vertices
+    gathered: bool                          # backward runs the gathered texture / depth pass
+    det: bool                               # the deterministic backward pass (checked against the switch in backward)
+    serial: bool                            # every branch on the forking stream (_serial_branches)
+    plan_open: bool                         # forward left the visibility list / plan branch open (defer_plan_join)
+    camera: Any                             # the camera inside the node (its parameter block) or None
+    cam_keep: Any
+    grad_sink: Any                          # _checked_sink
+    fit: Optional[_FitState]                # the node's own fused objective (rasterize_lit_fit)
+    hint: Optional[_FitState]               # a registered objective (fit_hint), evaluated in the pass that wrote the images
+    hint_mask_sum_given: bool               # ... with the caller's normaliser (else the node took sum(mask))
+    finish_deferred: bool = False           # the objective's finish is left to backward's gathered pass (FIT_FINISH_DEFERRED)
+    pre: Any = None                         # backward's buffers, allocated and zeroed by forward (_backward_buffers; one use)
+    link: Optional[LitImagesLink] = None    # a fit objective evaluated on the finished images (set by LitImagesLink)
+
+
+# _backward_buffers: the vertex accumulators, the texture / light gradients of batch B and where each view group's gathered
+# pass writes them (gt_g / gl_g; batch 1: the groups' sums, added up behind the join), the gathered pass's workspace (one
+# pipeline: PRECLEARED), the ranges to zero, and the deterministic mode's per-view light, its gradient, K4's / K6's arrays.
+_BackwardBuffers = collections.namedtuple("_BackwardBuffers", "grad_sv grad_vertices grad_textures gt_g grad_light gl_g lit_ws "
+                                                              "clears det_light det_gl det_k4 det_k6")
+
+
+def _backward_buffers(st, vertices, textures, light, B, V, Ft, ts, ws_stream=None):
+    """The lit node's backward accumulators, the gathered pass's workspace and the ranges of them to zero before its
+    kernels run (`clears`).  Called by backward (ws_stream: the stream of its gathered pass, whose cached workspace it
+    takes) or, for a caller that runs backward right behind forward, by forward (a workspace of its own)."""
+    L = _lib.lib()
+    dev, groups, sink = vertices.device, st.groups, st.grad_sink
+    G = len(groups)
+    grad_sv = torch.empty(B, V, 3, dtype=torch.float32, device=dev) if st.need_geom else None
+    grad_vertices = grad_textures = gt_g = grad_light = gl_g = lit_ws = None
+    det_light = det_gl = det_k4 = det_k6 = None
+    if st.need_vert:
+        grad_vertices = sink[0] if (sink is not None and st.camera is not None) else torch.empty_like(vertices)
+    if st.gathered:
+        if textures.shape[0] == 1:
+            gt_g = [sink[1] if (sink is not None and sink[1] is not None and G == 1) else torch.empty_like(textures)
+                    for _ in groups]
+        else:
+            grad_textures = torch.empty_like(textures)
+            gt_g = [grad_textures[lo:hi] for lo, hi in groups]
+        if st.need_vert:
+            if st.Bl == 1:
+                gl_g = [torch.empty_like(light) for _ in groups]
+            else:
+                grad_light = torch.empty_like(light)
+                gl_g = [grad_light[lo:hi] for lo, hi in groups]
+    clears = [_lib.tensor_range(t) for t in (grad_sv, grad_vertices) if t is not None]
+    if st.det:
+        # per-VIEW light gradients (one contribution per entry), the two per-face arrays of K4 and K6
+        Fp = 2 * Ft if st.fill_back else Ft
+        if st.need_vert:
+            det_light = light.expand(B, Fp, 3).contiguous() if st.Bl == 1 else light
+            det_gl = torch.empty(B, Fp, 3, dtype=torch.float32, device=dev)
+        if st.need_geom:
+            det_k4 = torch.empty(B, Fp, 3, 3, dtype=torch.float32, device=dev)
+            clears.append(_lib.tensor_range(det_k4))
+            if st.rd:
+                det_k6 = torch.empty(B, Fp, 3, 3, dtype=torch.float32, device=dev)
+                clears.append(_lib.tensor_range(det_k6))
+    if st.gathered and G == 1:
+        nbytes = int(L.d3m_backward_textures_lit_workspace_bytes(B, Ft, int(st.fill_back), ts))
+        if ws_stream is None:
+            lit_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        else:
+            with torch.cuda.stream(ws_stream):     # (scratch is cached per stream: the stream the pass will run on)
+                lit_ws = ops._workspace("lit", nbytes, dev)
+        # what d3m_backward_textures_lit (with a visibility blob) zeroes in front of its kernels
+        gl = det_gl if det_gl is not None else (gl_g[0] if gl_g is not None else None)
+        ptrs, sizes = (ctypes.c_void_p * 4)(), (ctypes.c_size_t * 4)()
+        n = L.d3m_backward_textures_lit_clear_ranges(
+            _lib.ptr(grad_textures if grad_textures is not None else gt_g[0]), textures.shape[0], _lib.ptr(gl),
+            B if det_gl is not None else st.Bl, B, Ft, int(st.fill_back), ts, _lib.ptr(lit_ws), 1, ptrs, sizes)
+        clears += [(ptrs[i], sizes[i]) for i in range(n)]
+    return _BackwardBuffers(grad_sv, grad_vertices, grad_textures, gt_g, grad_light, gl_g, lit_ws, clears, det_light,
+                            det_gl, det_k4, det_k6)
 
 
 class _RasterizeLit(torch.autograd.Function):
@@ -444,6 +609,8 @@ class _RasterizeLit(torch.autograd.Function):
         # the GEOMETRY side of backward (edge gradient K4, depth gradient K6, the light's and the camera's adjoints) only
         # exists for a mesh that wants a gradient: a texture-only optimisation builds no plan and walks no line
         need_geom = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        need_tex = bool(ctx.needs_input_grad[3])
+        need_vert = bool(ctx.needs_input_grad[1]) and idr != 0
         groups = _group_bounds(B, view_groups)
         G = len(groups)
         # Everything the branches write is allocated here, on the current stream: no tensor changes its owning stream.
@@ -466,28 +633,30 @@ class _RasterizeLit(torch.autograd.Function):
         plan = [torch.empty(int(L.d3m_edge_plan_bytes(hi - lo, Fp, S)), dtype=torch.uint8, device=dev) for lo, hi in groups] \
             if need_geom else None
         s_out = S // 2 if anti_aliasing else S
-        rgb = alpha = depth = loss_g = None
-        fit_state = None
+        rgb = alpha = depth = loss_g = fit_state = None
         # A REGISTERED objective (Renderer.fit_targets -> `fit_hint`): the node returns the IMAGES, as render() does, and the
         # pass that writes them also evaluates the objective the caller is about to evaluate on them and leaves its gradient
         # as walk records (the fused objective's pass with images_out): core.losses.multiview_fit_loss, handed these very
-        # images and targets, then finds value and records here instead of re-reading the images (`hint_state`).
+        # images and targets, then finds value and records here instead of re-reading the images (`_LitState.hint`).
         hinted = fit is None and fit_hint is not None and return_alpha and return_depth and need_grad and G == 1
         if fit is None:
             rgb = torch.empty(B, 3, s_out, s_out, dtype=torch.float32, device=dev)
             alpha = torch.empty(B, s_out, s_out, dtype=torch.float32, device=dev) if return_alpha else None
             depth = torch.empty(B, s_out, s_out, dtype=torch.float32, device=dev) if return_depth else None
-            if hinted:
-                fit = (tuple(fit_hint) + (None,))[:5] + ((rgb, depth, alpha),)
-        if fit is not None:
+        mask_sum_given = False
+        objective = (fit_hint, (rgb, depth, alpha)) if hinted else fit      # (targets, images_out | None)
+        if objective is not None:
             # the fit objective is evaluated where the images are produced: they are never written (rasterize_lit_fit)
             if not (return_alpha and return_depth):
                 raise ValueError("the fused fit objective needs rgb, alpha and depth")
-            rgb_t, depth_t, alpha_t, mask = (f32c(t) for t in fit[:4])
-            mask_sum = f32c(fit[4]).reshape(1) if len(fit) > 4 and fit[4] is not None else None
-            if len(fit) > 5 and fit[5] is not None:
+            targets, images_out = objective         # targets = (rgb_t, depth_t, alpha_t, mask[, mask_sum])
+            *targets, mask_sum = (tuple(targets) + (None,))[:5]
+            rgb_t, depth_t, alpha_t, mask = (f32c(t) for t in targets)
+            mask_sum_given = mask_sum is not None
+            mask_sum = f32c(mask_sum).reshape(1) if mask_sum is not None else None
+            if images_out is not None:
                 # the images as a by-product of the same pass (caller's buffers, not differentiable outputs)
-                rgb, depth, alpha = fit[5]
+                rgb, depth, alpha = images_out
                 for t, shape in ((rgb, (B, 3, s_out, s_out)), (depth, (B, s_out, s_out)), (alpha, (B, s_out, s_out))):
                     if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
                         raise ValueError("images_out must be contiguous float32 (rgb [B,3,s,s], depth [B,s,s], alpha [B,s,s])")
@@ -500,51 +669,59 @@ class _RasterizeLit(torch.autograd.Function):
             loss_g = grad_sink[2] if (grad_sink is not None and G == 1) else torch.empty(G, dtype=torch.float32, device=dev)
             scratch = [torch.empty(int(L.d3m_render_fit_scratch_floats(hi - lo, S)), dtype=torch.float32, device=dev)
                        for lo, hi in groups]
-            # with a backward pass to come, the same pass leaves the objective's gradient behind -- minus the gradient of the
-            # loss, only known later -- in the form its readers want: the edge gradient's per-pixel records at the internal
-            # size (what d3m_backward_pixel_map would otherwise pack from gradient maps: no pixel pass in backward at all),
-            # the lines' non-zero extents, and the depth gradient as a map.  With anti-aliasing an output pixel is the mean
-            # of four internal ones: each gets a quarter of its gradient (D3M_FIT_POOLED; round 4 left unscaled maps here
-            # and packed them in backward).
-            g_maps = None
-            if need_grad:
-                g_maps = (torch.empty(B, S, S, 4, dtype=torch.float32, device=dev),        # edge_grad
-                          torch.empty(B, S, S, 2, dtype=torch.float32, device=dev),        # edge_dot
-                          None,                                                            # (nz_lo_inv, nz_hi1): below
-                          torch.empty(B, S, S, dtype=torch.float32, device=dev))           # grad_depth_map
-            fit_state = (rgb_t, depth_t, alpha_t, mask, scratch, loss_g, g_maps, mask_sum, bool(anti_aliasing))
         cur = torch.cuda.current_stream()
         det = need_grad and _deterministic()
         if det:
             _RasterizeLit._deterministic_supported(G, tri, vertices, ts, idr, ctx.needs_input_grad[1])
             if need_geom:
                 vertex_adjacency(tri, V)            # (built here, outside any capture of the backward pass)
-        serial = G == 1 and (det or getattr(ctx, "force_serial", False) or _serial_branches(B, Ft, S))
+        # (LitFitManual: every kernel on the caller's stream -- the step is cut BETWEEN kernels of one stream)
+        manual = isinstance(ctx, _ManualContext)
+        serial = G == 1 and (det or manual or _serial_branches(B, Ft, S))
         mains = [cur] + [_side_stream(dev, k) for k in range(1, G)]
         auxs = [_side_stream(dev, G + k, serial) for k in range(G)]
-        nz_own = None
-        if fit_state is not None and fit_state[6] is not None:      # (records form)
-            # the lines' non-zero extents (zero before the objective's pass fills them): when the plan is built in front of
-            # that pass on the same stream, inside the plan's blob, cleared by the plan's own clear; else a fill of their own
-            if serial and plan is not None:
-                each = ctypes.c_size_t(0)
-                off = int(L.d3m_edge_plan_extents_offset(B, Fp, S, ctypes.byref(each)))
-                nz = tuple(plan[0][off + j * each.value: off + j * each.value + B * 2 * S * 4].view(torch.int32).view(B, 2, S)
-                           for j in range(2))
-            else:
-                nz_own = torch.empty(2, B, 2, S, dtype=torch.int32, device=dev)       # (zeroed by the first launch, below)
-                nz = tuple(nz_own.unbind(0))
-            fit_state = fit_state[:6] + (fit_state[6][:2] + (nz,) + fit_state[6][3:],) + fit_state[7:]
+        own_extents = False
+        if objective is not None:
+            # with a backward pass to come, the same pass leaves the objective's gradient behind -- minus the gradient of the
+            # loss, only known later -- in the form its readers want: the edge gradient's per-pixel records at the internal
+            # size (what d3m_backward_pixel_map would otherwise pack from gradient maps: no pixel pass in backward at all),
+            # the lines' non-zero extents, and the depth gradient as a map.  With anti-aliasing an output pixel is the mean
+            # of four internal ones: each gets a quarter of its gradient (D3M_FIT_POOLED; round 4 left unscaled maps here
+            # and packed them in backward).
+            records = None
+            if need_grad:
+                # the lines' non-zero extents (zero before the objective's pass fills them): when the plan is built in front
+                # of that pass on the same stream, inside the plan's blob, cleared by the plan's own clear; else a tensor of
+                # their own, zeroed by the first launch (below)
+                extents = None
+                if serial and plan is not None:
+                    each = ctypes.c_size_t(0)
+                    off = int(L.d3m_edge_plan_extents_offset(B, Fp, S, ctypes.byref(each)))
+                    extents = tuple(plan[0][off + j * each.value: off + j * each.value + B * 2 * S * 4].view(torch.int32)
+                                    .view(B, 2, S) for j in range(2))
+                own_extents = extents is None
+                records = _pixel_records(B, S, dev, grad_depth=True, extents=extents)
+            fit_state = _FitState(rgb_t, depth_t, alpha_t, mask, scratch, loss_g, mask_sum, bool(anti_aliasing), records)
+        st = _LitState(S=S, eps=float(eps), aa=bool(anti_aliasing), ra=bool(return_alpha), rd=bool(return_depth),
+                       fill_back=bool(fill_back), light=(float(ia), float(idr), ca, cd, direction), Bl=Bl, groups=groups,
+                       need_grad=need_grad, need_geom=need_geom, need_tex=need_tex, need_vert=need_vert,
+                       gathered=need_tex or need_vert, det=det, serial=serial,
+                       plan_open=bool(plan is not None and defer_plan_join and G == 1),   # (G > 1: capture crashes, as above)
+                       camera=camera, cam_keep=cam_keep, grad_sink=grad_sink,
+                       fit=None if hinted else fit_state, hint=fit_state if hinted else None,
+                       # (whether the registered objective brought its normaliser or the node took sum(mask):
+                       #  multiview_fit_loss only rides on the node's result when it is asked for the same one)
+                       hint_mask_sum_given=hinted and mask_sum_given)
         # THE STEP'S FIRST LAUNCH (d3m_lit_front): the camera transform (with its look_at basis), the per-face light and
         # every clear the operators below would otherwise each launch for themselves -- the forward workspace's counters (or
         # z-buffer), the plan's, the objective's arrival tickets, the lines' extents -- and, for a caller that runs backward
         # right behind forward (defer_plan_join: MultiViewFit's step; LitFitManual), the backward pass's accumulators and
-        # masks too, allocated here for that purpose (`ctx.pre`): five launches of round 4's step are block ranges of one.
-        # One pipeline only: view groups keep their own clears.
+        # masks too, allocated here for that purpose (`_LitState.pre`): five launches of round 4's step are block ranges of
+        # one.  One pipeline only: view groups keep their own clears.
         clears, pre = [], None
         flags_fwd = flags_plan = flags_fit = 0
         ws0 = ops._workspace("fwd", L.d3m_forward_workspace_bytes(groups[0][1] - groups[0][0], Fp, S), dev)
-        if G == 1 and os.environ.get("D3M_NO_PRECLEAR") != "1":      # (D3M_NO_PRECLEAR=1: every operator clears for itself; debugging)
+        if G == 1:
             nb = int(L.d3m_forward_clear_bytes(B, Ft, int(bool(fill_back)), S, ws0.numel()))
             if nb:
                 clears.append((ws0.data_ptr(), nb))
@@ -555,38 +732,31 @@ class _RasterizeLit(torch.autograd.Function):
             if fit_state is not None:
                 off = ctypes.c_size_t(0)
                 nfl = int(L.d3m_render_fit_scratch_clear_range(B, S, ctypes.byref(off)))
-                clears.append((fit_state[4][0].data_ptr() + 4 * off.value, 4 * nfl))
+                clears.append((fit_state.scratch[0].data_ptr() + 4 * off.value, 4 * nfl))
                 flags_fit = _lib.PRECLEARED
-        if nz_own is not None:
-            clears.append(_lib.tensor_range(nz_own))
-        step_mode = G == 1 and need_grad and (defer_plan_join or getattr(ctx, "force_serial", False)) and not det and \
-            os.environ.get("D3M_NO_PRECLEAR") != "1"
-        if step_mode:
-            pre = _RasterizeLit._backward_buffers(ctx, L, vertices, textures, light, grad_sink, camera is not None,
-                                                  B, V, Ft, ts, Bl, fill_back, idr, need_geom)
-            if len(clears) + len(pre["clears"]) <= _lib.FRONT_RANGES:
-                clears += pre["clears"]
+        if own_extents:
+            clears.append(_lib.tensor_range(fit_state.records.extents))
+        if G == 1 and need_grad and (defer_plan_join or manual) and not det:
+            pre = _backward_buffers(st, vertices, textures, light, B, V, Ft, ts)
+            if len(clears) + len(pre.clears) <= _lib.FRONT_RANGES:
+                clears += pre.clears
             else:
                 pre = None
-        assert len(clears) <= _lib.FRONT_RANGES
         # ... and the objective's finish (partial sums -> value) is left to a kernel that backward pass launches anyway
-        if pre is not None and pre["gathered"] and fit_state is not None and fit_state[6] is not None:
+        if pre is not None and st.gathered and fit_state is not None and fit_state.records is not None:
             flags_fit |= _lib.FIT_FINISH_DEFERRED
-        ctx.fit_flags = flags_fit & _lib.FIT_FINISH_DEFERRED
-        zp = (ctypes.c_void_p * max(1, len(clears)))(*[c[0] for c in clears])
-        zb = (ctypes.c_size_t * max(1, len(clears)))(*[c[1] for c in clears])
+        st.pre, st.finish_deferred = pre, bool(flags_fit & _lib.FIT_FINISH_DEFERRED)
+        zp, zb, nz = _front_clears(clears)
         _lib.check(L.d3m_lit_front(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam) if cam is not None else None,
                                    ctypes.byref(basis) if basis is not None else None,
                                    _lib.ptr(sv) if cam is not None else None, B, V, _lib.ptr(tri), tri.shape[0], Ft,
                                    int(bool(fill_back)), _lib.ptr(light), Bl, float(ia), float(idr), cca, ccd, cdir,
-                                   zp, zb, len(clears), _lib.stream_ptr()), "d3m_lit_front")
-        ctx.pre = pre
+                                   zp, zb, nz, _lib.stream_ptr()), "d3m_lit_front")
         # The visibility list and the plan are only read by backward.  A caller that runs backward right behind forward,
         # on the same stream and (if captured) in the same capture, may leave that branch open at the end of forward
         # (defer_plan_join): backward waits for the plan where it first needs it and joins the branch, which runs on
         # under the loss and the first backward passes.  The outputs are then only valid after backward.
-        plan_ready = [] if (plan is not None and defer_plan_join and G == 1) else None   # (G > 1: capture crashes, as above)
-        vis_ready, vis_on_main = None, False
+        plan_ready = [] if st.plan_open else None
         for k in range(G):
             if mains[k] is not cur:
                 mains[k].wait_stream(cur)
@@ -609,7 +779,6 @@ class _RasterizeLit(torch.autograd.Function):
                     # (texture-only: the list is all backward needs -- on this stream, no branch)
                     _lib.check(L.d3m_visibility(None, _lib.ptr(vis[k]), vis[k].numel(), Bg, Fp, S, _lib.stream_ptr()),
                                "d3m_visibility")
-                    vis_on_main = True
                 elif vis is not None:
                     # ONE FORK, BEHIND THE VISIBILITY LIST (round 5).  The list has two readers -- the plan (side branch) and
                     # backward's gathered pass (this stream) -- and the coverage pass two as well (the list, the sampling
@@ -618,12 +787,10 @@ class _RasterizeLit(torch.autograd.Function):
                     # shard: 5.8 us between k_bid_resolve and the list, 5.1 behind the list).  With the list on this
                     # stream, in front of the fork, only it has two successors; the sampling pass starts 5 us later on a
                     # chain that has 40 us to spare.  4 views 0.2747 -> 0.2709 ms, 8 views 0.4687 -> 0.4660 (same box).
-                    vis_first = plan_ready is not None and auxs[k] is not mains[k] and \
-                        os.environ.get("D3M_FORK_BEHIND_LIST", "1") != "0"
+                    vis_first = plan_ready is not None and auxs[k] is not mains[k]
                     if vis_first:
                         _lib.check(L.d3m_visibility(None, _lib.ptr(vis[k]), vis[k].numel(), Bg, Fp, S,
                                                     _lib.stream_ptr()), "d3m_visibility")
-                        vis_on_main = True
                     if auxs[k] is not mains[k]:
                         auxs[k].wait_stream(mains[k])
                     with torch.cuda.stream(auxs[k]):
@@ -631,18 +798,13 @@ class _RasterizeLit(torch.autograd.Function):
                         if not vis_first:
                             _lib.check(L.d3m_visibility(None, _lib.ptr(vis[k]), vis[k].numel(), Bg, Fp, S,
                                                         _lib.stream_ptr()), "d3m_visibility")
-                        if plan_ready is not None and not vis_first:
-                            vis_ready = torch.cuda.Event()
-                            vis_ready.record(auxs[k])
                         _lib.check(L.d3m_edge_plan(_lib.ptr(faces[lo:hi]), _lib.ptr(fi_g), _lib.ptr(vis[k]), _lib.ptr(plan[k]),
                                                    plan[k].numel(), Bg, Fp, S, flags_plan, _lib.stream_ptr()), "d3m_edge_plan")
                         if plan_ready is not None:
                             plan_ready.append(torch.cuda.Event())
                             plan_ready[k].record(auxs[k])
-                fit_c = None
-                if fit_state is not None:
-                    # (the objective's value is completed by the pass's own last workgroups: no finishing launch)
-                    fit_c = _RasterizeLit._fit_struct(fit_state, k, lo, hi, None, flags=flags_fit)
+                # (the objective's value is completed by the pass's own last workgroups: no finishing launch)
+                fit_c = fit_state.struct(k, lo, hi, flags=flags_fit) if fit_state is not None else None
                 # texture sampling + background blend + alpha + flip / pooling in one pass (no rgb_sampled round trip)
                 _lib.check(L.d3m_render_lit_epilogue(
                     _lib.ptr(faces[lo:hi]), _lib.ptr(tex_g), tex_g.shape[0], _lib.ptr(light_g), light_g.shape[0],
@@ -659,20 +821,11 @@ class _RasterizeLit(torch.autograd.Function):
         m["visibility"] = vis
         m["edge_plan"] = plan
         m["plan_ready"] = plan_ready
-        m["vis_ready"] = vis_ready if plan_ready is not None else None
-        m["vis_on_main"] = vis_on_main       # (the list was built on the forking stream: its readers there need no event)
         m["plan_stream"] = auxs[0]
-        ctx.cfg = (S, float(eps), bool(anti_aliasing), bool(return_alpha), bool(return_depth), bool(fill_back),
-                   (float(ia), float(idr), ca, cd, direction), Bl, groups)
+        ctx.state = st
         ctx.maps = m
-        ctx.fit = None if hinted else fit_state
-        ctx.hint_state = fit_state if hinted else None
-        # (whether the registered objective brought its normaliser or the node took sum(mask): multiview_fit_loss only rides
-        #  on the node's result when it is asked for the same one)
-        ctx.hint_mask_sum_given = bool(hinted and len(fit_hint) > 4 and fit_hint[4] is not None)
-        ctx.camera, ctx.cam_keep, ctx.grad_sink = camera, cam_keep, grad_sink
         ctx.save_for_backward(faces, vertices, tri, textures, light)
-        if fit is not None and not hinted:
+        if fit is not None:
             return loss_g.sum() if G > 1 else loss_g.reshape(())
         empty = torch.tensor([])
         return (rgb, alpha if return_alpha else empty, depth if return_depth else empty)
@@ -687,50 +840,6 @@ class _RasterizeLit(torch.autograd.Function):
                 "D3M_DETERMINISTIC / d3m_set_deterministic(1): the lit render node's reproducible backward pass needs "
                 "view_groups == 1, faces of batch 1 (one shared topology), texture_size 2..4 and, with directional light, "
                 "vertices of batch 1")
-
-    @staticmethod
-    def _backward_buffers(ctx, L, vertices, textures, light, grad_sink, camera_inside, B, V, Ft, ts, Bl, fill_back, idr,
-                          need_geom=True):
-        """The backward pass's accumulators and the gathered pass's workspace, allocated in FORWARD for a caller that runs
-        backward right behind it: the forward's first launch zeroes what they need zeroed (`clears`), so the backward
-        pass starts without a clear of its own.  Mirrors the allocations of _backward_halves (one pipeline)."""
-        dev = vertices.device
-        need_tex = ctx.needs_input_grad[3]
-        need_vert = ctx.needs_input_grad[1] and idr != 0
-        gathered = need_tex or need_vert
-        pre = {"clears": [], "gathered": gathered, "grad_vertices": None, "grad_sv": None}
-        if need_geom:
-            pre["grad_sv"] = torch.empty(B, V, 3, dtype=torch.float32, device=dev)
-            pre["clears"].append(_lib.tensor_range(pre["grad_sv"]))
-        if gathered and need_vert:
-            gv = grad_sink[0] if (grad_sink is not None and camera_inside) else torch.empty_like(vertices)
-            pre["grad_vertices"] = gv
-            pre["clears"].append(_lib.tensor_range(gv))
-        if gathered:
-            gt = grad_sink[1] if (textures.shape[0] == 1 and grad_sink is not None and grad_sink[1] is not None) \
-                else torch.empty_like(textures)
-            gl = torch.empty_like(light) if need_vert else None
-            ws = torch.empty(int(L.d3m_backward_textures_lit_workspace_bytes(B, Ft, int(bool(fill_back)), ts)),
-                             dtype=torch.uint8, device=dev)
-            pre["clears"] += _lit_clear_ranges(L, gt, textures.shape[0], gl, Bl, B, Ft, fill_back, ts, ws)
-            pre.update(gt=gt, gl=gl, lit_ws=ws)
-        return pre
-
-    @staticmethod
-    def _fit_struct(fit_state, k, lo, hi, grad_loss, flags=0):
-        """d3m_fit_targets of view group k (views lo..hi): forward's `fit` (grad_loss None) / backward's `unscaled`."""
-        rgb_t, depth_t, alpha_t, mask, scratch, loss_g, g_maps, mask_sum, pooled = fit_state
-        eg = ed = nz_lo = nz_hi = gd = None
-        if g_maps is not None:                      # the gradient as per-pixel records at the internal size
-            eg, ed, gd = g_maps[0][lo:hi], g_maps[1][lo:hi], g_maps[3][lo:hi]
-            nz_lo, nz_hi = g_maps[2][0][lo:hi], g_maps[2][1][lo:hi]
-            if pooled:
-                flags = int(flags) | _lib.FIT_POOLED
-        return _lib.D3MFitTargets(
-            _lib.ptr(rgb_t[lo:hi]), _lib.ptr(depth_t[lo:hi]), _lib.ptr(alpha_t[lo:hi]), _lib.ptr(mask[lo:hi]),
-            _lib.ptr(scratch[k]), _lib.ptr(loss_g[k:k + 1]), None, None, _lib.ptr(gd),
-            _lib.ptr(grad_loss), _lib.ptr(mask_sum), _lib.ptr(eg), _lib.ptr(ed), _lib.ptr(nz_lo), _lib.ptr(nz_hi),
-            int(flags))
 
     @staticmethod
     def backward(ctx, g_rgb, g_alpha=None, g_depth=None):
@@ -751,28 +860,25 @@ class _RasterizeLit(torch.autograd.Function):
         texture gradient on its way while the geometry side still runs (deep3dmap_amd/multiview.py).  With more than one
         view group the cut comes after the last group's passes have been issued (nothing to overlap)."""
         L = _lib.lib()
+        st, m = ctx.state, ctx.maps
+        _check_deterministic(st.det)
         faces, vertices, tri, textures, light = ctx.saved_tensors
-        S, eps, aa, ra, rd, fill_back, (ia, idr, ca, cd, direction), Bl, groups = ctx.cfg
-        m = ctx.maps
+        S, eps, ra, rd, fill_back, Bl, groups = st.S, st.eps, st.ra, st.rd, st.fill_back, st.Bl, st.groups
+        ia, idr, ca, cd, direction = st.light
+        need_geom, need_tex, need_vert, gathered, det = st.need_geom, st.need_tex, st.need_vert, st.gathered, st.det
         dev, B, G = faces.device, faces.shape[0], len(groups)
         Ft, V, ts = tri.shape[1], vertices.shape[1], textures.shape[2]
-        # a caller that runs backward right behind forward had its accumulators allocated AND zeroed by the forward's first
-        # launch (ctx.pre: one use -- a second backward over the same graph allocates and clears its own)
-        pre = getattr(ctx, "pre", None)
-        ctx.pre = None
-        # (no gradient for the mesh wanted -- a texture-only optimisation: no screen-space accumulator, no edge gradient, no
-        #  depth gradient, no camera adjoint; the node returns None for the vertices)
-        need_geom = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
-        grad_sv = None
-        if need_geom:
-            grad_sv = pre["grad_sv"] if pre is not None else torch.empty(B, V, 3, dtype=torch.float32, device=dev)
-        grad_loss = scratch = mask_sum = None
-        records = None
+        # a caller that runs backward right behind forward had its buffers allocated AND zeroed by the forward's first
+        # launch (`pre`: one use -- a second backward over the same graph allocates and clears its own).  (No gradient for
+        # the mesh wanted -- a texture-only optimisation: no screen-space accumulator, no edge gradient, no depth gradient,
+        # no camera adjoint; the node returns None for the vertices.)
+        bufs, st.pre = st.pre, None
+        grad_loss = records = None
         # A fit objective evaluated on this node's finished images (core.losses.multiview_fit_loss -> LitImagesLink) has left
         # its gradient as per-pixel records and sends zero-stride ZERO images back: if those are all that arrived, backward
         # is the fused objective's (no gradient images exist); if other consumers of the images added theirs, the
         # objective's gradient images are materialised after all and added.
-        fit, link = ctx.fit, getattr(ctx, "linked_fit", None)
+        fit, link = st.fit, st.link
         if fit is None and link is not None and link.pending:
             link.pending = False
             if link.is_dummy(g_rgb) and link.is_dummy(g_alpha) and link.is_dummy(g_depth):
@@ -784,62 +890,24 @@ class _RasterizeLit(torch.autograd.Function):
             # the adjoint of the output epilogue (un-pool, un-flip, CHW -> HWC) writes the rgb / alpha gradients straight
             # as the edge gradient's per-pixel records (what d3m_backward_pixel_map would pack from gradient maps: one
             # pass over the pixels instead of two, no [B,S,S,3] / [B,S,S] gradient maps); the depth gradient as a map
-            g_rgb_map = g_alpha_map = None
             g_depth_map = torch.empty(B, S, S, dtype=torch.float32, device=dev) if rd else None
-            records = (torch.empty(B, S, S, 4, dtype=torch.float32, device=dev),
-                       torch.empty(B, S, S, 2, dtype=torch.float32, device=dev),
-                       torch.empty(2, B, 2, S, dtype=torch.int32, device=dev))
+            records = _pixel_records(B, S, dev)
             _lib.check(L.d3m_output_epilogue_backward_records(
                 _lib.ptr(f32c(g_rgb)), _lib.ptr(f32c(g_alpha) if ra else None), _lib.ptr(f32c(g_depth) if rd else None),
                 _lib.ptr(m["face_index_map"]), _lib.ptr(m["rgb_map"]), _lib.ptr(m["alpha_map"] if ra else None),
-                _lib.ptr(records[0]), _lib.ptr(records[1]), _lib.ptr(records[2][0]), _lib.ptr(records[2][1]),
-                _lib.ptr(g_depth_map), B, S, int(aa), _lib.stream_ptr()), "d3m_output_epilogue_backward_records")
+                _lib.ptr(records.edge_grad), _lib.ptr(records.edge_dot), _lib.ptr(records.extents[0]),
+                _lib.ptr(records.extents[1]), _lib.ptr(g_depth_map), B, S, int(st.aa), _lib.stream_ptr()),
+                "d3m_output_epilogue_backward_records")
         else:       # g_rgb is the gradient of the scalar objective; the maps were left by forward, minus their scalars
-            scratch, g_depth_map = fit[4], fit[6][3]
-            g_rgb_map = g_alpha_map = None              # they exist as per-pixel records (fit[6][:3])
+            g_depth_map = fit.records.grad_depth        # (the rgb / alpha gradients exist as per-pixel records)
             grad_loss = f32c(g_rgb).reshape(1)
         # K4 -> textures (separate buffers) -> K6, as NR/rasterize.py:141-151; both face gradients land in grad_sv,
         # and both passes run over the compacted list of the faces that own a pixel.  The edge gradient (K4: ~8
         # latency-bound launches) and the gathered texture / depth pass (K5+K6) are independent -- they only meet in
         # the float atomics on grad_sv -- so the second runs on a stream of its own, per view group.
         vis = m["visibility"]
-        need_tex = ctx.needs_input_grad[3]
-        need_vert = ctx.needs_input_grad[1] and idr != 0
-        gathered = need_tex or need_vert
-        grad_textures = grad_vertices = grad_light = None
         tex_shared, light_shared = textures.shape[0] == 1, Bl == 1
-        gt_g = gl_g = None
-        sink = ctx.grad_sink
-        if pre is not None and (pre["gathered"] != gathered or G != 1):
-            pre = None
-            if grad_sv is not None:
-                _lib.zero_(grad_sv)                  # (cannot happen: the same inputs decide both; stay correct anyway)
-        if gathered and need_vert:
-            grad_vertices = pre["grad_vertices"] if pre is not None else \
-                (sink[0] if (sink is not None and ctx.camera is not None) else torch.empty_like(vertices))
-        if gathered:
-            if pre is not None:
-                if tex_shared:
-                    gt_g = [pre["gt"]]
-                else:
-                    grad_textures, gt_g = pre["gt"], [pre["gt"]]
-                if need_vert:
-                    gl_g = [pre["gl"]]
-                    if not light_shared:
-                        grad_light = pre["gl"]
-            else:
-                if tex_shared:
-                    gt_g = [sink[1] if (sink is not None and sink[1] is not None and G == 1) else torch.empty_like(textures)
-                            for _ in groups]
-                else:
-                    grad_textures = torch.empty_like(textures)
-                    gt_g = [grad_textures[lo:hi] for lo, hi in groups]
-                if need_vert:
-                    if light_shared:
-                        gl_g = [torch.empty_like(light) for _ in groups]
-                    else:
-                        grad_light = torch.empty_like(light)
-                        gl_g = [grad_light[lo:hi] for lo, hi in groups]
+        sink = st.grad_sink
         # DETERMINISTIC (d3m_set_deterministic / D3M_DETERMINISTIC=1; one pipeline, one shared topology).  Everything the
         # pass adds up with float atomics in arrival order is produced per (view, face) by the lanes that own it and then
         # summed in a FIXED order instead:
@@ -851,71 +919,42 @@ class _RasterizeLit(torch.autograd.Function):
         #   the visibility list in ascending order (the library, same switch); every kernel on one stream.
         # The camera's adjoint and the sum of the per-view texel gradients already add in view order.  What stays
         # unordered: the plan's fallback for an undersized workspace (k_edge_overflow) -- see DESIGN.md section 6.
-        det = _deterministic()
-        if det:
-            _RasterizeLit._deterministic_supported(G, tri, vertices, ts, idr, ctx.needs_input_grad[1])
-            pre = None
+        # Forward decided it (st.det, checked above against the switch) and, with it, one stream and no `pre`.
         cur = torch.cuda.current_stream()
-        serial = G == 1 and (det or getattr(ctx, "force_serial", False) or _serial_branches(B, Ft, S))
         mains = [cur] + [_side_stream(dev, k) for k in range(1, G)]
-        auxs = [_side_stream(dev, G + k, serial) for k in range(G)]
+        auxs = [_side_stream(dev, G + k, st.serial) for k in range(G)]
         plan_ready = m["plan_ready"]
         # THE EDGE GRADIENT STAYS ON THE PLAN'S STREAM (round 4).  With the forward's branch left open (plan_ready), the
         # step's critical chain is coverage -> visibility list -> plan -> line walk -> gather: all but the first on the side
         # stream if the line walk is issued there too, right behind the plan's last kernel, instead of on the forking stream
         # behind an event -- a replayed graph pays ~9 us for every cross-queue edge whose producer has only just finished
         # (trace of the 4-view shard: scatter ends 190.0, the line walk starts 198.6).  The gathered texture / depth pass
-        # takes the forking stream then; it only needs the visibility list (an event behind d3m_visibility).
-        swap = plan_ready is not None and G == 1 and auxs[0] is not cur and \
-            (m.get("vis_ready") is not None or m.get("vis_on_main", False))
+        # takes the forking stream then; it only needs the visibility list, which forward built on that stream in front of
+        # the fork (ONE FORK, BEHIND THE VISIBILITY LIST): no event.
+        swap = st.plan_open and G == 1 and auxs[0] is not cur
         s_edges = [auxs[0]] if swap else mains
         s_gath = [mains[0]] if swap else auxs
         # The backward pass's clears -- the two vertex accumulators and what the gathered pass needs zeroed -- as ONE launch
         # in front of the branches (round 4: one here and one inside d3m_backward_textures_lit), or none at all (`pre`).
-        lit_ws, lit_flags = None, 0
-        if pre is not None:
-            if gathered:
-                lit_ws, lit_flags = [pre["lit_ws"]], _lib.PRECLEARED
-        else:
-            ranges = [_lib.tensor_range(grad_sv)] if grad_sv is not None else []
-            if grad_vertices is not None:
-                ranges.append(_lib.tensor_range(grad_vertices))
-            det_light = det_gl = det_k4 = det_k6 = None
-            if det:
-                # per-VIEW light gradients (one contribution per entry), the two per-face arrays of K4 and K6
-                Fp_ = 2 * Ft if fill_back else Ft
-                if gathered and need_vert:
-                    det_light = light.expand(B, Fp_, 3).contiguous() if light_shared else light
-                    det_gl = torch.empty(B, Fp_, 3, dtype=torch.float32, device=dev)
-                if need_geom:
-                    det_k4 = torch.empty(B, Fp_, 3, 3, dtype=torch.float32, device=dev)
-                    ranges.append(_lib.tensor_range(det_k4))
-                    if rd:
-                        det_k6 = torch.empty(B, Fp_, 3, 3, dtype=torch.float32, device=dev)
-                        ranges.append(_lib.tensor_range(det_k6))
-            if gathered and G == 1:
-                with torch.cuda.stream(s_gath[0]):     # (scratch is cached per stream: the stream the pass will run on)
-                    ws1 = ops._workspace("lit", L.d3m_backward_textures_lit_workspace_bytes(B, Ft, int(fill_back), ts), dev)
-                ranges += _lit_clear_ranges(L, grad_textures if grad_textures is not None else gt_g[0], textures.shape[0],
-                                            det_gl if det_gl is not None else (gl_g[0] if gl_g is not None else None),
-                                            B if det_gl is not None else light.shape[0], B, Ft, fill_back, ts, ws1)
-                lit_ws, lit_flags = [ws1], _lib.PRECLEARED
-            _lib.zero_raw(ranges)
+        if bufs is None:
+            bufs = _backward_buffers(st, vertices, textures, light, B, V, Ft, ts, ws_stream=s_gath[0])
+            _lib.zero_raw(bufs.clears)
+        grad_sv, grad_vertices, grad_textures, grad_light = bufs.grad_sv, bufs.grad_vertices, bufs.grad_textures, bufs.grad_light
+        gt_g, gl_g, det_gl, det_k4, det_k6 = bufs.gt_g, bufs.gl_g, bufs.det_gl, bufs.det_k4, bufs.det_k6
+        lit_flags = _lib.PRECLEARED if bufs.lit_ws is not None else 0
         for k in range(G):
             if mains[k] is not cur:
                 mains[k].wait_stream(cur)
-            if gathered or plan_ready is not None:
+            if gathered or st.plan_open:
                 auxs[k].wait_stream(cur)
             if swap:
-                if m.get("vis_ready") is not None:
-                    mains[k].wait_event(m["vis_ready"])
                 # the line walk reads the plan.  Backward normally runs under the stream forward forked from (autograd
                 # restores it), so auxs[k] IS the stream the plan was recorded on and needs no edge -- and must not get
                 # one: a wait on an event of the waiting stream itself inside a capture makes hipStreamEndCapture segfault
                 # (ROCm 7.2).  Driven under another current stream the side stream is another object: then it waits.
                 if auxs[k].cuda_stream != m["plan_stream"].cuda_stream:
                     auxs[k].wait_event(plan_ready[k])
-            elif plan_ready is not None:
+            elif st.plan_open:
                 mains[k].wait_event(plan_ready[k])       # the forward's open branch: visibility + plan of this group
         for k, (lo, hi) in enumerate(groups):
             Bg = hi - lo
@@ -928,43 +967,31 @@ class _RasterizeLit(torch.autograd.Function):
             if fit is not None:
                 # (the deferred finish belongs to the objective THIS node evaluated -- its own or the registered one -- not to
                 #  a foreign state a linked loss built on the finished images)
-                own_fit = fit is ctx.fit or fit is getattr(ctx, "hint_state", None)
-                unscaled = _RasterizeLit._fit_struct(fit, k, lo, hi, grad_loss,
-                                                     flags=getattr(ctx, "fit_flags", 0) if own_fit else 0)
-            elif records is not None:           # final records: no scratch, no scalars to apply
-                unscaled = _lib.D3MFitTargets(None, None, None, None, None, None, None, None, None, None, None,
-                                              _lib.ptr(records[0][lo:hi]), _lib.ptr(records[1][lo:hi]),
-                                              _lib.ptr(records[2][0][lo:hi]), _lib.ptr(records[2][1][lo:hi]), 0)
+                deferred = st.finish_deferred and (fit is st.fit or fit is st.hint)
+                unscaled = fit.struct(k, lo, hi, grad_loss, flags=_lib.FIT_FINISH_DEFERRED if deferred else 0)
+            elif records is not None:
+                unscaled = records.struct(lo, hi)
             if gathered:
                 with torch.cuda.stream(s_gath[k]):
-                    ws = lit_ws[k] if lit_ws is not None else \
+                    ws = bufs.lit_ws if bufs.lit_ws is not None else \
                         ops._workspace("lit", L.d3m_backward_textures_lit_workspace_bytes(Bg, Ft, int(fill_back), ts), dev)
-                    # the depth gradient (K6, add) rides along in the same pass over the faces' pixels
-                    if det:     # per-view light gradient, K6 into its own per-face array: no vertex target (see DETERMINISTIC)
-                        light_d = det_light if det_light is not None else light_g
-                        _lib.check(L.d3m_backward_textures_lit(
-                            _lib.ptr(faces), _lib.ptr(tex_g), tex_g.shape[0], _lib.ptr(light_d), light_d.shape[0],
-                            _lib.ptr(fi_g), _lib.ptr(wm_g), _lib.ptr(dm_g), None, _lib.ptr(gt_g[k]), _lib.ptr(det_gl),
-                            _lib.ptr(g_depth_map) if rd_geom else None, _lib.ptr(det_k6) if rd_geom else None, Bg, Ft,
-                            int(fill_back), S, ts, eps, _lib.ptr(ws), ws.numel(), None, _lib.ptr(vis[k]),
-                            ctypes.byref(unscaled) if unscaled is not None else None, lit_flags, _lib.stream_ptr()),
-                            "d3m_backward_textures_lit")
-                    else:
-                        _lib.check(L.d3m_backward_textures_lit(
-                            _lib.ptr(faces[lo:hi]), _lib.ptr(tex_g), tex_g.shape[0], _lib.ptr(light_g), light_g.shape[0],
-                            _lib.ptr(fi_g), _lib.ptr(wm_g), _lib.ptr(dm_g), _lib.ptr(_bslice(g_rgb_map, lo, hi)),
-                            _lib.ptr(gt_g[k]), _lib.ptr(gl_g[k]) if gl_g is not None else None,
-                            _lib.ptr(g_depth_map[lo:hi]) if rd_geom else None, None, Bg, Ft, int(fill_back), S, ts, eps,
-                            _lib.ptr(ws), ws.numel(), ctypes.byref(target) if rd_geom else None, _lib.ptr(vis[k]),
-                            ctypes.byref(unscaled) if unscaled is not None else None, lit_flags, _lib.stream_ptr()),
-                            "d3m_backward_textures_lit")
+                    # the depth gradient (K6, add) rides along in the same pass over the faces' pixels.  Deterministic:
+                    # per-view light gradient, K6 into its own per-face array, no vertex target (see DETERMINISTIC)
+                    light_d = bufs.det_light if bufs.det_light is not None else light_g
+                    gl_k = det_gl if det else (gl_g[k] if gl_g is not None else None)
+                    _lib.check(L.d3m_backward_textures_lit(
+                        _lib.ptr(faces[lo:hi]), _lib.ptr(tex_g), tex_g.shape[0], _lib.ptr(light_d), light_d.shape[0],
+                        _lib.ptr(fi_g), _lib.ptr(wm_g), _lib.ptr(dm_g), None, _lib.ptr(gt_g[k]), _lib.ptr(gl_k),
+                        _lib.ptr(g_depth_map[lo:hi]) if rd_geom else None, _lib.ptr(det_k6), Bg, Ft, int(fill_back), S, ts,
+                        eps, _lib.ptr(ws), ws.numel(), ctypes.byref(target) if (rd_geom and not det) else None,
+                        _lib.ptr(vis[k]), ctypes.byref(unscaled) if unscaled is not None else None, lit_flags,
+                        _lib.stream_ptr()), "d3m_backward_textures_lit")
             if G == 1:
                 yield "textures"        # (one pipeline: the texture side is complete in the order of its stream)
             if need_geom:
                 with torch.cuda.stream(s_edges[k]):
                     ops.backward_pixel_map(faces[lo:hi], fi_g, m["rgb_map"][lo:hi], m["alpha_map"][lo:hi] if ra else None,
-                                           _bslice(g_rgb_map, lo, hi), _bslice(g_alpha_map, lo, hi) if ra else None,
-                                           det_k4 if det else None, S, eps, True, ra,
+                                           None, None, det_k4, S, eps, True, ra,
                                            vertex_target=None if det else target, visibility=vis[k], unscaled=unscaled,
                                            edge_plan=m["edge_plan"][k])
                     if det:     # K4's and K6's per-face arrays -> the screen-space gradient, per vertex in a fixed order
@@ -977,9 +1004,7 @@ class _RasterizeLit(torch.autograd.Function):
         def light_to_vertices(grad_light):
             # the light gradient -> world-space vertices through the face normals
             if det:     # the views' gradients summed in view order (torch's reduction), the adjoint gathered per vertex
-                total = det_gl.sum(0) if light_shared else None
-                if total is None:
-                    raise NotImplementedError("deterministic mode: one shared mesh")
+                total = det_gl.sum(0)           # (one shared mesh: _deterministic_supported)
                 adj_off, adj_items = vertex_adjacency(tri, V)
                 _lib.check(L.d3m_face_light_backward_gather(
                     _lib.ptr(vertices), _lib.ptr(tri), _lib.ptr(adj_off), _lib.ptr(adj_items), _lib.ptr(total),
@@ -994,7 +1019,7 @@ class _RasterizeLit(torch.autograd.Function):
         # One pipeline on one stream with the camera inside the node: the light's adjoint and the camera's are the step's last
         # two kernels -- ONE launch then (d3m_lit_back: both add into the zeroed grad_vertices with float atomics).  With
         # branches the light's adjoint runs beside the line walk instead (below), where it costs the step nothing.
-        fused_tail = serial and G == 1 and gathered and need_vert and ctx.camera is not None and not det
+        fused_tail = st.serial and G == 1 and gathered and need_vert and st.camera is not None and not det
         light_done = fused_tail
         if gathered and need_vert and G == 1 and not fused_tail:
             # one pipeline: straight behind the gathered pass on its branch, beside the line walk, not behind the join
@@ -1004,13 +1029,13 @@ class _RasterizeLit(torch.autograd.Function):
         # ... and so does the camera's adjoint, the step's last kernel, behind the gather: the side stream waits for the
         # forking stream's (shorter, by then finished) chain instead of the other way round, and the final join is the
         # end of the step
-        tail_on_side = swap and gathered and ctx.camera is not None
+        tail_on_side = swap and gathered and st.camera is not None
         for k in range(G):
             if mains[k] is not cur:
                 cur.wait_stream(mains[k])
             if tail_on_side:
                 auxs[k].wait_stream(cur)
-            elif gathered or plan_ready is not None:
+            elif gathered or st.plan_open:
                 cur.wait_stream(auxs[k])
         if gathered:
             # shared textures / light: the groups' sums add up (a group's pass already summed over its views)
@@ -1027,7 +1052,7 @@ class _RasterizeLit(torch.autograd.Function):
                 # d3m_backward_depth_map takes final maps: the fused objective left sign(depth - target) * mask, which
                 # still lacks grad_loss / sum(mask) (GradScale::get, d3m_device.h); totals[2] of the scratch holds that
                 # sum (the same in every group: with more than one the normaliser is the batch's mask_sum)
-                g_depth_map = g_depth_map * (grad_loss / fit[7])              # mask_sum: set whenever gradients are wanted
+                g_depth_map = g_depth_map * (grad_loss / fit.mask_sum)              # mask_sum: set whenever gradients are wanted
             grad_faces = torch.zeros_like(faces)
             ops.backward_depth_map(faces, m["depth_map"], m["face_index_map"], m["face_inv_map"], m["weight_map"],
                                    g_depth_map, grad_faces, S)
@@ -1035,16 +1060,16 @@ class _RasterizeLit(torch.autograd.Function):
                                                 Ft, int(fill_back), _lib.stream_ptr()), "d3m_scatter_face_grads")
         if fused_tail:
             from . import cameras
-            cam, _keep = cameras._camera_struct(ctx.camera, dev)
+            cam, _keep = cameras._camera_struct(st.camera, dev)
             _lib.check(L.d3m_lit_back(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam), _lib.ptr(grad_sv),
                                       _lib.ptr(grad_vertices), B, V, _lib.ptr(tri), tri.shape[0], Ft, int(fill_back),
                                       _lib.ptr(gl_g[0] if light_shared else grad_light), Bl, ia, idr, _vec3_host(ca),
                                       _vec3_host(cd), _vec3_host(direction), _lib.stream_ptr()), "d3m_lit_back")
             grad_sv = None
-        elif ctx.camera is not None and need_geom:
+        elif st.camera is not None and need_geom:
             # the camera's adjoint joins the light's in the same buffer (or writes it, when there is none)
             from . import cameras
-            cam, _keep = cameras._camera_struct(ctx.camera, dev)
+            cam, _keep = cameras._camera_struct(st.camera, dev)
             if grad_vertices is None:
                 grad_vertices = sink[0] if sink is not None else torch.empty_like(vertices)
                 fn, what = L.d3m_camera_backward, "d3m_camera_backward"
@@ -1057,6 +1082,13 @@ class _RasterizeLit(torch.autograd.Function):
         if tail_on_side:
             cur.wait_stream(auxs[0])
         return (grad_sv if need_geom else None, grad_vertices if need_geom else None, None, grad_textures) + (None,) * 17
+
+
+# What _RasterizeMeshModes' forward decided and left for backward: configuration, the deterministic switch (checked in backward),
+# the camera (+ what its structs point into), the pass's maps and backward's accumulator, zeroed by forward (pre; one use)
+_MeshModesState = dataclasses.make_dataclass("_MeshModesState", (
+    "aa eps fill_back ra rd det camera keep faces face_index_map weight_map depth_map alpha_map visibility plan pre").split(),
+    eq=False)
 
 
 class _RasterizeMeshModes(torch.autograd.Function):
@@ -1115,13 +1147,11 @@ class _RasterizeMeshModes(torch.autograd.Function):
         if need_grad:
             pre = torch.empty(B * V * 3 + 64, dtype=torch.float32, device=dev)
             clears.append(_lib.tensor_range(pre))
-        zp = (ctypes.c_void_p * max(1, len(clears)))(*[c[0] for c in clears])
-        zb = (ctypes.c_size_t * max(1, len(clears)))(*[c[1] for c in clears])
         zero3 = _vec3_host((0.0, 0.0, 0.0))
         _lib.check(L.d3m_lit_front(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam),
                                    ctypes.byref(basis) if basis is not None else None, _lib.ptr(sv), B, V, _lib.ptr(tri),
-                                   tri.shape[0], Ft, int(bool(fill_back)), None, 0, 0.0, 0.0, zero3, zero3, zero3, zp, zb,
-                                   len(clears), _lib.stream_ptr()), "d3m_lit_front")
+                                   tri.shape[0], Ft, int(bool(fill_back)), None, 0, 0.0, 0.0, zero3, zero3, zero3,
+                                   *_front_clears(clears), _lib.stream_ptr()), "d3m_lit_front")
         # without anti-aliasing the output images are the maps with their rows reversed: coverage's last pass writes them too
         # (no epilogue pass); with it, the 2x2 pooling is a pass of its own
         in_pass = not anti_aliasing
@@ -1141,12 +1171,12 @@ class _RasterizeMeshModes(torch.autograd.Function):
             if plan is not None:
                 _lib.check(L.d3m_edge_plan(_lib.ptr(faces), _lib.ptr(fi), _lib.ptr(vis), _lib.ptr(plan), plan.numel(), B, Fp, S,
                                            flags_plan, _lib.stream_ptr()), "d3m_edge_plan")
-        if need_grad and (return_alpha != return_depth) and tri.shape[0] == 1 and _deterministic():
+        det = bool(need_grad) and _deterministic()
+        if det and (return_alpha != return_depth) and tri.shape[0] == 1:
             vertex_adjacency(tri, V)            # (the deterministic backward pass's CSR adjacency: built outside any capture of it)
-        ctx.cfg = (B, V, Ft, Fp, S, bool(anti_aliasing), float(eps), bool(fill_back), bool(return_alpha), bool(return_depth))
-        ctx.camera, ctx.keep = camera, (cam_keep, basis_keep)
-        ctx.maps = (faces, fi, wm, dm, alpha_map, vis, plan)
-        ctx.pre = pre
+        ctx.state = _MeshModesState(aa=bool(anti_aliasing), eps=float(eps), fill_back=bool(fill_back), ra=bool(return_alpha), rd=bool(return_depth), det=det,
+                                    camera=camera, keep=(cam_keep, basis_keep), faces=faces, face_index_map=fi,
+                                    weight_map=wm, depth_map=dm, alpha_map=alpha_map, visibility=vis, plan=plan, pre=pre)
         ctx.save_for_backward(vertices, tri)
         empty = torch.tensor([])
         return (alpha if return_alpha else empty, depth if return_depth else empty)
@@ -1155,11 +1185,17 @@ class _RasterizeMeshModes(torch.autograd.Function):
     def backward(ctx, g_alpha, g_depth):
         from . import cameras
         L = _lib.lib()
+        st = ctx.state
+        _check_deterministic(st.det)
         vertices, tri = ctx.saved_tensors
-        B, V, Ft, Fp, S, aa, eps, fill_back, ra, rd = ctx.cfg
-        faces, fi, wm, dm, alpha_map, vis, plan = ctx.maps
+        aa, eps, fill_back, ra, rd = st.aa, st.eps, st.fill_back, st.ra, st.rd
+        faces, fi, wm, dm, alpha_map = st.faces, st.face_index_map, st.weight_map, st.depth_map, st.alpha_map
+        vis, plan = st.visibility, st.plan
+        (B, Fp), S, V, Ft = faces.shape[:2], fi.shape[1], vertices.shape[1], tri.shape[1]
         dev = vertices.device
-        acc, ctx.pre = getattr(ctx, "pre", None), None
+        # (the fixed-order sums cover one shared topology; per-view topologies keep their float atomics: DESIGN.md section 6)
+        ordered = st.det and tri.shape[0] == 1
+        acc, st.pre = st.pre, None
         if acc is None:
             acc = torch.empty(B * V * 3 + 64, dtype=torch.float32, device=dev)
             _lib.zero_raw([_lib.tensor_range(acc)])
@@ -1170,13 +1206,10 @@ class _RasterizeMeshModes(torch.autograd.Function):
             # silhouettes only: the edge gradient reads the image's gradient where it is -- through the row flip and the
             # pooling's adjoint -- and the owners from face_index_map; no per-pixel records (d3m_edge_grad.h, "DIRECT")
             g_img = f32c(g_alpha)
-            unscaled = _lib.D3MFitTargets(None, None, None, None, None, None, None, _lib.ptr(g_img), None, None, None,
-                                          None, None, None, None,
-                                          _lib.GRAD_OF_OUTPUT_IMAGE | (_lib.FIT_POOLED if aa else 0))
-            if tri.shape[0] == 1 and _deterministic():
+            unscaled = _image_grad_struct(g_img, aa)
+            if ordered:
                 # DETERMINISTIC (as the lit node's): K4 into its own per-face array (plain stores), summed per vertex in a
-                # fixed order over the index tensor's CSR adjacency -- bit-identical runs.  (One shared topology; per-view
-                # topologies keep their float atomics: DESIGN.md section 6.)
+                # fixed order over the index tensor's CSR adjacency -- bit-identical runs.
                 det_k4 = torch.empty(B, Fp, 3, 3, dtype=torch.float32, device=dev)
                 _lib.zero_raw([_lib.tensor_range(det_k4)])
                 ops.backward_pixel_map(faces, fi, None, alpha_map, None, None, det_k4, S, eps, False, True,
@@ -1190,20 +1223,17 @@ class _RasterizeMeshModes(torch.autograd.Function):
         elif ra:
             # the adjoint of the output epilogue writes the alpha gradient straight as the edge gradient's per-pixel records
             # (and the depth gradient as the map K6 reads)
-            records = (torch.empty(B, S, S, 4, dtype=torch.float32, device=dev),
-                       torch.empty(B, S, S, 2, dtype=torch.float32, device=dev),
-                       torch.empty(2, B, 2, S, dtype=torch.int32, device=dev))
+            records = _pixel_records(B, S, dev)
             _lib.check(L.d3m_output_epilogue_backward_records(
                 None, _lib.ptr(f32c(g_alpha)), _lib.ptr(f32c(g_depth) if rd else None), _lib.ptr(fi), None, _lib.ptr(alpha_map),
-                _lib.ptr(records[0]), _lib.ptr(records[1]), _lib.ptr(records[2][0]), _lib.ptr(records[2][1]),
-                _lib.ptr(g_depth_map), B, S, int(aa), _lib.stream_ptr()), "d3m_output_epilogue_backward_records")
-            unscaled = _lib.D3MFitTargets(None, None, None, None, None, None, None, None, None, None, None,
-                                          _lib.ptr(records[0]), _lib.ptr(records[1]), _lib.ptr(records[2][0]),
-                                          _lib.ptr(records[2][1]), 0)
+                _lib.ptr(records.edge_grad), _lib.ptr(records.edge_dot), _lib.ptr(records.extents[0]),
+                _lib.ptr(records.extents[1]), _lib.ptr(g_depth_map), B, S, int(aa), _lib.stream_ptr()),
+                "d3m_output_epilogue_backward_records")
+            unscaled = records.struct(0, B)
             ops.backward_pixel_map(faces, fi, None, alpha_map, None, None, None, S, eps, False, True, vertex_target=target,
                                    visibility=vis, unscaled=unscaled, edge_plan=plan)
         k6_flags = _lib.PRECLEARED
-        det_depth = rd and not ra and tri.shape[0] == 1 and _deterministic()
+        det_depth = rd and not ra and ordered
         if det_depth:
             # DETERMINISTIC, depth mode: the adjoint of the output epilogue as a map, K6 gathered per face into its own array by
             # the reference-shaped operator (in this mode without its per-pixel fallback for large faces: d3m_backward_depth_map),
@@ -1228,7 +1258,7 @@ class _RasterizeMeshModes(torch.autograd.Function):
                                                      _lib.ptr(g_depth_map), B, Fp, S, ctypes.byref(target), _lib.ptr(vis),
                                                      _lib.ptr(counter), k6_flags, _lib.stream_ptr()),
                        "d3m_backward_depth_map_mesh")
-        cam, _keep = cameras._camera_struct(ctx.camera, dev)
+        cam, _keep = cameras._camera_struct(st.camera, dev)
         grad_vertices = torch.empty_like(vertices)
         _lib.check(L.d3m_camera_backward(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam), _lib.ptr(grad_sv),
                                          _lib.ptr(grad_vertices), B, V, _lib.stream_ptr()), "d3m_camera_backward")
@@ -1246,11 +1276,13 @@ def rasterize_mesh_modes(vertices, tri, camera, fill_back, image_size, anti_alia
 
 class _ManualContext:
     """What _RasterizeLit.forward / _backward_halves use of an autograd context, for calling them WITHOUT the autograd
-    engine (LitFitManual): needs_input_grad, save_for_backward / saved_tensors, free attributes."""
+    engine (LitFitManual): needs_input_grad, save_for_backward / saved_tensors, the node's state.  Forward runs every kernel
+    of a node given this context on one stream."""
 
     def __init__(self, needs_input_grad):
         self.needs_input_grad = tuple(needs_input_grad)
         self.saved_tensors = ()
+        self.state = self.maps = None
 
     def save_for_backward(self, *tensors):
         self.saved_tensors = tuple(tensors)
@@ -1274,15 +1306,11 @@ class LitFitManual:
 
     def forward(self, vertices, tri, textures, light_cfg, fill_back, targets, image_size, near, far, eps, background_color,
                 camera, grad_sink=None, images_out=None, anti_aliasing=False):
-        fit = tuple(targets)
-        if images_out is not None:
-            fit = (fit + (None,))[:5] + (tuple(images_out),)
         self._ctx = _ManualContext(self._needs)
-        self._ctx.force_serial = True       # every kernel on the caller's stream: the step is cut BETWEEN kernels of one stream
         with torch.no_grad():
             return _RasterizeLit.forward(self._ctx, None, vertices, tri, textures, light_cfg, fill_back, image_size,
-                                         bool(anti_aliasing), near, far, eps, background_color, True, True, True, fit, 1,
-                                         False, camera, grad_sink)
+                                         bool(anti_aliasing), near, far, eps, background_color, True, True, True,
+                                         (targets, images_out), 1, False, camera, grad_sink)
 
     def backward_texture_side(self, grad_loss):
         with torch.no_grad():
@@ -1375,12 +1403,10 @@ def rasterize_lit_fit(screen_vertices, vertices, tri, textures, light_cfg, fill_
     ALL ranks' views when these views are one shard of a camera-sharded fit, so that values and gradients add up): the sums are taken where the images are produced and the gradient is written straight into the
     internal-resolution maps, so the images and their gradients never exist in memory.  Same value and gradients as
     core.losses.multiview_fit_loss(*rasterize_lit(...), ...)."""
-    fit = tuple(targets)
-    if images_out is not None:          # (rgb, depth, alpha) buffers the same pass fills with the images render() returns
-        fit = (fit + (None,))[:5] + (tuple(images_out),)
+    # (images_out: (rgb, depth, alpha) buffers the same pass fills with the images render() returns)
     return _RasterizeLit.apply(screen_vertices, vertices, tri, textures, light_cfg, fill_back, image_size,
-                               bool(anti_aliasing), near, far, eps, background_color, True, True, True, fit, view_groups,
-                               defer_plan_join, camera, grad_sink)
+                               bool(anti_aliasing), near, far, eps, background_color, True, True, True,
+                               (targets, images_out), view_groups, defer_plan_join, camera, grad_sink)
 
 
 def rasterize_rgbad(

@@ -1489,6 +1489,34 @@ def test_deterministic_mode_refuses_what_it_does_not_cover():
     assert _rel_max(grads[0], vv.grad) < 1e-6
 
 
+@pytest.mark.parametrize("node", ["lit", "silhouettes"])
+def test_deterministic_switch_must_enclose_backward(node):
+    """... and the switch must hold from a node's forward pass to its backward pass: forward builds the ascending visibility
+    list and the CSR adjacency (or not), and the library reads the switch again at launch time, so a backward pass outside
+    the deterministic() block that enclosed its forward pass -- or inside one that did not -- raises instead of running
+    half deterministic.  A pass with both inside still runs."""
+    from deep3dmap_amd import _lib
+    vs, tris, texs = (t.cuda() for t in _scene(B=1, n=10))            # one shared mesh: what the mode covers
+    r = _nr().Renderer(camera_mode="look_at", image_size=32, anti_aliasing=False)
+    r.eye = [0.3, 0.4, -2.5]
+
+    def forward():
+        v = vs.clone().requires_grad_(True)
+        return v, (r(v, tris, texs)[0] if node == "lit" else r.render_silhouettes(v, tris)).sum()
+
+    with _lib.deterministic():
+        _, loss = forward()
+    with pytest.raises(RuntimeError, match="must enclose backward"):
+        loss.backward()
+    _, loss = forward()
+    with _lib.deterministic():
+        with pytest.raises(RuntimeError, match="must enclose backward"):
+            loss.backward()
+        v, loss = forward()
+        loss.backward()
+    assert float(v.grad.abs().max()) > 0
+
+
 def test_second_backward_over_one_forward_result():
     """One render(), two backward passes (retain_graph): the plan built in forward is walked twice, and whatever the first
     walk leaves in the plan's blob and the node's buffers must not reach the second.  Both passes give the same gradients."""
