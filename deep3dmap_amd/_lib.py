@@ -28,6 +28,12 @@ class D3MVertexTarget(ctypes.Structure):
                 ("fill_back", _I)]
 
 
+class D3MLight(ctypes.Structure):
+    """d3m_light (include/d3m_raster.h): the light's five parameters as device arrays of batch 1 or B."""
+    _fields_ = [("intensity_ambient", _P), ("intensity_directional", _P), ("color_ambient", _P), ("color_directional", _P),
+                ("direction", _P), ("ia_batch", _I), ("id_batch", _I), ("ca_batch", _I), ("cd_batch", _I), ("dir_batch", _I)]
+
+
 class D3MFitTargets(ctypes.Structure):
     _fields_ = [("rgb_target", _P), ("depth_target", _P), ("alpha_target", _P), ("mask", _P), ("scratch", _P),
                 ("loss", _P), ("grad_rgb_map", _P), ("grad_alpha_map", _P), ("grad_depth_map", _P), ("grad_loss", _P),
@@ -115,6 +121,12 @@ _SIGNATURES = {
     "d3m_uv_unwrap_backward": (_I, [_P] * 12 + [_I] * 8 + [_P]),
     "d3m_face_light": (_I, [_P, _I, _P, _I, _P, _F, _F, _P, _P, _P, _I, _I, _I, _I, _P]),
     "d3m_face_light_backward": (_I, [_P, _I, _P, _I, _P, _P, _F, _F, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "d3m_face_light_dev": (_I, [_P, _I, _P, _I, _P, ctypes.POINTER(D3MLight), _I, _I, _I, _I, _P]),
+    "d3m_face_light_backward_dev": (_I, [_P, _I, _P, _I, _P, _P, ctypes.POINTER(D3MLight), _I, _I, _I, _I, _P]),
+    "d3m_face_light_backward_gather_dev": (_I, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(D3MLight), _I, _I, _I, _P]),
+    "d3m_light_params_backward_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "d3m_light_params_backward": (_I, [_P, _I, _P, _I, _P, _I, ctypes.POINTER(D3MLight), ctypes.POINTER(D3MLight), _I, _I, _I,
+                                       _P, _SZ, _P]),
     "d3m_forward_texture_sampling_lit": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "d3m_backward_textures_lit_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
     "d3m_render_lit_epilogue": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I,
@@ -128,6 +140,10 @@ _SIGNATURES = {
     "d3m_backward_textures_lit_clear_ranges": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, ctypes.POINTER(_P),
                                                     ctypes.POINTER(_SZ)]),
     "d3m_lit_back": (_I, [_P, _I, ctypes.POINTER(D3MCamera), _P, _P, _I, _I, _P, _I, _I, _I, _P, _I, _F, _F, _P, _P, _P, _P]),
+    "d3m_lit_back_dev": (_I, [_P, _I, ctypes.POINTER(D3MCamera), _P, _P, _I, _I, _P, _I, _I, _I, _P, _I, ctypes.POINTER(D3MLight),
+                              _P]),
+    "d3m_lit_front_dev": (_I, [_P, _I, ctypes.POINTER(D3MCamera), ctypes.POINTER(D3MBasis), _P, _I, _I, _P, _I, _I, _I, _P, _I,
+                               ctypes.POINTER(D3MLight), ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P]),
     "d3m_lit_front": (_I, [_P, _I, ctypes.POINTER(D3MCamera), ctypes.POINTER(D3MBasis), _P, _I, _I, _P, _I, _I, _I, _P, _I,
                            _F, _F, _P, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P]),
     "d3m_output_epilogue": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -335,7 +335,7 @@ class NrRenderer():
         r = self.renderer
         # frames that need no gradient (the usual case: visualisation) are rendered from the image itself: implicit grid
         # topology, texture cubes evaluated in the sampler -- no get_face_idx / get_textures_from_im arrays
-        direct = (self.tex_cube_size == 2 and r.fill_back and r._on_the_fly() and
+        direct = (self.tex_cube_size == 2 and r.fill_back and r._on_the_fly() and r._constant_light() and
                   not (torch.is_grad_enabled() and (vertices.requires_grad or any(im.requires_grad for im in images))))
         out = []
         for im in images:

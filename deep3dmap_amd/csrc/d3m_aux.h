@@ -301,6 +301,26 @@ __device__ __forceinline__ void face_light(const float* f, const LightParams& lp
     if (nrm) { nrm[0] = nx; nrm[1] = ny; nrm[2] = nz; *len = n; *cosv = cs; }
 }
 
+// A light read from DEVICE memory when the kernel runs (d3m_light: learnable or per-view lights; a captured graph reads it
+// at replay).  Every parameter has batch 1 (all views) or one row per view; light_at(.., b) is view b's LightParams, which
+// face_light then evaluates unchanged -- a light that is the same in every view gives the by-value kernels' bits.
+struct DevLight {
+    const float *ia, *id, *ca, *cd, *dir;       // [n], [n], [n,3], [n,3], [n,3]
+    int ia_b, id_b, ca_b, cd_b, dir_b;
+};
+__device__ __forceinline__ LightParams light_at(const LightParams& lp, int) { return lp; }
+__device__ __forceinline__ LightParams light_at(const DevLight& dl, int b) {
+    LightParams lp;
+    lp.ia = dl.ia[dl.ia_b > 1 ? b : 0];
+    lp.id = dl.id[dl.id_b > 1 ? b : 0];
+    const float* ca = dl.ca + (size_t)(dl.ca_b > 1 ? b : 0) * 3;
+    const float* cd = dl.cd + (size_t)(dl.cd_b > 1 ? b : 0) * 3;
+    const float* dir = dl.dir + (size_t)(dl.dir_b > 1 ? b : 0) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { lp.ca[k] = ca[k]; lp.cd[k] = cd[k]; lp.dir[k] = dir[k]; }
+    return lp;
+}
+
 __global__ void __launch_bounds__(256) k_lighting_forward(const float* __restrict__ faces, const float* __restrict__ tex_in,
                                                          float* __restrict__ tex_out, LightParams lp, long n_faces,
                                                          int texels3 /* ts^3*3 */) {

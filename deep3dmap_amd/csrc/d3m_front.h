@@ -217,4 +217,130 @@ __global__ void __launch_bounds__(256) k_lit_back(BackArgs a) {
     }
 }
 
+// ---- the same two launches with the light read from DEVICE memory (DevLight, view b's row for light row b): copies of the
+// kernels above that differ only where the light is read -- the by-value kernels keep their code.
+__global__ void __launch_bounds__(256) k_lit_front_dev(FrontArgs a, DevLight dl) {
+    const unsigned nb_zero = gridDim.x - a.nb_cam - a.nb_light;
+    if (blockIdx.x < nb_zero) {
+        // as k_zero_ranges (d3m_launch.h), over this part's blocks
+        const size_t stride = (size_t)nb_zero * 256, i0 = (size_t)blockIdx.x * 256 + threadIdx.x;
+#pragma unroll
+        for (int k = 0; k < FRONT_RANGES; k++) {
+            const size_t n_words = a.z_words[k];
+            if (n_words == 0) continue;
+            size_t head = ((16u - (unsigned)((uintptr_t)a.z_ptr[k] & 15u)) & 15u) >> 2;     // words up to the 16-byte boundary
+            if (head > n_words) head = n_words;
+            const size_t n4 = (n_words - head) >> 2;
+            uint4* p4 = reinterpret_cast<uint4*>(a.z_ptr[k] + head);
+            if (i0 < head) a.z_ptr[k][i0] = 0;
+            for (size_t i = i0; i < n4; i += stride) p4[i] = make_uint4(0, 0, 0, 0);
+            for (size_t i = head + (n4 << 2) + i0; i < n_words; i += stride) a.z_ptr[k][i] = 0;
+        }
+        return;
+    }
+    const unsigned bx = blockIdx.x - nb_zero;
+    if (bx < a.nb_cam) {
+        __shared__ float s_rot[2][9];
+        const long i0 = (long)bx * 256, n = (long)a.B * a.V;
+        const int b0 = (int)(i0 / a.V);
+        Cam c = a.cam;
+        if (a.basis.eye) {
+            // a block's 256 consecutive (view, vertex) entries belong to one view or (V < 256: to several; then every lane
+            // computes its own) two: lanes 0 and 1 compute the bases of views b0 and b0 + 1
+            const bool two_at_most = a.V >= 256;
+            if (two_at_most) {
+                if (threadIdx.x < 2 && b0 + (int)threadIdx.x < a.B) front_basis(a.basis, b0 + threadIdx.x, s_rot[threadIdx.x]);
+                __syncthreads();
+            }
+            const long i = i0 + threadIdx.x;
+            if (i >= n) return;
+            const int b = (int)(i / a.V), v = (int)(i - (long)b * a.V);
+            float rot[9];
+            if (two_at_most) {
+#pragma unroll
+                for (int k = 0; k < 9; k++) rot[k] = s_rot[b - b0][k];
+            } else {
+                front_basis(a.basis, b, rot);
+            }
+            if (v == 0) {
+#pragma unroll
+                for (int k = 0; k < 9; k++) a.basis.rot_out[(size_t)(a.cam.rot_b > 1 ? b : 0) * 9 + k] = rot[k];   // (one camera for all views: the same nine floats from every view)
+            }
+            c.rot = rot; c.rot_b = 1;               // camera_point reads the basis through the pointer: this lane's copy
+            const float* p = a.vertices + ((size_t)(a.vb > 1 ? b : 0) * a.V + v) * 3;
+            const float in[3] = {p[0], p[1], p[2]};
+            float o[3];
+            camera_point(c, b, in, o, nullptr);
+            a.screen[i * 3 + 0] = o[0]; a.screen[i * 3 + 1] = o[1]; a.screen[i * 3 + 2] = o[2];
+            return;
+        }
+        const long i = i0 + threadIdx.x;
+        if (i >= n) return;
+        const int b = (int)(i / a.V), v = (int)(i - (long)b * a.V);
+        const float* p = a.vertices + ((size_t)(a.vb > 1 ? b : 0) * a.V + v) * 3;
+        const float in[3] = {p[0], p[1], p[2]};
+        float o[3];
+        camera_point(c, b, in, o, nullptr);
+        a.screen[i * 3 + 0] = o[0]; a.screen[i * 3 + 1] = o[1]; a.screen[i * 3 + 2] = o[2];
+        return;
+    }
+    {
+        const long i = (long)(bx - a.nb_cam) * 256 + threadIdx.x;
+        const int Fp = a.faces.num_faces();
+        if (i >= (long)a.light_b * Fp) return;
+        float fc[9], l[3];
+        const int b = (int)(i / Fp);
+        a.faces.load(b, (int)(i % Fp), fc);
+        face_light(fc, light_at(dl, b), l, nullptr, nullptr, nullptr);
+        a.light[3 * i + 0] = l[0]; a.light[3 * i + 1] = l[1]; a.light[3 * i + 2] = l[2];
+        return;
+    }
+}
+
+__global__ void __launch_bounds__(256) k_lit_back_dev(BackArgs a, DevLight dl) {
+    if (blockIdx.x < a.nb_cam) {
+        const long t = (long)blockIdx.x * 256 + threadIdx.x;
+        const bool shared = a.vb <= 1;
+        const long i = shared ? t >> 3 : t;
+        const int sub = shared ? (int)(t & 7) : 0;
+        const long n = (long)(shared ? 1 : a.B) * a.V;
+        const bool on = i < n;
+        const int v = on ? (int)(i % a.V) : 0;
+        const int b_lo = shared ? sub : (int)(i / a.V), b_hi = shared ? a.B : b_lo + 1, b_step = shared ? 8 : 1;
+        float acc[3] = {0, 0, 0};
+        if (on) {
+            const float* p = a.vertices + (size_t)i * 3;
+            const float in[3] = {p[0], p[1], p[2]};
+            for (int b = b_lo; b < b_hi; b += b_step) {
+                const float* gp = a.grad_screen + ((size_t)b * a.V + v) * 3;
+                const float g[3] = {gp[0], gp[1], gp[2]};
+                float gv[3];
+                camera_point_adjoint(a.cam, b, in, g, gv);
+                acc[0] += gv[0]; acc[1] += gv[1]; acc[2] += gv[2];
+            }
+        }
+        if (shared) {
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                acc[k] += dpp_f32<0xB1>(acc[k]);      // quad_perm [1,0,3,2]
+                acc[k] += dpp_f32<0x4E>(acc[k]);      // quad_perm [2,3,0,1]
+                acc[k] += dpp_f32<0x141>(acc[k]);     // row_half_mirror: the other quad of the 8
+            }
+        }
+        if (on && sub == 0) {
+            atomicAdd(&a.grad_vertices[i * 3 + 0], acc[0]);
+            atomicAdd(&a.grad_vertices[i * 3 + 1], acc[1]);
+            atomicAdd(&a.grad_vertices[i * 3 + 2], acc[2]);
+        }
+        return;
+    }
+    // the light's adjoint: k_face_light_backward_dev's body
+    const long i = (long)(blockIdx.x - a.nb_cam) * 256 + threadIdx.x;
+    const int Fp = a.faces.num_faces();
+    if (i >= (long)a.light_b * Fp) return;
+    const LightParams lp = light_at(dl, (int)(i / Fp));
+    if (lp.id == 0) return;
+    face_light_adjoint(a.faces, lp, a.grad_light, a.grad_vertices, a.vb, i);
+}
+
 }  // namespace d3m

@@ -90,6 +90,63 @@ __global__ void __launch_bounds__(256) k_face_light_backward(IndexedFaces fs, Li
     }
 }
 
+// ---- the same two with the light read from DEVICE memory (DevLight: row b of a per-view parameter for light row b).  New
+// kernels beside the by-value ones, which keep their code.
+__global__ void __launch_bounds__(256) k_face_light_dev(IndexedFaces fs, DevLight dl, float* __restrict__ light, int Bm) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int Fp = fs.num_faces();
+    if (i >= (long)Bm * Fp) return;
+    const int b = (int)(i / Fp);
+    float fc[9], l[3];
+    fs.load(b, (int)(i % Fp), fc);
+    face_light(fc, light_at(dl, b), l, nullptr, nullptr, nullptr);
+    light[3 * i + 0] = l[0]; light[3 * i + 1] = l[1]; light[3 * i + 2] = l[2];
+}
+
+// k_face_light_backward's body for entry i = (b, f) of a light with lp.id != 0
+__device__ __forceinline__ void face_light_adjoint(const IndexedFaces& fs, const LightParams& lp, const float* g_light,
+                                                   float* grad_vertices, int vertices_batch, long i) {
+    const float gl[3] = {g_light[3 * i], g_light[3 * i + 1], g_light[3 * i + 2]};
+    if (gl[0] == 0 && gl[1] == 0 && gl[2] == 0) return;
+    const int Fp = fs.num_faces();
+    const int b = (int)(i / Fp), f = (int)(i % Fp);
+    float fc[9], l[3], nrm[3], len, cs;
+    fs.load(b, f, fc);
+    face_light(fc, lp, l, nrm, &len, &cs);
+    if (!(cs > 0)) return;
+    const float g_cos = lp.id * (lp.cd[0] * gl[0] + lp.cd[1] * gl[1] + lp.cd[2] * gl[2]);
+    const float gn[3] = {g_cos * lp.dir[0], g_cos * lp.dir[1], g_cos * lp.dir[2]};
+    float gc[3];
+    if (len > 1e-5f) {
+        const float dot = nrm[0] * gn[0] + nrm[1] * gn[1] + nrm[2] * gn[2];
+        for (int k = 0; k < 3; k++) gc[k] = (gn[k] - nrm[k] * dot) / len;
+    } else {
+        for (int k = 0; k < 3; k++) gc[k] = gn[k] / 1e-5f;
+    }
+    const float a[3] = {fc[0] - fc[3], fc[1] - fc[4], fc[2] - fc[5]};
+    const float bb[3] = {fc[6] - fc[3], fc[7] - fc[4], fc[8] - fc[5]};
+    float ga[3], gb[3];
+    cross3(bb, gc, ga);
+    cross3(gc, a, gb);
+    int ids[3];
+    fs.vertex_ids(b, f, ids);
+    float* base = grad_vertices + (size_t)(vertices_batch > 1 ? b : 0) * fs.V * 3;
+    for (int k = 0; k < 3; k++) {
+        atomicAdd(&base[(size_t)ids[0] * 3 + k], ga[k]);
+        atomicAdd(&base[(size_t)ids[2] * 3 + k], gb[k]);
+        atomicAdd(&base[(size_t)ids[1] * 3 + k], -(ga[k] + gb[k]));
+    }
+}
+__global__ void __launch_bounds__(256) k_face_light_backward_dev(IndexedFaces fs, DevLight dl, const float* __restrict__ g_light,
+                                                                float* __restrict__ grad_vertices, int vertices_batch, int Bm) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int Fp = fs.num_faces();
+    if (i >= (long)Bm * Fp) return;
+    const LightParams lp = light_at(dl, (int)(i / Fp));
+    if (lp.id == 0) return;
+    face_light_adjoint(fs, lp, g_light, grad_vertices, vertices_batch, i);
+}
+
 // The same adjoint GATHERED per vertex in a fixed order (deterministic mode; see k_vertex_gather): one lane per vertex of
 // ONE shared mesh walks the vertex's incident (triangle, corner) pairs and adds what the front copy and the fill_back copy of
 // each triangle send to that corner -- the per-face expressions of k_face_light_backward, recomputed per incident face
@@ -125,6 +182,26 @@ __global__ void __launch_bounds__(256) k_face_light_backward_gather(IndexedFaces
                                                                    float* __restrict__ grad_vertices) {
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= fs.V) return;
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    if (lp.id != 0) {
+        for (int e = adj_offsets[v]; e < adj_offsets[v + 1]; e++) {
+            const int item = adj_items[e], f = item / 3, c = item - 3 * f;
+            face_light_corner_grad(fs, lp, g_light, f, c, acc);
+            if (fs.fill_back) face_light_corner_grad(fs, lp, g_light, fs.Ft + f, 2 - c, acc);
+        }
+    }
+    grad_vertices[3 * (size_t)v + 0] = acc[0]; grad_vertices[3 * (size_t)v + 1] = acc[1]; grad_vertices[3 * (size_t)v + 2] = acc[2];
+}
+
+// k_face_light_backward_gather with the (shared) light read from device memory
+__global__ void __launch_bounds__(256) k_face_light_backward_gather_dev(IndexedFaces fs, DevLight dl,
+                                                                       const float* __restrict__ g_light,
+                                                                       const int32_t* __restrict__ adj_offsets,
+                                                                       const int32_t* __restrict__ adj_items,
+                                                                       float* __restrict__ grad_vertices) {
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    if (v >= fs.V) return;
+    const LightParams lp = light_at(dl, 0);
     float acc[3] = {0.0f, 0.0f, 0.0f};
     if (lp.id != 0) {
         for (int e = adj_offsets[v]; e < adj_offsets[v + 1]; e++) {

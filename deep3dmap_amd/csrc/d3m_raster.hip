@@ -20,6 +20,7 @@
 #include "d3m_g2s.h"
 #include "d3m_bid.h"
 #include "d3m_front.h"
+#include "d3m_light_grad.h"
 #include <climits>
 #include <cstdlib>
 #include <atomic>
@@ -807,6 +808,19 @@ static LightParams to_light(float ia, float id, const float* ca, const float* cd
     return lp;
 }
 
+// view b's light row b: every parameter of batch 1 or light_batch
+static int to_dev_light(const d3m_light* l, int light_batch, DevLight& dl) {
+    if (!l || light_batch <= 0) return D3M_ERR_INVALID;
+    if (!l->intensity_ambient || !l->intensity_directional || !l->color_ambient || !l->color_directional || !l->direction)
+        return D3M_ERR_INVALID;
+    const int nb[5] = {l->ia_batch, l->id_batch, l->ca_batch, l->cd_batch, l->dir_batch};
+    for (int k = 0; k < 5; k++)
+        if (nb[k] != 1 && nb[k] != light_batch) return D3M_ERR_INVALID;
+    dl = DevLight{l->intensity_ambient, l->intensity_directional, l->color_ambient, l->color_directional, l->direction,
+                  l->ia_batch, l->id_batch, l->ca_batch, l->cd_batch, l->dir_batch};
+    return D3M_OK;
+}
+
 D3M_EXPORT int d3m_lighting_forward(const float* faces, const float* textures_in, float* textures_out,
                                     float intensity_ambient, float intensity_directional, const float* color_ambient,
                                     const float* color_directional, const float* direction, long num_faces_total,
@@ -1017,6 +1031,38 @@ D3M_EXPORT int d3m_face_light_backward(const float* vertices, int vertices_batch
     return check_launch();
 }
 
+// ... the same two with the light read from device memory (d3m_light, row b of a parameter of batch light_batch)
+D3M_EXPORT int d3m_face_light_dev(const float* vertices, int vertices_batch, const int32_t* tri, int tri_batch, float* light,
+                                  const d3m_light* params, int light_batch, int num_vertices, int num_tri, int fill_back,
+                                  d3m_stream_t stream) {
+    if (!vertices || !light || light_batch <= 0 || num_vertices <= 0 || num_tri <= 0) return D3M_ERR_INVALID;
+    DevLight dl;
+    if (int rc = to_dev_light(params, light_batch, dl)) return rc;
+    int grid_w;
+    if (!tri_source_ok(tri, tri_batch, tri_batch, num_vertices, num_tri, grid_w)) return D3M_ERR_INVALID;
+    IndexedFaces fs{vertices, tri, num_vertices, num_tri, tri ? tri_batch : 1, fill_back ? 1 : 0, vertices_batch, grid_w};
+    const long n = (long)light_batch * fs.num_faces();
+    LAUNCH("k_face_light_dev", k_face_light_dev, dim3(blocks_for(n, 256)), dim3(256), (hipStream_t)stream, fs, dl, light,
+           light_batch);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_face_light_backward_dev(const float* vertices, int vertices_batch, const int32_t* tri, int tri_batch,
+                                           const float* grad_light, float* grad_vertices, const d3m_light* params,
+                                           int light_batch, int num_vertices, int num_tri, int fill_back, d3m_stream_t stream) {
+    if (!vertices || !grad_light || !grad_vertices || light_batch <= 0 || num_vertices <= 0 || num_tri <= 0)
+        return D3M_ERR_INVALID;
+    DevLight dl;
+    if (int rc = to_dev_light(params, light_batch, dl)) return rc;
+    int grid_w;
+    if (!tri_source_ok(tri, tri_batch, tri_batch, num_vertices, num_tri, grid_w)) return D3M_ERR_INVALID;
+    IndexedFaces fs{vertices, tri, num_vertices, num_tri, tri ? tri_batch : 1, fill_back ? 1 : 0, vertices_batch, grid_w};
+    const long n = (long)light_batch * fs.num_faces();
+    LAUNCH("k_face_light_backward_dev", k_face_light_backward_dev, dim3(blocks_for(n, 256)), dim3(256), (hipStream_t)stream, fs,
+           dl, grad_light, grad_vertices, vertices_batch, light_batch);
+    return check_launch();
+}
+
 // ---- deterministic mode: the vertex sums gathered in a fixed order instead of scattered with float atomics ---------------
 D3M_EXPORT int d3m_vertex_gather(const float* grad_faces_a, const float* grad_faces_b, const int32_t* adj_offsets,
                                  const int32_t* adj_items, float* grad_vertices, int batch_size, int num_vertices,
@@ -1047,16 +1093,28 @@ D3M_EXPORT int d3m_face_light_backward_gather(const float* vertices, const int32
     return check_launch();
 }
 
+D3M_EXPORT int d3m_face_light_backward_gather_dev(const float* vertices, const int32_t* tri, const int32_t* adj_offsets,
+                                                  const int32_t* adj_items, const float* grad_light, float* grad_vertices,
+                                                  const d3m_light* params, int num_vertices, int num_tri, int fill_back,
+                                                  d3m_stream_t stream) {
+    if (!vertices || !tri || !adj_offsets || !adj_items || !grad_light || !grad_vertices || num_vertices <= 0 || num_tri <= 0)
+        return D3M_ERR_INVALID;
+    DevLight dl;
+    if (int rc = to_dev_light(params, 1, dl)) return rc;        // one shared mesh: one light
+    IndexedFaces fs{vertices, tri, num_vertices, num_tri, 1, fill_back ? 1 : 0, 1, 0};
+    LAUNCH("k_face_light_backward_gather_dev", k_face_light_backward_gather_dev, dim3(blocks_for((long)num_vertices, 256)),
+           dim3(256), (hipStream_t)stream, fs, dl, grad_light, adj_offsets, adj_items, grad_vertices);
+    return check_launch();
+}
+
 // ---- the first launch of a lit render step: camera + per-face light + every clear (d3m_front.h) ------------------------
-D3M_EXPORT int d3m_lit_front(const float* vertices, int vertices_batch, const d3m_camera* cam, const d3m_basis* basis,
-                             float* screen_out, int batch_size, int num_vertices, const int32_t* tri, int tri_batch,
-                             int num_tri, int fill_back, float* light, int light_batch, float intensity_ambient,
-                             float intensity_directional, const float* color_ambient, const float* color_directional,
-                             const float* direction, void* const* zero_ptrs, const size_t* zero_bytes, int zero_count,
-                             d3m_stream_t stream) {
+// the arguments of k_lit_front / k_lit_front_dev (light by value: lp, else from device memory: dl)
+static int front_args(const float* vertices, int vertices_batch, const d3m_camera* cam, const d3m_basis* basis,
+                      float* screen_out, int batch_size, int num_vertices, const int32_t* tri, int tri_batch, int num_tri,
+                      int fill_back, float* light, int light_batch, const LightParams* lp, void* const* zero_ptrs,
+                      const size_t* zero_bytes, int zero_count, FrontArgs& a, unsigned& grid) {
     if (!vertices || batch_size <= 0 || num_vertices <= 0 || zero_count < 0 || zero_count > FRONT_RANGES) return D3M_ERR_INVALID;
     if (zero_count && (!zero_ptrs || !zero_bytes)) return D3M_ERR_INVALID;
-    FrontArgs a;
     memset(&a, 0, sizeof(a));
     a.vertices = vertices; a.vb = vertices_batch; a.B = batch_size; a.V = num_vertices;
     if (cam) {                                          // the camera part
@@ -1077,11 +1135,11 @@ D3M_EXPORT int d3m_lit_front(const float* vertices, int vertices_batch, const d3
         a.nb_cam = blocks_for((long)batch_size * num_vertices, 256);
     }
     if (light) {                                        // the light part
-        if (!color_ambient || !color_directional || !direction || light_batch <= 0 || num_tri <= 0) return D3M_ERR_INVALID;
+        if (light_batch <= 0 || num_tri <= 0) return D3M_ERR_INVALID;
         int grid_w;
         if (!tri_source_ok(tri, tri_batch, tri_batch, num_vertices, num_tri, grid_w)) return D3M_ERR_INVALID;
         a.faces = IndexedFaces{vertices, tri, num_vertices, num_tri, tri ? tri_batch : 1, fill_back ? 1 : 0, vertices_batch, grid_w};
-        a.lp = to_light(intensity_ambient, intensity_directional, color_ambient, color_directional, direction);
+        if (lp) a.lp = *lp;
         a.light = light; a.light_b = light_batch;
         a.nb_light = blocks_for((long)light_batch * a.faces.num_faces(), 256);
     }
@@ -1098,23 +1156,57 @@ D3M_EXPORT int d3m_lit_front(const float* vertices, int vertices_batch, const d3
     size_t nb_zero = used ? (most / 16 + 255) / 256 : 0;
     if (nb_zero > 2048) nb_zero = 2048;
     if (used && nb_zero == 0) nb_zero = 1;
-    const unsigned grid = a.nb_cam + a.nb_light + (unsigned)nb_zero;
+    grid = a.nb_cam + a.nb_light + (unsigned)nb_zero;
+    return D3M_OK;
+}
+
+D3M_EXPORT int d3m_lit_front(const float* vertices, int vertices_batch, const d3m_camera* cam, const d3m_basis* basis,
+                             float* screen_out, int batch_size, int num_vertices, const int32_t* tri, int tri_batch,
+                             int num_tri, int fill_back, float* light, int light_batch, float intensity_ambient,
+                             float intensity_directional, const float* color_ambient, const float* color_directional,
+                             const float* direction, void* const* zero_ptrs, const size_t* zero_bytes, int zero_count,
+                             d3m_stream_t stream) {
+    if (light && (!color_ambient || !color_directional || !direction)) return D3M_ERR_INVALID;
+    LightParams lp;
+    if (light) lp = to_light(intensity_ambient, intensity_directional, color_ambient, color_directional, direction);
+    FrontArgs a;
+    unsigned grid = 0;
+    if (int rc = front_args(vertices, vertices_batch, cam, basis, screen_out, batch_size, num_vertices, tri, tri_batch, num_tri,
+                            fill_back, light, light_batch, light ? &lp : nullptr, zero_ptrs, zero_bytes, zero_count, a, grid))
+        return rc;
     if (grid == 0) return D3M_OK;
     LAUNCH("k_lit_front", k_lit_front, dim3(grid), dim3(256), (hipStream_t)stream, a);
     return check_launch();
 }
 
+D3M_EXPORT int d3m_lit_front_dev(const float* vertices, int vertices_batch, const d3m_camera* cam, const d3m_basis* basis,
+                                 float* screen_out, int batch_size, int num_vertices, const int32_t* tri, int tri_batch,
+                                 int num_tri, int fill_back, float* light, int light_batch, const d3m_light* params,
+                                 void* const* zero_ptrs, const size_t* zero_bytes, int zero_count, d3m_stream_t stream) {
+    DevLight dl;
+    memset(&dl, 0, sizeof(dl));
+    if (light) {
+        if (int rc = to_dev_light(params, light_batch, dl)) return rc;
+        if (light_batch != 1 && light_batch != batch_size) return D3M_ERR_INVALID;
+    }
+    FrontArgs a;
+    unsigned grid = 0;
+    if (int rc = front_args(vertices, vertices_batch, cam, basis, screen_out, batch_size, num_vertices, tri, tri_batch, num_tri,
+                            fill_back, light, light_batch, nullptr, zero_ptrs, zero_bytes, zero_count, a, grid))
+        return rc;
+    if (grid == 0) return D3M_OK;
+    LAUNCH("k_lit_front_dev", k_lit_front_dev, dim3(grid), dim3(256), (hipStream_t)stream, a, dl);
+    return check_launch();
+}
+
 // ---- ... and its last launch: the camera's and the light's adjoints ADDED into grad_vertices (d3m_front.h k_lit_back) ------
-D3M_EXPORT int d3m_lit_back(const float* vertices, int vertices_batch, const d3m_camera* cam, const float* grad_screen,
-                            float* grad_vertices, int batch_size, int num_vertices, const int32_t* tri, int tri_batch,
-                            int num_tri, int fill_back, const float* grad_light, int light_batch, float intensity_ambient,
-                            float intensity_directional, const float* color_ambient, const float* color_directional,
-                            const float* direction, d3m_stream_t stream) {
-    if (!vertices || !cam || !grad_screen || !grad_vertices || !grad_light || !color_ambient || !color_directional ||
-        !direction || batch_size <= 0 || num_vertices <= 0 || num_tri <= 0 || light_batch <= 0)
+static int back_args(const float* vertices, int vertices_batch, const d3m_camera* cam, const float* grad_screen,
+                     float* grad_vertices, int batch_size, int num_vertices, const int32_t* tri, int tri_batch, int num_tri,
+                     int fill_back, const float* grad_light, int light_batch, BackArgs& a, unsigned& grid) {
+    if (!vertices || !cam || !grad_screen || !grad_vertices || !grad_light || batch_size <= 0 || num_vertices <= 0 ||
+        num_tri <= 0 || light_batch <= 0)
         return D3M_ERR_INVALID;
     if (vertices_batch != 1 && vertices_batch != batch_size) return D3M_ERR_INVALID;
-    BackArgs a;
     memset(&a, 0, sizeof(a));
     if (int rc = to_cam(cam, batch_size, a.cam)) return rc;
     int grid_w;
@@ -1122,12 +1214,82 @@ D3M_EXPORT int d3m_lit_back(const float* vertices, int vertices_batch, const d3m
     a.vertices = vertices; a.vb = vertices_batch; a.grad_screen = grad_screen; a.grad_vertices = grad_vertices;
     a.B = batch_size; a.V = num_vertices;
     a.faces = IndexedFaces{vertices, tri, num_vertices, num_tri, tri ? tri_batch : 1, fill_back ? 1 : 0, vertices_batch, grid_w};
-    a.lp = to_light(intensity_ambient, intensity_directional, color_ambient, color_directional, direction);
     a.grad_light = grad_light; a.light_b = light_batch;
     const long n_cam = vertices_batch > 1 ? (long)batch_size * num_vertices : 8l * num_vertices;     // lanes: see the kernel
     a.nb_cam = blocks_for(n_cam, 256);
     const unsigned nb_light = blocks_for((long)light_batch * a.faces.num_faces(), 256);
-    LAUNCH("k_lit_back", k_lit_back, dim3(a.nb_cam + nb_light), dim3(256), (hipStream_t)stream, a);
+    grid = a.nb_cam + nb_light;
+    return D3M_OK;
+}
+
+D3M_EXPORT int d3m_lit_back(const float* vertices, int vertices_batch, const d3m_camera* cam, const float* grad_screen,
+                            float* grad_vertices, int batch_size, int num_vertices, const int32_t* tri, int tri_batch,
+                            int num_tri, int fill_back, const float* grad_light, int light_batch, float intensity_ambient,
+                            float intensity_directional, const float* color_ambient, const float* color_directional,
+                            const float* direction, d3m_stream_t stream) {
+    if (!color_ambient || !color_directional || !direction) return D3M_ERR_INVALID;
+    BackArgs a;
+    unsigned grid = 0;
+    if (int rc = back_args(vertices, vertices_batch, cam, grad_screen, grad_vertices, batch_size, num_vertices, tri, tri_batch,
+                           num_tri, fill_back, grad_light, light_batch, a, grid))
+        return rc;
+    a.lp = to_light(intensity_ambient, intensity_directional, color_ambient, color_directional, direction);
+    LAUNCH("k_lit_back", k_lit_back, dim3(grid), dim3(256), (hipStream_t)stream, a);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_lit_back_dev(const float* vertices, int vertices_batch, const d3m_camera* cam, const float* grad_screen,
+                                float* grad_vertices, int batch_size, int num_vertices, const int32_t* tri, int tri_batch,
+                                int num_tri, int fill_back, const float* grad_light, int light_batch, const d3m_light* params,
+                                d3m_stream_t stream) {
+    DevLight dl;
+    if (int rc = to_dev_light(params, light_batch, dl)) return rc;
+    if (light_batch != 1 && light_batch != batch_size) return D3M_ERR_INVALID;
+    BackArgs a;
+    unsigned grid = 0;
+    if (int rc = back_args(vertices, vertices_batch, cam, grad_screen, grad_vertices, batch_size, num_vertices, tri, tri_batch,
+                           num_tri, fill_back, grad_light, light_batch, a, grid))
+        return rc;
+    LAUNCH("k_lit_back_dev", k_lit_back_dev, dim3(grid), dim3(256), (hipStream_t)stream, a, dl);
+    return check_launch();
+}
+
+// ---- the gradient of the light's parameters (d3m_light_grad.h) ------------------------------------------------------------
+D3M_EXPORT size_t d3m_light_params_backward_workspace_bytes(int light_batch, int num_tri, int fill_back) {
+    if (light_batch <= 0 || num_tri <= 0) return 0;
+    const int parts = light_parts(fill_back ? 2 * num_tri : num_tri);
+    return sizeof(float) * (size_t)light_batch * ((size_t)parts * LIGHT_SUMS + LIGHT_PARAMS);
+}
+
+D3M_EXPORT int d3m_light_params_backward(const float* vertices, int vertices_batch, const int32_t* tri, int tri_batch,
+                                         const float* grad_light, int light_batch, const d3m_light* light,
+                                         const d3m_light* grad, int num_vertices, int num_tri, int fill_back,
+                                         void* workspace, size_t workspace_bytes, d3m_stream_t stream) {
+    if (!vertices || !grad_light || !grad || num_vertices <= 0 || num_tri <= 0 || light_batch <= 0 || !workspace)
+        return D3M_ERR_INVALID;
+    if ((vertices_batch != 1 && vertices_batch != light_batch) || ((uintptr_t)workspace & 3)) return D3M_ERR_INVALID;
+    DevLight dl;
+    if (int rc = to_dev_light(light, light_batch, dl)) return rc;
+    int grid_w;
+    if (!tri_source_ok(tri, tri_batch, tri_batch, num_vertices, num_tri, grid_w)) return D3M_ERR_INVALID;
+    if (tri && tri_batch != 1 && tri_batch != light_batch) return D3M_ERR_INVALID;
+    // each output in the shape of its parameter (batch 1 or light_batch); NULL: not wanted
+    LightGradOut out{grad->intensity_ambient, grad->intensity_directional, grad->color_ambient, grad->color_directional,
+                     grad->direction, grad->ia_batch, grad->id_batch, grad->ca_batch, grad->cd_batch, grad->dir_batch};
+    const int nb[5] = {out.ia_b, out.id_b, out.ca_b, out.cd_b, out.dir_b};
+    const float* outs[5] = {out.ia, out.id, out.ca, out.cd, out.dir};
+    const int in_b[5] = {dl.ia_b, dl.id_b, dl.ca_b, dl.cd_b, dl.dir_b};
+    for (int k = 0; k < 5; k++)
+        if (outs[k] && nb[k] != in_b[k]) return D3M_ERR_INVALID;
+    if (workspace_bytes < d3m_light_params_backward_workspace_bytes(light_batch, num_tri, fill_back)) return D3M_ERR_INVALID;
+    IndexedFaces fs{vertices, tri, num_vertices, num_tri, tri ? tri_batch : 1, fill_back ? 1 : 0, vertices_batch, grid_w};
+    const int parts = light_parts(fs.num_faces());
+    float* partial = (float*)workspace;
+    float* rows = partial + (size_t)light_batch * parts * LIGHT_SUMS;
+    LAUNCH("k_light_params_partial", k_light_params_partial, dim3(parts, light_batch), dim3(256), (hipStream_t)stream, fs, dl,
+           grad_light, partial);
+    LAUNCH("k_light_params_finish", k_light_params_finish, dim3(1), dim3(256), (hipStream_t)stream, dl, partial, light_batch,
+           parts, rows, out);
     return check_launch();
 }
 

@@ -167,7 +167,7 @@ class MultiViewFit:
                                _lib.lib().d3m_forward_big_batch(int(n_largest), int(self.triangles.shape[0]),
                                                                 int(image_size * (2 if anti_aliasing else 1))) == 1))
         self.split_exchange = bool(split_exchange and objective_in_renderer and optimise_textures and view_groups == 1
-                                   and self.renderer._on_the_fly())
+                                   and self.renderer._on_the_fly() and self.renderer._constant_light())
         self._manual = self._tex_work = None
         self._grad_one = torch.ones(1, dtype=torch.float32, device=self.device)
         if self.split_exchange:

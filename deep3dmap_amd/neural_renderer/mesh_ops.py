@@ -118,25 +118,46 @@ def _light_rows(x, bs, device):
     return t.reshape(-1, 3).expand(bs, 3)
 
 
+def _intensity(x, device):
+    """an intensity as a number (kept on the host) or a [1|bs,1] tensor; a tensor's entries that are 0 contribute nothing
+    and get no gradient -- the term is skipped, as NR/lighting.py:36,40 skips it for a scalar"""
+    if not torch.is_tensor(x):
+        return float(x)
+    t = x.to(device=device, dtype=torch.float32).reshape(-1, 1)
+    return torch.where(t != 0, t, torch.zeros_like(t))
+
+
 def _lighting_per_batch(faces, textures, ia, idr, ca, cd, direction):
-    """The same light with one colour / direction per batch entry: a device-side tensor composition (a few small
-    launches; the fused kernel takes one light for the whole batch)."""
+    """The same light with one colour / direction / intensity per batch entry, or with parameters that require grad: a
+    device-side tensor composition (a few small launches; autograd differentiates every parameter)."""
     bs = faces.shape[0]
     ca, cd, direction = (_light_rows(x, bs, faces.device) for x in (ca, cd, direction))
+    ia, idr = _intensity(ia, faces.device), _intensity(idr, faces.device)
     normal = torch.linalg.cross(faces[:, :, 0] - faces[:, :, 1], faces[:, :, 2] - faces[:, :, 1], dim=2)
     normal = normal / normal.norm(dim=2, keepdim=True).clamp_min(1e-5)                      # F.normalize(eps=1e-5)
     cosine = (normal * direction[:, None, :]).sum(2).clamp_min(0)                            # relu(n . dir)
-    light = ia * ca[:, None, :] + idr * cd[:, None, :] * cosine[:, :, None]
+    if torch.is_tensor(ia) or torch.is_tensor(idr):
+        light = (ia * ca)[:, None, :] + (idr * cd)[:, None, :] * cosine[:, :, None]
+    else:
+        light = ia * ca[:, None, :] + idr * cd[:, None, :] * cosine[:, :, None]
     return textures * light[:, :, None, None, None, :]
+
+
+def _learnable_or_per_batch(*params):
+    """a light parameter that requires grad, or an intensity given per batch entry ([bs]): the torch composition"""
+    ia, idr = params[:2]
+    return any(torch.is_tensor(x) and x.requires_grad for x in params) or \
+        any((x.numel() if torch.is_tensor(x) else np.asarray(x).size) != 1 for x in (ia, idr))
 
 
 def lighting(faces, textures, intensity_ambient=0.5, intensity_directional=0.5, color_ambient=(1, 1, 1),
              color_directional=(1, 1, 1), direction=(0, 1, 0)):
     """Per-face ambient + directional light applied to the texture cubes (NR/lighting.py:5-57).
     faces [bs,nf,3,3] (world space), textures [bs,nf,ts,ts,ts,3]; returns the lit textures (the reference
-    multiplies in place and returns the same tensor).  Colours / direction: one 3-vector, or [bs,3]."""
-    if per_batch_light(color_ambient, color_directional, direction):
-        return _lighting_per_batch(faces, textures, intensity_ambient, intensity_directional, color_ambient,
-                                   color_directional, direction)
-    return _Lighting.apply(faces, textures, intensity_ambient, intensity_directional, color_ambient,
-                           color_directional, direction)
+    multiplies in place and returns the same tensor).  Colours / direction: one 3-vector, or [bs,3]; intensities: a
+    number, a 0-d tensor or (an extension of this library) one per batch entry [bs].  Parameters that require grad
+    receive their gradients."""
+    params = (intensity_ambient, intensity_directional, color_ambient, color_directional, direction)
+    if per_batch_light(color_ambient, color_directional, direction) or _learnable_or_per_batch(*params):
+        return _lighting_per_batch(faces, textures, *params)
+    return _Lighting.apply(faces, textures, *params)

@@ -239,6 +239,59 @@ def _vec3_host(x):
     return np.ctypeslib.as_ctypes(a)
 
 
+LIGHT_FIELDS = ("intensity_ambient", "intensity_directional", "color_ambient", "color_directional", "direction")
+
+
+def _light_param_batch(name, x):
+    """The batch of one light parameter, from its shape alone: colours / direction [3] (1) or [n,3] (n), intensities a
+    number, 0-d or [n] (n).  Anything else raises ValueError."""
+    import numpy as np
+    shape = tuple(x.shape) if torch.is_tensor(x) else np.shape(x)
+    if name.startswith("intensity"):
+        if len(shape) <= 1:
+            return shape[0] if shape else 1
+        raise ValueError(f"light {name} must be a number, a 0-d tensor or one value per view [B]; got shape {shape}")
+    if len(shape) == 1 and shape[0] == 3:
+        return 1
+    if len(shape) == 2 and shape[1] == 3:
+        return shape[0]
+    raise ValueError(f"light {name} must be [3] or one row per view [B,3]; got shape {shape}")
+
+
+def light_on_device(light_cfg):
+    """The lit node's route rule: its light is read from device memory (d3m_light) and is an autograd input of the node
+    when any parameter is a tensor that requires grad or is given per view; every other light is passed by value."""
+    return any((torch.is_tensor(x) and x.requires_grad) or _light_param_batch(name, x) > 1
+               for name, x in zip(LIGHT_FIELDS, light_cfg))
+
+
+def normalize_light(light_cfg, batch, device):
+    """(intensity_ambient, intensity_directional, color_ambient, color_directional, direction) -> five float32 device
+    tensors [n], [n], [n,3], [n,3], [n,3] with n = 1 or `batch` each; differentiable (reshapes of the caller's tensors).
+    Each may be a number, list, tuple, numpy array or tensor: colours and direction [3] or [B,3] (NR/lighting.py:25-30),
+    intensities a number, a 0-d tensor or -- an extension of this library; the reference takes one intensity for the
+    batch -- one per view, [B].  A batch other than 1 or `batch`, or a wrong last dimension, raises ValueError."""
+    out = []
+    for name, x in zip(LIGHT_FIELDS, light_cfg):
+        n = _light_param_batch(name, x)
+        if n not in (1, batch):
+            raise ValueError(f"light {name} has batch {n}; the render has {batch} views (1 or {batch} expected)")
+        t = x.to(device=device, dtype=torch.float32) if torch.is_tensor(x) else const_tensor(x, device)
+        out.append(t.reshape(n) if name.startswith("intensity") else t.reshape(n, 3))
+    return tuple(t.contiguous() for t in out)
+
+
+def _light_struct(tensors, like=None):
+    """d3m_light of five device tensors (gradient buffers: None = skipped) with the batches of `like` (default: themselves)"""
+    return _lib.D3MLight(*[_lib.ptr(t) for t in tensors], *[int(t.shape[0]) for t in (like or tensors)])
+
+
+def _host_zero(x):
+    """a light intensity known on the host to be 0 (a tensor is never looked at: that would synchronise)"""
+    import numpy as np
+    return not torch.is_tensor(x) and bool(np.all(np.asarray(x, dtype=np.float32) == 0))
+
+
 _side_streams = ops.StreamKeyedCache(max_per_kind=64)     # ((device index, which), forking stream handle) -> torch.cuda.Stream
 
 
@@ -467,7 +520,7 @@ class _LitState:
     ra: bool                                # alpha and depth returned (rgb always is)
     rd: bool
     fill_back: bool
-    light: tuple                            # (ia, idr, colour_ambient, colour_directional, direction)
+    light: tuple                            # (ia, idr, colour_ambient, colour_directional, direction) by value, or None
     Bl: int                                 # batch of the per-face light (1: one shared mesh)
     groups: list                            # the view groups' (lo, hi)
     need_grad: bool
@@ -487,6 +540,8 @@ class _LitState:
     finish_deferred: bool = False           # the objective's finish is left to backward's gathered pass (FIT_FINISH_DEFERRED)
     pre: Any = None                         # backward's buffers, allocated and zeroed by forward (_backward_buffers; one use)
     link: Optional[LitImagesLink] = None    # a fit objective evaluated on the finished images (set by LitImagesLink)
+    dlight: Any = None                      # the light read from device memory (normalize_light's five tensors) or None
+    need_lp: tuple = (False,) * 5           # which of them want a gradient (autograd inputs of the node)
 
 
 # _backward_buffers: the vertex accumulators, the texture / light gradients of batch B and where each view group's gathered
@@ -515,7 +570,7 @@ def _backward_buffers(st, vertices, textures, light, B, V, Ft, ts, ws_stream=Non
         else:
             grad_textures = torch.empty_like(textures)
             gt_g = [grad_textures[lo:hi] for lo, hi in groups]
-        if st.need_vert:
+        if st.need_vert or any(st.need_lp):
             if st.Bl == 1:
                 gl_g = [torch.empty_like(light) for _ in groups]
             else:
@@ -525,7 +580,7 @@ def _backward_buffers(st, vertices, textures, light, B, V, Ft, ts, ws_stream=Non
     if st.det:
         # per-VIEW light gradients (one contribution per entry), the two per-face arrays of K4 and K6
         Fp = 2 * Ft if st.fill_back else Ft
-        if st.need_vert:
+        if st.need_vert or any(st.need_lp):
             det_light = light.expand(B, Fp, 3).contiguous() if st.Bl == 1 else light
             det_gl = torch.empty(B, Fp, 3, dtype=torch.float32, device=dev)
         if st.need_geom:
@@ -571,7 +626,10 @@ class _RasterizeLit(torch.autograd.Function):
     @staticmethod
     def forward(ctx, screen_vertices, vertices, tri, textures, light_cfg, fill_back, image_size, anti_aliasing, near,
                 far, eps, background_color, return_rgb, return_alpha, return_depth, fit=None, view_groups=1,
-                defer_plan_join=False, camera=None, grad_sink=None, fit_hint=None):
+                defer_plan_join=False, camera=None, grad_sink=None, fit_hint=None, l_ia=None, l_idr=None, l_ca=None,
+                l_cd=None, l_dir=None):
+        # l_*: the light read from device memory (normalize_light; light_on_device) -- autograd inputs, so that backward
+        # can return their gradients; None: the light of light_cfg, passed to the kernels by value
         L = _lib.lib()
         vertices, textures = f32c(vertices), f32c(textures)
         tri = tri.to(torch.int32).contiguous()
@@ -601,16 +659,24 @@ class _RasterizeLit(torch.autograd.Function):
             raise ValueError("textures must be [1 or B, num_faces, ts, ts, ts, 3] for the given faces")
         S = int(image_size) * 2 if anti_aliasing else int(image_size)
         ia, idr, ca, cd, direction = light_cfg
-        cca, ccd, cdir = _vec3_host(ca), _vec3_host(cd), _vec3_host(direction)
-        Bl = 1 if (vertices.shape[0] == 1 and tri.shape[0] == 1) else B
+        dlight = None if l_ia is None else tuple(f32c(t) for t in (l_ia, l_idr, l_ca, l_cd, l_dir))
+        need_lp = tuple(bool(x) for x in (tuple(ctx.needs_input_grad) + (False,) * 5)[21:26]) if dlight is not None \
+            else (False,) * 5
+        if dlight is None:
+            cca, ccd, cdir = _vec3_host(ca), _vec3_host(cd), _vec3_host(direction)
+        elif any(t.shape[0] not in (1, B) for t in dlight):
+            raise ValueError("light parameters must have batch 1 or the number of views")
+        # (a light given per view makes the per-face light per view, even for one shared mesh)
+        light_per_view = dlight is not None and any(t.shape[0] > 1 for t in dlight)
+        Bl = 1 if (vertices.shape[0] == 1 and tri.shape[0] == 1 and not light_per_view) else B
         light = torch.empty(Bl, Fp, 3, dtype=torch.float32, device=dev)        # (filled by the first launch, below)
         background = _background_tensor(background_color, dev)
-        need_grad = any(ctx.needs_input_grad[:4])
+        need_grad = any(ctx.needs_input_grad[:4]) or any(need_lp)
         # the GEOMETRY side of backward (edge gradient K4, depth gradient K6, the light's and the camera's adjoints) only
         # exists for a mesh that wants a gradient: a texture-only optimisation builds no plan and walks no line
         need_geom = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
         need_tex = bool(ctx.needs_input_grad[3])
-        need_vert = bool(ctx.needs_input_grad[1]) and idr != 0
+        need_vert = bool(ctx.needs_input_grad[1]) and (not _host_zero(idr) if dlight is not None else idr != 0)
         groups = _group_bounds(B, view_groups)
         G = len(groups)
         # Everything the branches write is allocated here, on the current stream: no tensor changes its owning stream.
@@ -672,7 +738,8 @@ class _RasterizeLit(torch.autograd.Function):
         cur = torch.cuda.current_stream()
         det = need_grad and _deterministic()
         if det:
-            _RasterizeLit._deterministic_supported(G, tri, vertices, ts, idr, ctx.needs_input_grad[1])
+            _RasterizeLit._deterministic_supported(G, tri, vertices, ts, 0.0 if _host_zero(idr) else 1.0,
+                                                   ctx.needs_input_grad[1], light_per_view)
             if need_geom:
                 vertex_adjacency(tri, V)            # (built here, outside any capture of the backward pass)
         # (LitFitManual: every kernel on the caller's stream -- the step is cut BETWEEN kernels of one stream)
@@ -703,15 +770,15 @@ class _RasterizeLit(torch.autograd.Function):
                 records = _pixel_records(B, S, dev, grad_depth=True, extents=extents)
             fit_state = _FitState(rgb_t, depth_t, alpha_t, mask, scratch, loss_g, mask_sum, bool(anti_aliasing), records)
         st = _LitState(S=S, eps=float(eps), aa=bool(anti_aliasing), ra=bool(return_alpha), rd=bool(return_depth),
-                       fill_back=bool(fill_back), light=(float(ia), float(idr), ca, cd, direction), Bl=Bl, groups=groups,
-                       need_grad=need_grad, need_geom=need_geom, need_tex=need_tex, need_vert=need_vert,
-                       gathered=need_tex or need_vert, det=det, serial=serial,
+                       fill_back=bool(fill_back), light=(float(ia), float(idr), ca, cd, direction) if dlight is None else None,
+                       Bl=Bl, groups=groups, need_grad=need_grad, need_geom=need_geom, need_tex=need_tex,
+                       need_vert=need_vert, gathered=need_tex or need_vert or any(need_lp), det=det, serial=serial,
                        plan_open=bool(plan is not None and defer_plan_join and G == 1),   # (G > 1: capture crashes, as above)
                        camera=camera, cam_keep=cam_keep, grad_sink=grad_sink,
                        fit=None if hinted else fit_state, hint=fit_state if hinted else None,
                        # (whether the registered objective brought its normaliser or the node took sum(mask):
                        #  multiview_fit_loss only rides on the node's result when it is asked for the same one)
-                       hint_mask_sum_given=hinted and mask_sum_given)
+                       hint_mask_sum_given=hinted and mask_sum_given, dlight=dlight, need_lp=need_lp)
         # THE STEP'S FIRST LAUNCH (d3m_lit_front): the camera transform (with its look_at basis), the per-face light and
         # every clear the operators below would otherwise each launch for themselves -- the forward workspace's counters (or
         # z-buffer), the plan's, the objective's arrival tickets, the lines' extents -- and, for a caller that runs backward
@@ -747,11 +814,18 @@ class _RasterizeLit(torch.autograd.Function):
             flags_fit |= _lib.FIT_FINISH_DEFERRED
         st.pre, st.finish_deferred = pre, bool(flags_fit & _lib.FIT_FINISH_DEFERRED)
         zp, zb, nz = _front_clears(clears)
-        _lib.check(L.d3m_lit_front(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam) if cam is not None else None,
-                                   ctypes.byref(basis) if basis is not None else None,
-                                   _lib.ptr(sv) if cam is not None else None, B, V, _lib.ptr(tri), tri.shape[0], Ft,
-                                   int(bool(fill_back)), _lib.ptr(light), Bl, float(ia), float(idr), cca, ccd, cdir,
-                                   zp, zb, nz, _lib.stream_ptr()), "d3m_lit_front")
+        if dlight is None:
+            _lib.check(L.d3m_lit_front(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam) if cam is not None else None,
+                                       ctypes.byref(basis) if basis is not None else None,
+                                       _lib.ptr(sv) if cam is not None else None, B, V, _lib.ptr(tri), tri.shape[0], Ft,
+                                       int(bool(fill_back)), _lib.ptr(light), Bl, float(ia), float(idr), cca, ccd, cdir,
+                                       zp, zb, nz, _lib.stream_ptr()), "d3m_lit_front")
+        else:       # (the light's rows are read by the kernel: a captured step reads the light at replay)
+            _lib.check(L.d3m_lit_front_dev(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam) if cam is not None else None,
+                                           ctypes.byref(basis) if basis is not None else None,
+                                           _lib.ptr(sv) if cam is not None else None, B, V, _lib.ptr(tri), tri.shape[0], Ft,
+                                           int(bool(fill_back)), _lib.ptr(light), Bl, ctypes.byref(_light_struct(dlight)),
+                                           zp, zb, nz, _lib.stream_ptr()), "d3m_lit_front_dev")
         # The visibility list and the plan are only read by backward.  A caller that runs backward right behind forward,
         # on the same stream and (if captured) in the same capture, may leave that branch open at the end of forward
         # (defer_plan_join): backward waits for the plan where it first needs it and joins the branch, which runs on
@@ -831,15 +905,16 @@ class _RasterizeLit(torch.autograd.Function):
         return (rgb, alpha if return_alpha else empty, depth if return_depth else empty)
 
     @staticmethod
-    def _deterministic_supported(G, tri, vertices, ts, idr, vertices_need_grad):
+    def _deterministic_supported(G, tri, vertices, ts, idr, vertices_need_grad, light_per_view=False):
         """The deterministic backward pass covers one pipeline over ONE shared index tensor (and, for the light's adjoint,
-        one shared mesh) with gathered texture passes (texture_size 2, 3 or 4): anything else would silently fall back to
-        float atomics in arrival order, so it raises instead."""
-        if G != 1 or tri.shape[0] != 1 or ts not in (2, 3, 4) or (vertices_need_grad and idr != 0 and vertices.shape[0] != 1):
+        one shared mesh) with gathered texture passes (texture_size 2, 3 or 4) and one light for all views: anything else
+        would silently fall back to float atomics in arrival order, so it raises instead."""
+        if G != 1 or tri.shape[0] != 1 or ts not in (2, 3, 4) or (vertices_need_grad and idr != 0 and vertices.shape[0] != 1) \
+                or light_per_view:
             raise NotImplementedError(
                 "D3M_DETERMINISTIC / d3m_set_deterministic(1): the lit render node's reproducible backward pass needs "
-                "view_groups == 1, faces of batch 1 (one shared topology), texture_size 2..4 and, with directional light, "
-                "vertices of batch 1")
+                "view_groups == 1, faces of batch 1 (one shared topology), texture_size 2..4, one light for all views "
+                "and, with directional light, vertices of batch 1")
 
     @staticmethod
     def backward(ctx, g_rgb, g_alpha=None, g_depth=None):
@@ -864,7 +939,12 @@ class _RasterizeLit(torch.autograd.Function):
         _check_deterministic(st.det)
         faces, vertices, tri, textures, light = ctx.saved_tensors
         S, eps, ra, rd, fill_back, Bl, groups = st.S, st.eps, st.ra, st.rd, st.fill_back, st.Bl, st.groups
-        ia, idr, ca, cd, direction = st.light
+        dlight = st.dlight
+        if dlight is None:
+            ia, idr, ca, cd, direction = st.light
+            by_value = (ia, idr, _vec3_host(ca), _vec3_host(cd), _vec3_host(direction))
+        else:
+            dl_c = _light_struct(dlight)
         need_geom, need_tex, need_vert, gathered, det = st.need_geom, st.need_tex, st.need_vert, st.gathered, st.det
         dev, B, G = faces.device, faces.shape[0], len(groups)
         Ft, V, ts = tri.shape[1], vertices.shape[1], textures.shape[2]
@@ -1004,17 +1084,25 @@ class _RasterizeLit(torch.autograd.Function):
         def light_to_vertices(grad_light):
             # the light gradient -> world-space vertices through the face normals
             if det:     # the views' gradients summed in view order (torch's reduction), the adjoint gathered per vertex
-                total = det_gl.sum(0)           # (one shared mesh: _deterministic_supported)
+                total = det_gl.sum(0)           # (one shared mesh, one light: _deterministic_supported)
                 adj_off, adj_items = vertex_adjacency(tri, V)
-                _lib.check(L.d3m_face_light_backward_gather(
-                    _lib.ptr(vertices), _lib.ptr(tri), _lib.ptr(adj_off), _lib.ptr(adj_items), _lib.ptr(total),
-                    _lib.ptr(grad_vertices), ia, idr, _vec3_host(ca), _vec3_host(cd), _vec3_host(direction), V, Ft,
-                    int(fill_back), _lib.stream_ptr()), "d3m_face_light_backward_gather")
+                head = (_lib.ptr(vertices), _lib.ptr(tri), _lib.ptr(adj_off), _lib.ptr(adj_items), _lib.ptr(total),
+                        _lib.ptr(grad_vertices))
+                if dlight is None:
+                    _lib.check(L.d3m_face_light_backward_gather(*head, *by_value, V, Ft, int(fill_back), _lib.stream_ptr()),
+                               "d3m_face_light_backward_gather")
+                else:
+                    _lib.check(L.d3m_face_light_backward_gather_dev(*head, ctypes.byref(dl_c), V, Ft, int(fill_back),
+                                                                    _lib.stream_ptr()), "d3m_face_light_backward_gather_dev")
                 return
-            _lib.check(L.d3m_face_light_backward(
-                _lib.ptr(vertices), vertices.shape[0], _lib.ptr(tri), tri.shape[0], _lib.ptr(grad_light),
-                _lib.ptr(grad_vertices), ia, idr, _vec3_host(ca), _vec3_host(cd), _vec3_host(direction), Bl, V,
-                Ft, int(fill_back), _lib.stream_ptr()), "d3m_face_light_backward")
+            head = (_lib.ptr(vertices), vertices.shape[0], _lib.ptr(tri), tri.shape[0], _lib.ptr(grad_light),
+                    _lib.ptr(grad_vertices))
+            if dlight is None:
+                _lib.check(L.d3m_face_light_backward(*head, *by_value, Bl, V, Ft, int(fill_back), _lib.stream_ptr()),
+                           "d3m_face_light_backward")
+            else:
+                _lib.check(L.d3m_face_light_backward_dev(*head, ctypes.byref(dl_c), Bl, V, Ft, int(fill_back),
+                                                         _lib.stream_ptr()), "d3m_face_light_backward_dev")
 
         # One pipeline on one stream with the camera inside the node: the light's adjoint and the camera's are the step's last
         # two kernels -- ONE launch then (d3m_lit_back: both add into the zeroed grad_vertices with float atomics).  With
@@ -1058,13 +1146,33 @@ class _RasterizeLit(torch.autograd.Function):
                                    g_depth_map, grad_faces, S)
             _lib.check(L.d3m_scatter_face_grads(_lib.ptr(grad_faces), _lib.ptr(tri), tri.shape[0], _lib.ptr(grad_sv), B, V,
                                                 Ft, int(fill_back), _lib.stream_ptr()), "d3m_scatter_face_grads")
+        grad_lp = [None] * 5
+        if any(st.need_lp):
+            # the light's parameters: one fixed-order reduction of the per-face light's gradient (per view in the
+            # deterministic pass: summed over the views in view order by the same kernel)
+            if det:
+                gl_all, nbl = det_gl, B
+            elif light_shared:
+                gl_all = grad_light if grad_light is not None else (gl_g[0] if G == 1 else torch.stack(gl_g).sum(0))
+                nbl = 1
+            else:
+                gl_all, nbl = grad_light, Bl
+            grad_lp = [torch.empty_like(t) if need else None for t, need in zip(dlight, st.need_lp)]
+            ws = torch.empty(int(L.d3m_light_params_backward_workspace_bytes(nbl, Ft, int(fill_back))), dtype=torch.uint8,
+                             device=dev)
+            _lib.check(L.d3m_light_params_backward(
+                _lib.ptr(vertices), vertices.shape[0], _lib.ptr(tri), tri.shape[0], _lib.ptr(gl_all), nbl, ctypes.byref(dl_c),
+                ctypes.byref(_light_struct(grad_lp, dlight)), V, Ft, int(fill_back), _lib.ptr(ws), ws.numel(),
+                _lib.stream_ptr()), "d3m_light_params_backward")
         if fused_tail:
             from . import cameras
             cam, _keep = cameras._camera_struct(st.camera, dev)
-            _lib.check(L.d3m_lit_back(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam), _lib.ptr(grad_sv),
-                                      _lib.ptr(grad_vertices), B, V, _lib.ptr(tri), tri.shape[0], Ft, int(fill_back),
-                                      _lib.ptr(gl_g[0] if light_shared else grad_light), Bl, ia, idr, _vec3_host(ca),
-                                      _vec3_host(cd), _vec3_host(direction), _lib.stream_ptr()), "d3m_lit_back")
+            head = (_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam), _lib.ptr(grad_sv), _lib.ptr(grad_vertices), B, V,
+                    _lib.ptr(tri), tri.shape[0], Ft, int(fill_back), _lib.ptr(gl_g[0] if light_shared else grad_light), Bl)
+            if dlight is None:
+                _lib.check(L.d3m_lit_back(*head, *by_value, _lib.stream_ptr()), "d3m_lit_back")
+            else:
+                _lib.check(L.d3m_lit_back_dev(*head, ctypes.byref(dl_c), _lib.stream_ptr()), "d3m_lit_back_dev")
             grad_sv = None
         elif st.camera is not None and need_geom:
             # the camera's adjoint joins the light's in the same buffer (or writes it, when there is none)
@@ -1081,7 +1189,8 @@ class _RasterizeLit(torch.autograd.Function):
             grad_sv = None
         if tail_on_side:
             cur.wait_stream(auxs[0])
-        return (grad_sv if need_geom else None, grad_vertices if need_geom else None, None, grad_textures) + (None,) * 17
+        return (grad_sv if need_geom else None, grad_vertices if need_geom else None, None, grad_textures) + (None,) * 17 + \
+            tuple(grad_lp)
 
 
 # What _RasterizeMeshModes' forward decided and left for backward: configuration, the deterministic switch (checked in backward),
@@ -1301,11 +1410,13 @@ class LitFitManual:
     node: it is that node's code (tests/test_gpu_multirank.py)."""
 
     def __init__(self, vertices_grad=True, textures_grad=True):
-        self._needs = (False, bool(vertices_grad), False, bool(textures_grad)) + (False,) * 17
+        self._needs = (False, bool(vertices_grad), False, bool(textures_grad)) + (False,) * 22
         self._ctx = self._halves = None
 
     def forward(self, vertices, tri, textures, light_cfg, fill_back, targets, image_size, near, far, eps, background_color,
                 camera, grad_sink=None, images_out=None, anti_aliasing=False):
+        if light_on_device(light_cfg):
+            raise ValueError("LitFitManual takes one constant light for all views (no per-view light, no light that requires grad)")
         self._ctx = _ManualContext(self._needs)
         with torch.no_grad():
             return _RasterizeLit.forward(self._ctx, None, vertices, tri, textures, light_cfg, fill_back, image_size,
@@ -1328,6 +1439,16 @@ class LitFitManual:
         raise RuntimeError("_backward_halves yields once")
 
 
+def _device_light(light_cfg, screen_vertices, vertices, camera):
+    """The five light tensors the lit node takes as autograd inputs (normalize_light) when the light goes by device memory
+    (light_on_device), else five None: the light of light_cfg by value, today's route.  Shapes are checked here, in front of
+    any launch."""
+    if not light_on_device(light_cfg):
+        return (None,) * 5
+    batch = camera["batch"] if camera is not None else screen_vertices.shape[0]
+    return normalize_light(light_cfg, batch, vertices.device)
+
+
 def rasterize_lit(screen_vertices, vertices, tri, textures, light_cfg, fill_back, image_size=DEFAULT_IMAGE_SIZE,
                   anti_aliasing=DEFAULT_ANTI_ALIASING, near=DEFAULT_NEAR, far=DEFAULT_FAR, eps=DEFAULT_EPS,
                   background_color=DEFAULT_BACKGROUND_COLOR, return_alpha=True, return_depth=True, view_groups=1,
@@ -1338,10 +1459,13 @@ def rasterize_lit(screen_vertices, vertices, tri, textures, light_cfg, fill_back
     lighting() + rasterize_rgbad() on the materialised arrays.  `camera` (with screen_vertices None): the fused camera
     kernels' parameter block (cameras.look_at_params) -- the transform then runs inside the node.  `fit_hint` = the targets
     (rgb, depth, alpha, mask[, mask_sum]) of a multi-view fit objective the caller is about to evaluate on the returned
-    images: see _RasterizeLit.forward, "a REGISTERED objective"."""
+    images: see _RasterizeLit.forward, "a REGISTERED objective".  `light_cfg` = (intensity_ambient, intensity_directional,
+    color_ambient, color_directional, direction): see normalize_light; a light that requires grad or is given per view is
+    read from device memory and receives its gradient (light_on_device)."""
     rgb, alpha, depth = _RasterizeLit.apply(screen_vertices, vertices, tri, textures, light_cfg, fill_back, image_size,
                                             anti_aliasing, near, far, eps, background_color, True, return_alpha,
-                                            return_depth, None, view_groups, defer_plan_join, camera, None, fit_hint)
+                                            return_depth, None, view_groups, defer_plan_join, camera, None, fit_hint,
+                                            *_device_light(light_cfg, screen_vertices, vertices, camera))
     return {'rgb': rgb, 'alpha': alpha if return_alpha else None, 'depth': depth if return_depth else None}
 
 
@@ -1406,7 +1530,8 @@ def rasterize_lit_fit(screen_vertices, vertices, tri, textures, light_cfg, fill_
     # (images_out: (rgb, depth, alpha) buffers the same pass fills with the images render() returns)
     return _RasterizeLit.apply(screen_vertices, vertices, tri, textures, light_cfg, fill_back, image_size,
                                bool(anti_aliasing), near, far, eps, background_color, True, True, True,
-                               (targets, images_out), view_groups, defer_plan_join, camera, grad_sink)
+                               (targets, images_out), view_groups, defer_plan_join, camera, grad_sink, None,
+                               *_device_light(light_cfg, screen_vertices, vertices, camera))
 
 
 def rasterize_rgbad(

@@ -9,8 +9,8 @@ import torch
 import torch.nn as nn
 
 from . import cameras, mesh_ops
-from .rasterize import (rasterize, rasterize_depth, rasterize_lit, rasterize_lit_fit, rasterize_lit_image_grid,
-                        rasterize_mesh_modes, rasterize_rgbad, rasterize_silhouettes)
+from .rasterize import (light_on_device, rasterize, rasterize_depth, rasterize_lit, rasterize_lit_fit,
+                        rasterize_lit_image_grid, rasterize_mesh_modes, rasterize_rgbad, rasterize_silhouettes)
 
 
 class Renderer(nn.Module):
@@ -148,10 +148,14 @@ class Renderer(nn.Module):
                 self.light_color_directional, self.light_direction)
 
     def _on_the_fly(self):
-        # one light for the whole batch goes through the fused sampler; per-batch colours / directions
-        # (NR/lighting.py:25-30) through the materialised sequence
-        return self.lighting_on_the_fly and not mesh_ops.per_batch_light(
-            self.light_color_ambient, self.light_color_directional, self.light_direction)
+        # every light goes through the fused sampler -- per-view colours / directions (NR/lighting.py:25-30), per-view
+        # intensities and lights that require grad are read from device memory there (rasterize.light_on_device);
+        # lighting_on_the_fly = False: the materialised sequence cat -> lighting -> rasterize
+        return self.lighting_on_the_fly
+
+    def _constant_light(self):
+        """one light for the batch that needs no gradient: the light the forward-only and hand-driven paths take"""
+        return not light_on_device(self._light_cfg())
 
     def _camera_in_node(self, vertices, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         """Cameras with constant parameters run INSIDE the render node (its first launch projects, lights and clears; one
@@ -189,7 +193,7 @@ class Renderer(nn.Module):
         [B,3,h,w] with tx_size-2 cubes -- render_rgb(vertices, get_face_idx(b,h,w), get_textures_from_im(image, 2)) of
         deep3dmap's NrRenderer (renderer_nr.py:196-198) without the index and texture arrays (rasterize_lit_image_grid).
         Forward only; needs fill_back and one light for the batch."""
-        if not (self._on_the_fly() and self.fill_back):
+        if not (self._on_the_fly() and self.fill_back and self._constant_light()):
             raise ValueError("render_rgb_image_grid needs fill_back and lighting_on_the_fly (one light for the batch)")
         sv = self._transform(vertices, K, R, t, dist_coeffs, orig_size)
         return rasterize_lit_image_grid(sv, vertices, tuple(image.shape[2:]), image, self._light_cfg(), self.image_size,
@@ -205,7 +209,7 @@ class Renderer(nn.Module):
         objective and its two gradients into in place (per call, never remembered; ignored unless they fit this call's
         tensors exactly and the camera runs inside the node)."""
         if not self._on_the_fly():
-            raise ValueError("render_fit_loss needs lighting_on_the_fly (one light for the batch)")
+            raise ValueError("render_fit_loss needs lighting_on_the_fly")
         # look_at cameras with constant parameters run INSIDE the node (one gradient for the mesh instead of the camera's
         # plus the light's; results straight into the caller's grad_sink buffers when it has set them)
         cam = self._camera_in_node(vertices, K, R, t, dist_coeffs, orig_size)
@@ -219,8 +223,9 @@ class Renderer(nn.Module):
     def render_fit_loss_manual(self, manual, vertices, faces, textures, targets, images_out=None, grad_sink=None):
         """render_fit_loss driven without the autograd engine: `manual` is a rasterize.LitFitManual whose forward is run
         here (look_at cameras only: the camera runs inside the node); its two backward halves are the caller's to call."""
-        if not self._on_the_fly() or self.camera_mode != 'look_at':
-            raise ValueError("render_fit_loss_manual needs lighting_on_the_fly and camera_mode 'look_at'")
+        if not (self._on_the_fly() and self._constant_light()) or self.camera_mode != 'look_at':
+            raise ValueError("render_fit_loss_manual needs lighting_on_the_fly, one constant light for the batch and camera_mode "
+                             "'look_at'")
         cam = self._camera_in_node(vertices)
         if cam is None:
             raise ValueError("render_fit_loss_manual: the camera's parameters must be constants (no requires_grad)")

@@ -447,6 +447,53 @@ int d3m_face_light_backward(const float* vertices, int vertices_batch, const int
                             float intensity_directional, const float* color_ambient, const float* color_directional,
                             const float* direction, int light_batch, int num_vertices, int num_tri, int fill_back,
                             d3m_stream_t stream);
+/* --- lights read from DEVICE memory (learnable lights, one light per view) ----------------------------------------------
+ * d3m_light: the five light parameters as device arrays, each of batch 1 (every view) or light_batch (row b for light row
+ * b, i.e. view b):  intensity_ambient [n], intensity_directional [n], color_ambient [n,3], color_directional [n,3],
+ * direction [n,3].  The *_dev entry points read the rows when their kernels run (a captured graph reads the light at
+ * replay, nothing of it is baked into kernel arguments) and evaluate the by-value forms' expression on them: a light that
+ * is the same in every view gives the bits of d3m_face_light / d3m_lit_front.  light_batch is B whenever any parameter is
+ * given per view, even for a shared mesh.  d3m_light_params_backward WRITES a gradient laid out the same way. */
+typedef struct d3m_light {
+    float* intensity_ambient;     /* [ia_batch] */
+    float* intensity_directional; /* [id_batch] */
+    float* color_ambient;         /* [ca_batch,3] */
+    float* color_directional;     /* [cd_batch,3] */
+    float* direction;             /* [dir_batch,3] */
+    int ia_batch, id_batch, ca_batch, cd_batch, dir_batch; /* 1 or light_batch each */
+} d3m_light;
+/* d3m_face_light / d3m_face_light_backward with the light of d3m_light */
+int d3m_face_light_dev(const float* vertices, int vertices_batch, const int32_t* tri, int tri_batch, float* light,
+                       const d3m_light* params, int light_batch, int num_vertices, int num_tri, int fill_back,
+                       d3m_stream_t stream);
+int d3m_face_light_backward_dev(const float* vertices, int vertices_batch, const int32_t* tri, int tri_batch,
+                                const float* grad_light, float* grad_vertices, const d3m_light* params, int light_batch,
+                                int num_vertices, int num_tri, int fill_back, d3m_stream_t stream);
+/* d3m_face_light_backward_gather with the light of d3m_light (every parameter of batch 1: one shared mesh) */
+int d3m_face_light_backward_gather_dev(const float* vertices, const int32_t* tri, const int32_t* adj_offsets,
+                                       const int32_t* adj_items, const float* grad_light, float* grad_vertices,
+                                       const d3m_light* params, int num_vertices, int num_tri, int fill_back,
+                                       d3m_stream_t stream);
+/* d3m_lit_front / d3m_lit_back with the light of d3m_light (light_batch 1 or batch_size) */
+int d3m_lit_front_dev(const float* vertices, int vertices_batch, const d3m_camera* cam, const d3m_basis* basis,
+                      float* screen_out, int batch_size, int num_vertices, const int32_t* tri, int tri_batch, int num_tri,
+                      int fill_back, float* light, int light_batch, const d3m_light* params, void* const* zero_ptrs,
+                      const size_t* zero_bytes, int zero_count, d3m_stream_t stream);
+int d3m_lit_back_dev(const float* vertices, int vertices_batch, const d3m_camera* cam, const float* grad_screen,
+                     float* grad_vertices, int batch_size, int num_vertices, const int32_t* tri, int tri_batch, int num_tri,
+                     int fill_back, const float* grad_light, int light_batch, const d3m_light* params, d3m_stream_t stream);
+/* d3m_light_params_backward -- the gradient of the light's parameters from grad_light [light_batch,F',3] (the per-face
+ * light's gradient, d3m_backward_textures_lit) on WORLD vertices [vertices_batch,V,3] / tri [tri_batch,F,3], the normals
+ * recomputed as d3m_face_light does.  With r = relu(n . dir), G = grad_light, summed over the faces of a row:
+ *   d ia = sum G . ca,  d ca = ia sum G,  d id = sum r (G . cd),  d cd = id sum r G,  d dir = id sum [n . dir > 0] (G . cd) n;
+ * a term whose intensity is 0 gives zeros (NR/lighting.py:36,40).  `grad` fields are WRITTEN in the shape of the matching
+ * `light` parameter (the same batch; batch 1: the sum over the rows); a NULL field is skipped.  Fixed-order two-stage
+ * reduction (per-workgroup partials in `workspace`, then one ordered pass; no float atomics): bit-reproducible. */
+size_t d3m_light_params_backward_workspace_bytes(int light_batch, int num_tri, int fill_back);
+int d3m_light_params_backward(const float* vertices, int vertices_batch, const int32_t* tri, int tri_batch,
+                              const float* grad_light, int light_batch, const d3m_light* light, const d3m_light* grad,
+                              int num_vertices, int num_tri, int fill_back, void* workspace, size_t workspace_bytes,
+                              d3m_stream_t stream);
 /* forward_texture_sampling on the VIRTUAL lit array: faces [B,F',3,3] (F' = 2*num_tri if fill_back),
  * textures [Bx,num_tri,ts,ts,ts,3] (Bx = 1: shared), light [Bl,F',3]; writes rgb_map [B,S,S,3] for covered
  * pixels.  Colours are bit-identical to sampling the materialised array (same f32 products). */
