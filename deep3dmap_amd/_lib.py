@@ -23,6 +23,11 @@ class D3MBasis(ctypes.Structure):
                 ("is_look_at", _I)]
 
 
+class D3MCameraGrad(ctypes.Structure):
+    """d3m_camera_grad (include/d3m_raster.h): where d3m_camera_params_backward writes each parameter's gradient (NULL: skipped)."""
+    _fields_ = [("eye_or_t", _P), ("at_or_direction", _P), ("up", _P), ("rot", _P), ("K", _P), ("dist", _P)]
+
+
 class D3MVertexTarget(ctypes.Structure):
     _fields_ = [("grad_vertices", _P), ("tri", _P), ("num_vertices", _I), ("num_tri", _I), ("tri_batch", _I),
                 ("fill_back", _I)]
@@ -105,6 +110,9 @@ _SIGNATURES = {
     "d3m_camera_forward": (_I, [_P, _I, ctypes.POINTER(D3MCamera), _P, _I, _I, _P]),
     "d3m_camera_backward": (_I, [_P, _I, ctypes.POINTER(D3MCamera), _P, _P, _I, _I, _P]),
     "d3m_camera_backward_add": (_I, [_P, _I, ctypes.POINTER(D3MCamera), _P, _P, _I, _I, _P]),
+    "d3m_camera_params_backward_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "d3m_camera_params_backward": (_I, [_P, _I, ctypes.POINTER(D3MCamera), ctypes.POINTER(D3MBasis), _P,
+                                        ctypes.POINTER(D3MCameraGrad), _I, _I, _P, _SZ, _P]),
     "d3m_gather_faces": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "d3m_scatter_face_grads": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "d3m_lighting_forward": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _L, _I, _P]),

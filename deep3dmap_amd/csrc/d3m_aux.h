@@ -99,15 +99,13 @@ __device__ __forceinline__ void camera_point(const Cam& c, int b, const float* v
     }
 }
 
-// adjoint of camera_point at v: g (wrt output) -> gv (wrt input vertex)
-__device__ __forceinline__ void camera_point_adjoint(const Cam& c, int b, const float* v, const float* g, float* gv) {
-    if (c.mode == D3M_CAMERA_NONE) {
-        gv[0] = g[0]; gv[1] = g[1]; gv[2] = g[2];
-        return;
-    }
+// the camera-space part of camera_point's adjoint at v (look / look_at / projection): g (wrt output) -> gc (wrt the
+// camera-space point: (v - eye) in the basis, or R v + t).  `tmp` (projection only, may be NULL) receives the chain's
+// intermediate values.
+__device__ __forceinline__ void camera_point_grad_cam(const Cam& c, int b, const float* v, const float* g, float* gc,
+                                                      ProjTmp* tmp) {
     const float* r = cam_ptr(c.rot, c.rot_b, b, 9);
     const float* e = cam_ptr(c.eye_or_t, c.eye_b, b, 3);
-    float gc[3];
     if (c.mode == D3M_CAMERA_LOOK_AT || c.mode == D3M_CAMERA_LOOK) {
         if (c.perspective) {
             const float d0 = v[0] - e[0], d1 = v[1] - e[1], d2 = v[2] - e[2];
@@ -139,7 +137,19 @@ __device__ __forceinline__ void camera_point_adjoint(const Cam& c, int b, const 
         gc[0] = gx1 / t.zz;
         gc[1] = gy1 / t.zz;
         gc[2] = g[2] - (gx1 * x_ + gy1 * y_) / t.zz;
+        if (tmp) *tmp = t;
     }
+}
+
+// adjoint of camera_point at v: g (wrt output) -> gv (wrt input vertex)
+__device__ __forceinline__ void camera_point_adjoint(const Cam& c, int b, const float* v, const float* g, float* gv) {
+    if (c.mode == D3M_CAMERA_NONE) {
+        gv[0] = g[0]; gv[1] = g[1]; gv[2] = g[2];
+        return;
+    }
+    const float* r = cam_ptr(c.rot, c.rot_b, b, 9);
+    float gc[3];
+    camera_point_grad_cam(c, b, v, g, gc, nullptr);
     gv[0] = r[0] * gc[0] + r[3] * gc[1] + r[6] * gc[2];
     gv[1] = r[1] * gc[0] + r[4] * gc[1] + r[7] * gc[2];
     gv[2] = r[2] * gc[0] + r[5] * gc[1] + r[8] * gc[2];

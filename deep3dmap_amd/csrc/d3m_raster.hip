@@ -21,6 +21,7 @@
 #include "d3m_bid.h"
 #include "d3m_front.h"
 #include "d3m_light_grad.h"
+#include "d3m_camera_grad.h"
 #include <climits>
 #include <cstdlib>
 #include <atomic>
@@ -775,6 +776,52 @@ D3M_EXPORT int d3m_camera_backward_add(const float* vertices, int vertices_batch
                                        d3m_stream_t stream) {
     return run_camera_backward(vertices, vertices_batch, cam, grad_out, grad_vertices, batch_size, num_vertices, true,
                                (hipStream_t)stream);
+}
+
+// ---- the gradient of the camera's parameters (d3m_camera_grad.h) ----------------------------------------------------------
+D3M_EXPORT size_t d3m_camera_params_backward_workspace_bytes(int batch_size, int num_vertices, int mode) {
+    if (batch_size <= 0 || num_vertices <= 0) return 0;
+    if (mode != D3M_CAMERA_LOOK_AT && mode != D3M_CAMERA_LOOK && mode != D3M_CAMERA_PROJECTION) return 0;
+    return sizeof(float) * (size_t)batch_size * ((size_t)camera_parts(num_vertices) * CAM_SUMS + CAM_ROW);
+}
+
+D3M_EXPORT int d3m_camera_params_backward(const float* vertices, int vertices_batch, const d3m_camera* cam,
+                                          const d3m_basis* basis, const float* grad_screen, const d3m_camera_grad* grad,
+                                          int batch_size, int num_vertices, void* workspace, size_t workspace_bytes,
+                                          d3m_stream_t stream) {
+    if (!vertices || !grad_screen || !grad || !workspace || batch_size <= 0 || num_vertices <= 0) return D3M_ERR_INVALID;
+    if ((vertices_batch != 1 && vertices_batch != batch_size) || ((uintptr_t)workspace & 3)) return D3M_ERR_INVALID;
+    Cam c;
+    if (int rc = to_cam(cam, batch_size, c)) return rc;
+    const bool proj = c.mode == D3M_CAMERA_PROJECTION;
+    if (c.mode == D3M_CAMERA_NONE) return D3M_ERR_INVALID;
+    CamBasis bs{nullptr, nullptr, nullptr, 1, 1, 1, 0, 0};
+    if (basis) {
+        if (proj || !basis->eye || !basis->at_or_direction || !basis->up) return D3M_ERR_INVALID;
+        const int nb[3] = {basis->eye_batch, basis->at_batch, basis->up_batch};
+        for (int k = 0; k < 3; k++)
+            if (nb[k] != 1 && nb[k] != batch_size) return D3M_ERR_INVALID;
+        if (basis->eye_batch != c.eye_b || (basis->is_look_at != 0) != (c.mode == D3M_CAMERA_LOOK_AT)) return D3M_ERR_INVALID;
+        bs = CamBasis{basis->eye, basis->at_or_direction, basis->up, nb[0], nb[1], nb[2], basis->is_look_at ? 1 : 0, 1};
+    }
+    // each output in the shape of its parameter; NULL: not wanted.  at / up need the basis' vectors, K / dist a projection
+    if ((grad->at_or_direction || grad->up) && !bs.on) return D3M_ERR_INVALID;
+    if (!proj && (grad->K || grad->dist)) return D3M_ERR_INVALID;
+    if (workspace_bytes < d3m_camera_params_backward_workspace_bytes(batch_size, num_vertices, c.mode)) return D3M_ERR_INVALID;
+    CamGradOut out{grad->eye_or_t, grad->at_or_direction, grad->up, grad->rot, grad->K, grad->dist,
+                   c.eye_b, bs.at_b, bs.up_b, c.rot_b, c.K_b, c.dist_b};
+    const int parts = camera_parts(num_vertices);
+    float* partial = (float*)workspace;
+    float* rows = partial + (size_t)batch_size * parts * CAM_SUMS;
+    if (proj)
+        LAUNCH("k_camera_params_partial", k_camera_params_partial<true>, dim3(parts, batch_size), dim3(256),
+               (hipStream_t)stream, vertices, vertices_batch, c, grad_screen, num_vertices, partial);
+    else
+        LAUNCH("k_camera_params_partial", k_camera_params_partial<false>, dim3(parts, batch_size), dim3(256),
+               (hipStream_t)stream, vertices, vertices_batch, c, grad_screen, num_vertices, partial);
+    LAUNCH("k_camera_params_finish", k_camera_params_finish, dim3(1), dim3(256), (hipStream_t)stream, c, bs, partial,
+           batch_size, parts, rows, out);
+    return check_launch();
 }
 
 D3M_EXPORT int d3m_gather_faces(const float* vertices, const int32_t* tri, int tri_batch, float* faces_out,

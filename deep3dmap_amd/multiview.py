@@ -96,11 +96,16 @@ class MultiViewFit:
     targets, all-reduced once in set_targets_from() -- and the ranks' values and gradients then simply add up
     (R ranks x n/R cameras == 1 rank x n cameras, tests/test_gpu_multirank.py).  Per step ONE all-reduce(SUM) of the
     persistent flat buffer [loss | grad_vertices 3V | grad_textures 3 F ts^3].
+
+    optimise_cameras=True: this rank's eyes [n_local,3] require grad (pose refinement beside the mesh), and step() also
+    returns their gradient.  No other rank renders these views, so that gradient is exact on this rank and is not
+    exchanged; it is written inside the (captured) step into a persistent buffer, and in-place updates of `eyes` between
+    replays are read at replay.
     """
 
     def __init__(self, vertices, triangles, textures, eyes, image_size=512, anti_aliasing=False, rank=0,
                  world_size=1, optimise_textures=True, device="cuda", objective_in_renderer=True, view_groups=1,
-                 split_exchange=None, loss_form="linked"):
+                 split_exchange=None, loss_form="linked", optimise_cameras=False):
         self.device = torch.device(device)
         self.rank, self.world_size = rank, world_size
         lo, hi = shard_views(len(eyes), rank, world_size)
@@ -109,6 +114,15 @@ class MultiViewFit:
         self.triangles = torch.as_tensor(triangles, dtype=torch.int32).to(self.device)
         self.textures = torch.as_tensor(textures, dtype=torch.float32).to(self.device).requires_grad_(optimise_textures)
         self.eyes = torch.as_tensor(eyes, dtype=torch.float32)[lo:hi].to(self.device).contiguous()
+        self.optimise_cameras = bool(optimise_cameras)
+        self._grad_eyes = None
+        if self.optimise_cameras:
+            # (the split exchange's hand-driven halves take constant cameras only: Renderer.render_fit_loss_manual)
+            if split_exchange:
+                raise ValueError("MultiViewFit: optimise_cameras needs split_exchange=False (or None)")
+            split_exchange = False
+            self.eyes.requires_grad_(True)
+            self._grad_eyes = torch.zeros_like(self.eyes)       # the step's eye gradient (persistent: written in the step)
         self.renderer = nr.Renderer(image_size=image_size, anti_aliasing=anti_aliasing, camera_mode="look_at",
                                     fill_back=True)
         self.renderer.eye = self.eyes
@@ -234,6 +248,7 @@ class MultiViewFit:
     def _forward_backward(self):
         self.vertices.grad = None
         self.textures.grad = None
+        self.eyes.grad = None
         # backward runs right behind forward, on the same stream and inside the same capture: only HERE may the forward
         # leave its side branch (visibility list, edge plan, the loss's last reduction step) open for backward to join.
         # A bare fit_loss() (logging, evaluation) joins everything before it returns.
@@ -258,6 +273,8 @@ class MultiViewFit:
             if part.data_ptr() != dst.data_ptr():
                 dst.copy_(part)
             at += part.numel()
+        if self.optimise_cameras:
+            self._grad_eyes.copy_(self.eyes.grad)       # (this rank's views only: exact here, not exchanged)
         return self._flat
 
     # ---- the step in two parts (split_exchange) --------------------------------------------------------------------
@@ -295,6 +312,7 @@ class MultiViewFit:
         Vertices / textures / targets are updated IN PLACE between replays."""
         self.vertices.grad = None
         self.textures.grad = None
+        self.eyes.grad = None
         self._runner.capture(warmup)
         if self.split_exchange:
             # capture() ran the callback between the parts for real (warm-up, and once between the two captures): that
@@ -320,7 +338,8 @@ class MultiViewFit:
 
     def step(self):
         """forward + loss + backward + all-reduce.  Returns (loss, grad_vertices, grad_textures) of the WHOLE objective
-        (all ranks' cameras) as views of the persistent flat buffer, valid until the next step."""
+        (all ranks' cameras) as views of the persistent flat buffer, valid until the next step; with optimise_cameras also
+        grad_eyes [n_local,3], the objective's gradient with respect to this rank's eyes (a persistent buffer as well)."""
         nv = self.vertices.numel()
         if self.split_exchange:
             flat = self._runner()                   # ... during which the texture part's all-reduce was started
@@ -332,4 +351,6 @@ class MultiViewFit:
             flat = allreduce_sum_(self._runner())
         gv = flat[1:1 + nv].view_as(self.vertices)
         gt = flat[1 + nv:].view_as(self.textures) if self.textures.requires_grad else None
+        if self.optimise_cameras:
+            return flat[0], gv, gt, self._grad_eyes
         return flat[0], gv, gt

@@ -14,11 +14,12 @@ from ._util import as_device_f32, const_tensor, f32c
 
 
 class _CameraFunction(torch.autograd.Function):
-    """vertices [Bv,V,3] -> [B,V,3].  `params` is a dict of plain values / device tensors; gradients
-    flow to the vertices only (camera parameters are treated as constants)."""
+    """vertices [Bv,V,3] -> [B,V,3].  `params` is a parameter block (look_at_params & co); the block's parameter tensors
+    (camera_inputs) follow as autograd inputs, so that backward returns their gradients (d3m_camera_params_backward) beside
+    the vertices' (d3m_camera_backward)."""
 
     @staticmethod
-    def forward(ctx, vertices, params):
+    def forward(ctx, vertices, params, *inputs):
         v = f32c(vertices)
         B = params["batch"]
         cam, keep = _camera_struct(params, v.device)
@@ -36,11 +37,14 @@ class _CameraFunction(torch.autograd.Function):
         params = ctx.params
         g = f32c(grad_out)
         cam, keep = _camera_struct(params, v.device)
-        gv = torch.empty_like(v)
-        rc = _lib.lib().d3m_camera_backward(_lib.ptr(v), v.shape[0], ctypes.byref(cam), _lib.ptr(g), _lib.ptr(gv),
-                                            params["batch"], v.shape[1], _lib.stream_ptr())
-        _lib.check(rc, "d3m_camera_backward")
-        return gv, None
+        gv = None
+        if ctx.needs_input_grad[0]:
+            gv = torch.empty_like(v)
+            rc = _lib.lib().d3m_camera_backward(_lib.ptr(v), v.shape[0], ctypes.byref(cam), _lib.ptr(g), _lib.ptr(gv),
+                                                params["batch"], v.shape[1], _lib.stream_ptr())
+            _lib.check(rc, "d3m_camera_backward")
+        n = len(ctx.needs_input_grad) - 2          # (perspective() has no parameter tensors)
+        return (gv, None) + (params_backward(params, v, g, ctx.needs_input_grad[2:])[:n] if n else ())
 
 
 def _camera_struct(p, device):
@@ -59,37 +63,53 @@ def _camera_struct(p, device):
     return cam, keep
 
 
-def _learnable(*params):
-    """A camera parameter that requires grad (camera optimisation, e.g. neural_renderer's example4): the fused camera
-    kernels only differentiate with respect to the vertices, so these few [batch, 3]-sized quantities then go through
-    the device-side torch composition below and autograd."""
-    return any(torch.is_tensor(p) and p.requires_grad for p in params)
+# The parameter tensors of a block in the order of d3m_camera_grad's fields: the autograd inputs of _CameraFunction and of
+# the render nodes that run the camera inside (rasterize._RasterizeLit, _RasterizeMeshModes).
+CAMERA_INPUTS = ("eye_or_t", "at_or_direction", "up", "rot", "K", "dist")
 
 
-def _unit(v):
-    return v / v.norm(dim=-1, keepdim=True).clamp_min(1e-5)            # F.normalize(eps=1e-5), look_at.py:47-50
+def camera_inputs(p):
+    """the six parameter tensors of block `p` (CAMERA_INPUTS; None where the mode has none).  look / look_at: eye, at or
+    direction, up (the basis rows are computed from them); projection: t, R, K, dist."""
+    if p["mode"] == _lib.CAMERA_PROJECTION:
+        return (p["eye_or_t"], None, None, p["rot"], p["K"], p["dist"])
+    eye, at_or_dir, up, _ = p["vectors"]
+    return (eye, at_or_dir, up, None, None, None)
 
 
-def _frame_torch(eye, target, up, is_look_at):
-    """Rows (x, y, z) of the camera frame [b,3,3] from differentiable inputs (look_at.py:47-53, look.py:40-46)."""
-    z = _unit(target - eye) if is_look_at else _unit(target)
-    x = _unit(torch.linalg.cross(up.expand_as(z), z, dim=-1))
-    y = _unit(torch.linalg.cross(z, x, dim=-1))
-    return torch.stack((x, y, z), dim=1)
+def camera_learnable(p):
+    """whether any parameter of block `p` requires grad"""
+    return p is not None and any(t is not None and t.requires_grad for t in camera_inputs(p))
 
 
-def _view_torch(vertices, eye, frame, perspective_angle):
-    """(v - eye) expressed in the camera frame, then the optional perspective division (perspective.py:15-20)."""
-    out = torch.einsum('bvk,bjk->bvj', vertices - eye[:, None, :], frame)
-    if perspective_angle is not None:
-        width = _tan_width(perspective_angle)
-        zc = out[..., 2]
-        out = torch.stack((out[..., 0] / zc / width, out[..., 1] / zc / width, zc), dim=-1)
-    return out
+def params_backward(p, vertices, grad_screen, needs, stream=None):
+    """the gradients of block `p`'s parameters (camera_inputs order; None where `needs` is False) from grad_screen [B,V,3],
+    the gradient of the camera's output, on vertices [Bv,V,3] (one fixed-order reduction: d3m_camera_params_backward).  The
+    block's basis rows must hold the basis of its vectors (the forward pass left them there).  Allocated on the current
+    stream; launched on `stream` (default: the current one)."""
+    needs = tuple(bool(n) for n in tuple(needs)[:6]) + (False,) * max(0, 6 - len(needs))
+    if not any(needs):
+        return (None,) * 6
+    ins = camera_inputs(p)
+    grads = [torch.empty_like(t) if (t is not None and need) else None for t, need in zip(ins, needs)]
+    L = _lib.lib()
+    dev = vertices.device
+    cam, keep = _camera_struct(p, dev)
+    basis, bkeep = basis_struct(p, "vectors")
+    gs = _lib.D3MCameraGrad(*[_lib.ptr(g) for g in grads])
+    B, V = p["batch"], vertices.shape[1]
+    ws = torch.empty(int(L.d3m_camera_params_backward_workspace_bytes(B, V, p["mode"])), dtype=torch.uint8, device=dev)
+    with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+        _lib.check(L.d3m_camera_params_backward(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam),
+                                                ctypes.byref(basis) if basis is not None else None, _lib.ptr(grad_screen),
+                                                ctypes.byref(gs), B, V, _lib.ptr(ws), ws.numel(), _lib.stream_ptr()),
+                   "d3m_camera_params_backward")
+    return tuple(grads)
 
 
 def _projection_torch(vertices, K, R, t, dist, orig_size, eps):
-    """projection.py:19-43 as one differentiable device-side composition (all five inputs may require grad)."""
+    """projection.py:19-43 as one differentiable device-side composition: projection() with a non-default eps (the fused
+    kernels have the reference's 1e-9 built in)."""
     cam = torch.einsum('bvk,bjk->bvj', vertices, R) + t.reshape(-1, 1, 3)
     z = cam[..., 2]
     xn, yn = cam[..., 0] / (z + eps), cam[..., 1] / (z + eps)
@@ -118,36 +138,62 @@ def _basis(eye, at_or_dir, up, is_look_at, batch, device):
     return rot
 
 
-def _vec_param(x, device):
+def camera_param(name, x, inner, device):
+    """One camera parameter as a float32 device tensor [n, *inner] -- a differentiable reshape of the caller's tensor, so
+    that its gradient comes back in the caller's shape.  Accepted: [*inner] (n = 1), [n, *inner], and [n, 1, *inner] (t of
+    projection.py); anything else raises ValueError."""
     t = as_device_f32(x, device)
-    return t[None, :].contiguous() if t.dim() == 1 else t
+    k = len(inner)
+    shape = tuple(t.shape)
+    ok = shape[len(shape) - k:] == tuple(inner) and (len(shape) == k or len(shape) == k + 1
+                                                     or (len(shape) == k + 2 and shape[1] == 1))
+    if not ok:
+        raise ValueError(f"camera {name} must be {list(inner)} or one per view [B,{','.join(map(str, inner))}]; "
+                         f"got shape {list(shape)}")
+    return t.reshape(-1, *inner).contiguous()
+
+
+def _batch_of(vertices, named):
+    """the batch of a camera: the vertices' or the parameters' (1 or B each); another batch raises ValueError"""
+    B = max([vertices.shape[0]] + [t.shape[0] for t in named.values()])
+    for name, t in list(named.items()) + [("vertices", vertices)]:
+        if t.shape[0] not in (1, B):
+            raise ValueError(f"camera: {name} has batch {t.shape[0]}; the others make {B} views (1 or {B} expected)")
+    return B
+
+
+def _look_block(vertices, mode, eye, target, up, is_look_at, _perspective_angle, defer_basis):
+    device = vertices.device
+    eye_t = camera_param("eye", eye, (3,), device)
+    tgt_t = camera_param("at" if is_look_at else "direction", target, (3,), device)
+    up_t = camera_param("up", up, (3,), device)
+    batch = _batch_of(vertices, {"eye": eye_t, "at" if is_look_at else "direction": tgt_t, "up": up_t})
+    nb = max(eye_t.shape[0], tgt_t.shape[0], up_t.shape[0])
+    p = dict(mode=mode, batch=batch, eye_or_t=eye_t, perspective=_perspective_angle is not None,
+             width=_tan_width(_perspective_angle) if _perspective_angle is not None else 1.0,
+             vectors=(eye_t, tgt_t, up_t, is_look_at))
+    if defer_basis:
+        p["rot"] = torch.empty(nb, 3, 3, dtype=torch.float32, device=device)
+        p["basis"] = p["vectors"]
+    else:
+        with torch.no_grad():
+            p["rot"] = _basis(eye_t, tgt_t, up_t, is_look_at, nb, device)
+    return p
 
 
 def look_at_params(vertices, eye, at=[0, 0, 0], up=[0, 1, 0], _perspective_angle=None, defer_basis=False):
     """The fused camera kernels' parameter block of look_at(vertices, eye, at, up) -- for callers that run
-    d3m_camera_forward / _backward inside a larger node (rasterize._RasterizeLit) -- or None when a camera parameter
-    requires grad (those go through the torch composition in look_at).  defer_basis: the frame is NOT computed here
+    d3m_camera_forward / _backward inside a larger node (rasterize._RasterizeLit).  Parameters that require grad stay
+    differentiable (camera_inputs; their gradient: params_backward).  defer_basis: the frame is NOT computed here
     (d3m_camera_basis, a launch of its own) but by the caller's d3m_lit_front, which leaves it in `rot`: the block then
-    carries the vectors it is made of (`basis`)."""
-    if _learnable(eye, at, up):
-        return None
-    device = vertices.device
-    eye_t, at_t, up_t = _vec_param(eye, device), _vec_param(at, device), _vec_param(up, device)
-    nb = max(eye_t.shape[0], at_t.shape[0], up_t.shape[0])
-    p = dict(mode=_lib.CAMERA_LOOK_AT, batch=max(vertices.shape[0], nb), eye_or_t=eye_t,
-             perspective=_perspective_angle is not None,
-             width=_tan_width(_perspective_angle) if _perspective_angle is not None else 1.0)
-    if defer_basis:
-        p["rot"] = torch.empty(nb, 3, 3, dtype=torch.float32, device=device)
-        p["basis"] = (eye_t, at_t, up_t, True)
-    else:
-        p["rot"] = _basis(eye_t, at_t, up_t, True, nb, device)
-    return p
+    carries the vectors it is made of (`basis`).  Shapes [3] or [B,3]; another batch raises ValueError."""
+    return _look_block(vertices, _lib.CAMERA_LOOK_AT, eye, at, up, True, _perspective_angle, defer_basis)
 
 
-def basis_struct(p):
-    """(D3MBasis, tensors to keep alive) of a parameter block made with defer_basis, else (None, [])"""
-    b = p.get("basis")
+def basis_struct(p, key="basis"):
+    """(D3MBasis, tensors to keep alive) of a parameter block made with defer_basis (key "basis"), or of the vectors of any
+    look / look_at block (key "vectors"), else (None, [])"""
+    b = p.get(key)
     if b is None:
         return None, []
     eye, at, up, is_look_at = b
@@ -157,53 +203,25 @@ def basis_struct(p):
 
 def look_at(vertices, eye, at=[0, 0, 0], up=[0, 1, 0], _perspective_angle=None):
     """"Look at" transformation of vertices (NR/look_at.py:6-62).
-    `eye`, `at`, `up`: list / tuple / ndarray / tensor of shape [3] or [batch, 3]."""
+    `eye`, `at`, `up`: list / tuple / ndarray / tensor of shape [3] or [batch, 3]; tensors that require grad get it."""
     if vertices.ndimension() != 3:
         raise ValueError('vertices Tensor should have 3 dimensions')
     params = look_at_params(vertices, eye, at, up, _perspective_angle)
-    if params is None:
-        device = vertices.device
-        eye_t, at_t, up_t = _vec_param(eye, device), _vec_param(at, device), _vec_param(up, device)
-        B = max(vertices.shape[0], eye_t.shape[0], at_t.shape[0], up_t.shape[0])   # vertices of batch 1 = one mesh seen by every camera
-        return _view_torch(vertices.float().expand(B, -1, -1), eye_t.expand(B, 3),
-                           _frame_torch(eye_t.expand(B, 3), at_t.expand(B, 3), up_t.expand(B, 3), True),
-                           _perspective_angle)
-    return _CameraFunction.apply(vertices, params)
+    return _CameraFunction.apply(vertices, params, *camera_inputs(params))
 
 
 def look(vertices, eye, direction=[0, 1, 0], up=None, _perspective_angle=None):
     """"Look" transformation of vertices (NR/look.py:6-53); `up` defaults to [0, 1, 0]."""
     if vertices.ndimension() != 3:
         raise ValueError('vertices Tensor should have 3 dimensions')
-    device = vertices.device
-    eye_t, dir_t = _vec_param(eye, device), _vec_param(direction, device)
-    up_t = _vec_param([0, 1, 0] if up is None else up, device)
-    nb = max(eye_t.shape[0], dir_t.shape[0], up_t.shape[0])
-    B = max(vertices.shape[0], nb)
-    if _learnable(eye, direction, up):
-        return _view_torch(vertices.float().expand(B, -1, -1), eye_t.expand(B, 3),
-                           _frame_torch(eye_t.expand(B, 3), dir_t.expand(B, 3), up_t.expand(B, 3), False),
-                           _perspective_angle)
-    return _CameraFunction.apply(vertices, look_params(vertices, eye, direction, up, _perspective_angle))
+    params = look_params(vertices, eye, direction, up, _perspective_angle)
+    return _CameraFunction.apply(vertices, params, *camera_inputs(params))
 
 
 def look_params(vertices, eye, direction=[0, 1, 0], up=None, _perspective_angle=None, defer_basis=False):
-    """look()'s parameter block (see look_at_params), or None when a camera parameter requires grad."""
-    if _learnable(eye, direction, up):
-        return None
-    device = vertices.device
-    eye_t, dir_t = _vec_param(eye, device), _vec_param(direction, device)
-    up_t = _vec_param([0, 1, 0] if up is None else up, device)
-    nb = max(eye_t.shape[0], dir_t.shape[0], up_t.shape[0])
-    p = dict(mode=_lib.CAMERA_LOOK, batch=max(vertices.shape[0], nb), eye_or_t=eye_t,
-             perspective=_perspective_angle is not None,
-             width=_tan_width(_perspective_angle) if _perspective_angle is not None else 1.0)
-    if defer_basis:
-        p["rot"] = torch.empty(nb, 3, 3, dtype=torch.float32, device=device)
-        p["basis"] = (eye_t, dir_t, up_t, False)
-    else:
-        p["rot"] = _basis(eye_t, dir_t, up_t, False, nb, device)
-    return p
+    """look()'s parameter block (see look_at_params)."""
+    return _look_block(vertices, _lib.CAMERA_LOOK, eye, direction, [0, 1, 0] if up is None else up, False,
+                       _perspective_angle, defer_basis)
 
 
 def perspective(vertices, angle=30.):
@@ -220,26 +238,23 @@ def perspective(vertices, angle=30.):
 def projection(vertices, K, R, t, dist_coeffs, orig_size, eps=1e-9):
     """Projective transformation with lens distortion (NR/projection.py:6-43).
     K [b,3,3], R [b,3,3], t [b,1,3] (or [b,3]), dist_coeffs [b,5]; b is 1 or the batch size."""
-    device = vertices.device
-    tt = as_device_f32(t, device).reshape(-1, 3)
-    rot, Kt, dist = (as_device_f32(R, device).reshape(-1, 3, 3), as_device_f32(K, device).reshape(-1, 3, 3),
-                     as_device_f32(dist_coeffs, device).reshape(-1, 5))
-    batch = max(vertices.shape[0], tt.shape[0], rot.shape[0], Kt.shape[0], dist.shape[0])
-    if _learnable(K, R, t, dist_coeffs) or eps != 1e-9:      # the fused kernel has the reference's default eps built in
-        return _projection_torch(vertices.float().expand(batch, -1, -1), Kt.expand(batch, 3, 3), rot.expand(batch, 3, 3),
-                                 tt.expand(batch, 3), dist.expand(batch, 5), float(orig_size), eps)
-    return _CameraFunction.apply(vertices, projection_params(vertices, K, R, t, dist_coeffs, orig_size))
+    params = projection_params(vertices, K, R, t, dist_coeffs, orig_size)
+    if eps != 1e-9:      # the fused kernels have the reference's default eps built in
+        batch = params["batch"]
+        return _projection_torch(vertices.float().expand(batch, -1, -1), params["K"].expand(batch, 3, 3),
+                                 params["rot"].expand(batch, 3, 3), params["eye_or_t"].expand(batch, 3),
+                                 params["dist"].expand(batch, 5), float(orig_size), eps)
+    return _CameraFunction.apply(vertices, params, *camera_inputs(params))
 
 
 def projection_params(vertices, K, R, t, dist_coeffs, orig_size):
-    """projection()'s parameter block (default eps), or None when a camera parameter requires grad."""
-    if _learnable(K, R, t, dist_coeffs):
-        return None
+    """projection()'s parameter block (default eps).  Parameters that require grad stay differentiable (camera_inputs);
+    K / R [3,3] or [B,3,3], t [3], [B,3] or [B,1,3], dist_coeffs [5] or [B,5]; another batch raises ValueError."""
     device = vertices.device
-    tt = as_device_f32(t, device).reshape(-1, 3).contiguous()
-    rot, Kt, dist = (as_device_f32(R, device).reshape(-1, 3, 3).contiguous(), as_device_f32(K, device).reshape(-1, 3, 3).contiguous(),
-                     as_device_f32(dist_coeffs, device).reshape(-1, 5).contiguous())
-    batch = max(vertices.shape[0], tt.shape[0], rot.shape[0], Kt.shape[0], dist.shape[0])
+    tt = camera_param("t", t, (3,), device)
+    rot, Kt, dist = (camera_param("R", R, (3, 3), device), camera_param("K", K, (3, 3), device),
+                     camera_param("dist_coeffs", dist_coeffs, (5,), device))
+    batch = _batch_of(vertices, {"t": tt, "R": rot, "K": Kt, "dist_coeffs": dist})
     return dict(mode=_lib.CAMERA_PROJECTION, batch=batch, rot=rot, eye_or_t=tt, K=Kt, dist=dist, orig_size=float(orig_size))
 
 

@@ -542,6 +542,8 @@ class _LitState:
     link: Optional[LitImagesLink] = None    # a fit objective evaluated on the finished images (set by LitImagesLink)
     dlight: Any = None                      # the light read from device memory (normalize_light's five tensors) or None
     need_lp: tuple = (False,) * 5           # which of them want a gradient (autograd inputs of the node)
+    need_mesh: bool = False                 # the mesh (vertices or screen vertices) wants a gradient
+    need_cp: tuple = (False,) * 6           # which of the camera's parameters want one (cameras.camera_inputs order)
 
 
 # _backward_buffers: the vertex accumulators, the texture / light gradients of batch B and where each view group's gathered
@@ -627,9 +629,11 @@ class _RasterizeLit(torch.autograd.Function):
     def forward(ctx, screen_vertices, vertices, tri, textures, light_cfg, fill_back, image_size, anti_aliasing, near,
                 far, eps, background_color, return_rgb, return_alpha, return_depth, fit=None, view_groups=1,
                 defer_plan_join=False, camera=None, grad_sink=None, fit_hint=None, l_ia=None, l_idr=None, l_ca=None,
-                l_cd=None, l_dir=None):
+                l_cd=None, l_dir=None, c_eye_or_t=None, c_at_or_direction=None, c_up=None, c_rot=None, c_K=None,
+                c_dist=None):
         # l_*: the light read from device memory (normalize_light; light_on_device) -- autograd inputs, so that backward
-        # can return their gradients; None: the light of light_cfg, passed to the kernels by value
+        # can return their gradients; None: the light of light_cfg, passed to the kernels by value.  c_*: the parameter
+        # tensors of `camera` (cameras.camera_inputs), autograd inputs likewise: the block's own tensors, read by the kernels
         L = _lib.lib()
         vertices, textures = f32c(vertices), f32c(textures)
         tri = tri.to(torch.int32).contiguous()
@@ -671,10 +675,14 @@ class _RasterizeLit(torch.autograd.Function):
         Bl = 1 if (vertices.shape[0] == 1 and tri.shape[0] == 1 and not light_per_view) else B
         light = torch.empty(Bl, Fp, 3, dtype=torch.float32, device=dev)        # (filled by the first launch, below)
         background = _background_tensor(background_color, dev)
-        need_grad = any(ctx.needs_input_grad[:4]) or any(need_lp)
+        # which of the camera's parameters want a gradient (the camera inside the node only)
+        need_cp = tuple(bool(x) for x in (tuple(ctx.needs_input_grad) + (False,) * 6)[26:32]) if camera is not None \
+            else (False,) * 6
+        need_grad = any(ctx.needs_input_grad[:4]) or any(need_lp) or any(need_cp)
         # the GEOMETRY side of backward (edge gradient K4, depth gradient K6, the light's and the camera's adjoints) only
-        # exists for a mesh that wants a gradient: a texture-only optimisation builds no plan and walks no line
-        need_geom = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        # exists for a mesh or a camera that wants a gradient: a texture-only optimisation builds no plan and walks no line
+        need_mesh = bool(ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
+        need_geom = need_mesh or any(need_cp)
         need_tex = bool(ctx.needs_input_grad[3])
         need_vert = bool(ctx.needs_input_grad[1]) and (not _host_zero(idr) if dlight is not None else idr != 0)
         groups = _group_bounds(B, view_groups)
@@ -772,13 +780,15 @@ class _RasterizeLit(torch.autograd.Function):
         st = _LitState(S=S, eps=float(eps), aa=bool(anti_aliasing), ra=bool(return_alpha), rd=bool(return_depth),
                        fill_back=bool(fill_back), light=(float(ia), float(idr), ca, cd, direction) if dlight is None else None,
                        Bl=Bl, groups=groups, need_grad=need_grad, need_geom=need_geom, need_tex=need_tex,
-                       need_vert=need_vert, gathered=need_tex or need_vert or any(need_lp), det=det, serial=serial,
+                       need_vert=need_vert, gathered=need_tex or need_vert or any(need_lp) or any(need_cp), det=det,
+                       serial=serial,
                        plan_open=bool(plan is not None and defer_plan_join and G == 1),   # (G > 1: capture crashes, as above)
                        camera=camera, cam_keep=cam_keep, grad_sink=grad_sink,
                        fit=None if hinted else fit_state, hint=fit_state if hinted else None,
                        # (whether the registered objective brought its normaliser or the node took sum(mask):
                        #  multiview_fit_loss only rides on the node's result when it is asked for the same one)
-                       hint_mask_sum_given=hinted and mask_sum_given, dlight=dlight, need_lp=need_lp)
+                       hint_mask_sum_given=hinted and mask_sum_given, dlight=dlight, need_lp=need_lp,
+                       need_mesh=need_mesh, need_cp=need_cp)
         # THE STEP'S FIRST LAUNCH (d3m_lit_front): the camera transform (with its look_at basis), the per-face light and
         # every clear the operators below would otherwise each launch for themselves -- the forward workspace's counters (or
         # z-buffer), the plan's, the objective's arrival tickets, the lines' extents -- and, for a caller that runs backward
@@ -1164,6 +1174,9 @@ class _RasterizeLit(torch.autograd.Function):
                 _lib.ptr(vertices), vertices.shape[0], _lib.ptr(tri), tri.shape[0], _lib.ptr(gl_all), nbl, ctypes.byref(dl_c),
                 ctypes.byref(_light_struct(grad_lp, dlight)), V, Ft, int(fill_back), _lib.ptr(ws), ws.numel(),
                 _lib.stream_ptr()), "d3m_light_params_backward")
+        # the camera's parameters (a learnable camera inside the node): one fixed-order reduction of the final grad_sv,
+        # beside the camera's adjoint on the same stream
+        grad_cp = (None,) * 6
         if fused_tail:
             from . import cameras
             cam, _keep = cameras._camera_struct(st.camera, dev)
@@ -1173,30 +1186,35 @@ class _RasterizeLit(torch.autograd.Function):
                 _lib.check(L.d3m_lit_back(*head, *by_value, _lib.stream_ptr()), "d3m_lit_back")
             else:
                 _lib.check(L.d3m_lit_back_dev(*head, ctypes.byref(dl_c), _lib.stream_ptr()), "d3m_lit_back_dev")
+            grad_cp = cameras.params_backward(st.camera, vertices, grad_sv, st.need_cp)
             grad_sv = None
         elif st.camera is not None and need_geom:
             # the camera's adjoint joins the light's in the same buffer (or writes it, when there is none)
             from . import cameras
             cam, _keep = cameras._camera_struct(st.camera, dev)
-            if grad_vertices is None:
-                grad_vertices = sink[0] if sink is not None else torch.empty_like(vertices)
-                fn, what = L.d3m_camera_backward, "d3m_camera_backward"
-            else:
-                fn, what = L.d3m_camera_backward_add, "d3m_camera_backward_add"
-            with torch.cuda.stream(auxs[0] if tail_on_side else cur):
-                _lib.check(fn(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam), _lib.ptr(grad_sv),
-                              _lib.ptr(grad_vertices), B, V, _lib.stream_ptr()), what)
+            tail = auxs[0] if tail_on_side else cur
+            if st.need_mesh:
+                if grad_vertices is None:
+                    grad_vertices = sink[0] if sink is not None else torch.empty_like(vertices)
+                    fn, what = L.d3m_camera_backward, "d3m_camera_backward"
+                else:
+                    fn, what = L.d3m_camera_backward_add, "d3m_camera_backward_add"
+                with torch.cuda.stream(tail):
+                    _lib.check(fn(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam), _lib.ptr(grad_sv),
+                                  _lib.ptr(grad_vertices), B, V, _lib.stream_ptr()), what)
+            grad_cp = cameras.params_backward(st.camera, vertices, grad_sv, st.need_cp, stream=tail)
             grad_sv = None
         if tail_on_side:
             cur.wait_stream(auxs[0])
         return (grad_sv if need_geom else None, grad_vertices if need_geom else None, None, grad_textures) + (None,) * 17 + \
-            tuple(grad_lp)
+            tuple(grad_lp) + tuple(grad_cp)
 
 
 # What _RasterizeMeshModes' forward decided and left for backward: configuration, the deterministic switch (checked in backward),
 # the camera (+ what its structs point into), the pass's maps and backward's accumulator, zeroed by forward (pre; one use)
 _MeshModesState = dataclasses.make_dataclass("_MeshModesState", (
-    "aa eps fill_back ra rd det camera keep faces face_index_map weight_map depth_map alpha_map visibility plan pre").split(),
+    "aa eps fill_back ra rd det camera keep faces face_index_map weight_map depth_map alpha_map visibility plan pre need_mesh "
+    "need_cp").split(),
     eq=False)
 
 
@@ -1213,7 +1231,9 @@ class _RasterizeMeshModes(torch.autograd.Function):
     (tests/test_gpu_renderer.py; docs/EXPERIMENTS.md C)."""
 
     @staticmethod
-    def forward(ctx, vertices, tri, camera, fill_back, image_size, anti_aliasing, near, far, eps, return_alpha, return_depth):
+    def forward(ctx, vertices, tri, camera, fill_back, image_size, anti_aliasing, near, far, eps, return_alpha, return_depth,
+                c_eye_or_t=None, c_at_or_direction=None, c_up=None, c_rot=None, c_K=None, c_dist=None):
+        # c_*: the parameter tensors of `camera` (cameras.camera_inputs) as autograd inputs: backward returns their gradients
         from . import cameras
         L = _lib.lib()
         vertices = f32c(vertices)
@@ -1227,7 +1247,8 @@ class _RasterizeMeshModes(torch.autograd.Function):
             raise ValueError("vertices must be [1 or B, V, 3] and faces [1 or B, F, 3]")
         S = int(image_size) * 2 if anti_aliasing else int(image_size)
         s_out = int(image_size)
-        need_grad = ctx.needs_input_grad[0]
+        need_cp = tuple(bool(x) for x in (tuple(ctx.needs_input_grad) + (False,) * 6)[11:17])
+        need_grad = ctx.needs_input_grad[0] or any(need_cp)
         sv = torch.empty(B, V, 3, dtype=torch.float32, device=dev)
         faces = torch.empty(B, Fp, 3, 3, dtype=torch.float32, device=dev)      # (the dense copy of faces that can own a pixel)
         fi = torch.empty(B, S, S, dtype=torch.int32, device=dev)
@@ -1285,7 +1306,8 @@ class _RasterizeMeshModes(torch.autograd.Function):
             vertex_adjacency(tri, V)            # (the deterministic backward pass's CSR adjacency: built outside any capture of it)
         ctx.state = _MeshModesState(aa=bool(anti_aliasing), eps=float(eps), fill_back=bool(fill_back), ra=bool(return_alpha), rd=bool(return_depth), det=det,
                                     camera=camera, keep=(cam_keep, basis_keep), faces=faces, face_index_map=fi,
-                                    weight_map=wm, depth_map=dm, alpha_map=alpha_map, visibility=vis, plan=plan, pre=pre)
+                                    weight_map=wm, depth_map=dm, alpha_map=alpha_map, visibility=vis, plan=plan, pre=pre,
+                                    need_mesh=bool(ctx.needs_input_grad[0]), need_cp=need_cp)
         ctx.save_for_backward(vertices, tri)
         empty = torch.tensor([])
         return (alpha if return_alpha else empty, depth if return_depth else empty)
@@ -1367,11 +1389,14 @@ class _RasterizeMeshModes(torch.autograd.Function):
                                                      _lib.ptr(g_depth_map), B, Fp, S, ctypes.byref(target), _lib.ptr(vis),
                                                      _lib.ptr(counter), k6_flags, _lib.stream_ptr()),
                        "d3m_backward_depth_map_mesh")
-        cam, _keep = cameras._camera_struct(st.camera, dev)
-        grad_vertices = torch.empty_like(vertices)
-        _lib.check(L.d3m_camera_backward(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam), _lib.ptr(grad_sv),
-                                         _lib.ptr(grad_vertices), B, V, _lib.stream_ptr()), "d3m_camera_backward")
-        return (grad_vertices,) + (None,) * 10
+        grad_vertices = None
+        if st.need_mesh:
+            cam, _keep = cameras._camera_struct(st.camera, dev)
+            grad_vertices = torch.empty_like(vertices)
+            _lib.check(L.d3m_camera_backward(_lib.ptr(vertices), vertices.shape[0], ctypes.byref(cam), _lib.ptr(grad_sv),
+                                             _lib.ptr(grad_vertices), B, V, _lib.stream_ptr()), "d3m_camera_backward")
+        # a learnable camera: its parameters' gradient from the same grad_sv (d3m_camera_params_backward)
+        return (grad_vertices,) + (None,) * 10 + cameras.params_backward(st.camera, vertices, grad_sv, st.need_cp)
 
 
 def rasterize_mesh_modes(vertices, tri, camera, fill_back, image_size, anti_aliasing, return_alpha, return_depth,
@@ -1379,7 +1404,8 @@ def rasterize_mesh_modes(vertices, tri, camera, fill_back, image_size, anti_alia
     """(alpha, depth) images -- either may be left out -- of an indexed mesh seen through `camera` (the parameter block of
     cameras.look_at_params & co): the silhouette / depth modes of the renderer as one node.  See _RasterizeMeshModes."""
     alpha, depth = _RasterizeMeshModes.apply(vertices, tri, camera, bool(fill_back), int(image_size), bool(anti_aliasing),
-                                             float(near), float(far), float(eps), bool(return_alpha), bool(return_depth))
+                                             float(near), float(far), float(eps), bool(return_alpha), bool(return_depth),
+                                             *_camera_tensors(camera))
     return (alpha if return_alpha else None), (depth if return_depth else None)
 
 
@@ -1449,6 +1475,13 @@ def _device_light(light_cfg, screen_vertices, vertices, camera):
     return normalize_light(light_cfg, batch, vertices.device)
 
 
+def _camera_tensors(camera):
+    """The six parameter tensors of a camera inside a node (cameras.camera_inputs), autograd inputs of the node: a
+    parameter that requires grad receives its gradient from the node's backward pass."""
+    from . import cameras
+    return cameras.camera_inputs(camera) if camera is not None else (None,) * 6
+
+
 def rasterize_lit(screen_vertices, vertices, tri, textures, light_cfg, fill_back, image_size=DEFAULT_IMAGE_SIZE,
                   anti_aliasing=DEFAULT_ANTI_ALIASING, near=DEFAULT_NEAR, far=DEFAULT_FAR, eps=DEFAULT_EPS,
                   background_color=DEFAULT_BACKGROUND_COLOR, return_alpha=True, return_depth=True, view_groups=1,
@@ -1465,7 +1498,8 @@ def rasterize_lit(screen_vertices, vertices, tri, textures, light_cfg, fill_back
     rgb, alpha, depth = _RasterizeLit.apply(screen_vertices, vertices, tri, textures, light_cfg, fill_back, image_size,
                                             anti_aliasing, near, far, eps, background_color, True, return_alpha,
                                             return_depth, None, view_groups, defer_plan_join, camera, None, fit_hint,
-                                            *_device_light(light_cfg, screen_vertices, vertices, camera))
+                                            *_device_light(light_cfg, screen_vertices, vertices, camera),
+                                            *_camera_tensors(camera))
     return {'rgb': rgb, 'alpha': alpha if return_alpha else None, 'depth': depth if return_depth else None}
 
 
@@ -1531,7 +1565,7 @@ def rasterize_lit_fit(screen_vertices, vertices, tri, textures, light_cfg, fill_
     return _RasterizeLit.apply(screen_vertices, vertices, tri, textures, light_cfg, fill_back, image_size,
                                bool(anti_aliasing), near, far, eps, background_color, True, True, True,
                                (targets, images_out), view_groups, defer_plan_join, camera, grad_sink, None,
-                               *_device_light(light_cfg, screen_vertices, vertices, camera))
+                               *_device_light(light_cfg, screen_vertices, vertices, camera), *_camera_tensors(camera))
 
 
 def rasterize_rgbad(

@@ -13,6 +13,18 @@ from .rasterize import (light_on_device, rasterize, rasterize_depth, rasterize_l
                         rasterize_lit_image_grid, rasterize_mesh_modes, rasterize_rgbad, rasterize_silhouettes)
 
 
+CAMERA_MODES_IN_NODE = ('look_at', 'look', 'projection')
+
+
+def camera_in_node(camera_mode, vertices):
+    """The render nodes' camera route rule: a look_at, look or projection camera on vertices [B,V,3] runs INSIDE the node
+    (the node's first launch projects; its parameters are read from device memory and, when they require grad, are
+    autograd inputs of the node that receive their gradient from its backward pass).  Any other camera_mode (vertices as
+    they are) or vertices of another rank keep _transform's route.  viewing_angle and orig_size are host floats on either
+    route (they receive no gradient)."""
+    return camera_mode in CAMERA_MODES_IN_NODE and vertices.ndimension() == 3
+
+
 class Renderer(nn.Module):
     def __init__(self, image_size=256, anti_aliasing=True, background_color=[0, 0, 0],
                  fill_back=True, camera_mode='projection',
@@ -158,10 +170,12 @@ class Renderer(nn.Module):
         return not light_on_device(self._light_cfg())
 
     def _camera_in_node(self, vertices, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
-        """Cameras with constant parameters run INSIDE the render node (its first launch projects, lights and clears; one
-        gradient for the mesh instead of the camera's plus the light's): their parameter block, else None (a parameter that
-        requires grad, or no camera_mode: _transform's torch composition / identity)."""
-        if vertices.ndimension() != 3:
+        """Cameras run INSIDE the render node (its first launch projects, lights and clears; one gradient for the mesh
+        instead of the camera's plus the light's; parameters that require grad are inputs of the node and get theirs from
+        the node's backward pass): their parameter block, else None (camera_in_node: _transform's route).  Parameters are
+        [3] or [B,3] (t also [B,1,3]; K / R [3,3] or [B,3,3]); a batch other than 1 or B raises ValueError here, before any
+        launch."""
+        if not camera_in_node(self.camera_mode, vertices):
             return None
         if self.camera_mode == 'look_at':
             return cameras.look_at_params(vertices, self.eye, defer_basis=True,
@@ -207,11 +221,11 @@ class Renderer(nn.Module):
         return (for display / logging; gradients flow through the returned objective only).  `grad_sink` = (grad_vertices
         like `vertices`, grad_textures like `textures` | None, loss [1]): buffers of the CALLER that the node writes the
         objective and its two gradients into in place (per call, never remembered; ignored unless they fit this call's
-        tensors exactly and the camera runs inside the node)."""
+        tensors exactly and the camera runs inside the node -- a learnable camera's gradient is returned by autograd as usual)."""
         if not self._on_the_fly():
             raise ValueError("render_fit_loss needs lighting_on_the_fly")
-        # look_at cameras with constant parameters run INSIDE the node (one gradient for the mesh instead of the camera's
-        # plus the light's; results straight into the caller's grad_sink buffers when it has set them)
+        # the camera runs INSIDE the node (one gradient for the mesh instead of the camera's plus the light's; results
+        # straight into the caller's grad_sink buffers when it has set them; a learnable camera is an input of the node)
         cam = self._camera_in_node(vertices, K, R, t, dist_coeffs, orig_size)
         sv = None if cam is not None else self._transform(vertices, K, R, t, dist_coeffs, orig_size)
         return rasterize_lit_fit(sv, vertices, faces, textures, self._light_cfg(), self.fill_back, targets,
@@ -227,7 +241,7 @@ class Renderer(nn.Module):
             raise ValueError("render_fit_loss_manual needs lighting_on_the_fly, one constant light for the batch and camera_mode "
                              "'look_at'")
         cam = self._camera_in_node(vertices)
-        if cam is None:
+        if cam is None or cameras.camera_learnable(cam):
             raise ValueError("render_fit_loss_manual: the camera's parameters must be constants (no requires_grad)")
         return manual.forward(vertices, faces, textures, self._light_cfg(), self.fill_back, targets, self.image_size,
                               self.near, self.far, self.rasterizer_eps, self.background_color, cam, grad_sink=grad_sink,

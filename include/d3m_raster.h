@@ -348,6 +348,27 @@ int d3m_camera_backward(const float* vertices, int vertices_batch, const d3m_cam
 int d3m_camera_backward_add(const float* vertices, int vertices_batch, const d3m_camera* cam,
                             const float* grad_out, float* grad_vertices, int batch_size, int num_vertices,
                             d3m_stream_t stream);
+/* d3m_camera_params_backward -- the gradient of the camera's PARAMETERS from grad_screen [B,V,3] (what d3m_camera_backward
+ * takes to the vertices) on vertices [vertices_batch,V,3].  The camera block is read when the kernels run (a captured graph
+ * reads in-place updates of the parameters at replay).  look / look_at: the gradient of the rows (x, y, z) of cam->rot and
+ * of the translation; with `basis` (the vectors cam->rot was made of, as d3m_lit_front takes them) the rows' gradient goes
+ * on through the basis (F.normalize(eps=1e-5): in the clamped branch not through the norm) to eye, at_or_direction and up.
+ * projection: R, t, K (row 3 gets zeros, as in the reference) and dist.  `grad` fields are WRITTEN in the shape of the
+ * matching parameter (the batch of cam / basis; batch 1: the sum over the views in view order); a NULL field is skipped;
+ * at_or_direction / up need `basis`, K / dist a projection.  Fixed-order two-stage reduction (per-(view, vertex chunk)
+ * partials in `workspace`, then one ordered pass; no float atomics): bit-reproducible for a given grad_screen. */
+typedef struct d3m_camera_grad {      /* each field: device, written in the shape of the matching parameter; NULL = skipped */
+    float* eye_or_t;                  /* look_at / look: eye [eye_batch,3];  projection: t [eye_batch,3] */
+    float* at_or_direction;           /* look_at: at;  look: direction  [at_batch,3] (needs the d3m_basis) */
+    float* up;                        /* [up_batch,3] (needs the d3m_basis) */
+    float* rot;                       /* projection: R [rot_batch,3,3];  look / look_at: the basis rows [rot_batch,3,3] */
+    float* K;                         /* projection only: K [K_batch,3,3] (row 3 gets zeros, as in the reference) */
+    float* dist;                      /* projection only: [dist_batch,5] */
+} d3m_camera_grad;
+size_t d3m_camera_params_backward_workspace_bytes(int batch_size, int num_vertices, int mode);
+int d3m_camera_params_backward(const float* vertices, int vertices_batch, const d3m_camera* cam, const d3m_basis* basis,
+                               const float* grad_screen, const d3m_camera_grad* grad, int batch_size, int num_vertices,
+                               void* workspace, size_t workspace_bytes, d3m_stream_t stream);
 
 /* vertices_to_faces (neural_renderer/vertices_to_faces.py:16-22) with the fill_back copy made on the
  * fly (renderer.py:86): faces_out [B,F',3,3], F' = 2F if fill_back else F; face F+f is face f with
