@@ -10,7 +10,8 @@
 //   0. visibility     faces that own no pixel cannot contribute: one mark per face (left by the forward's tile pass, or
 //                     by k_mark_visible_bytes from a face_index_map), then flags + compacted list, shared with the
 //                     gathered texture / depth pass through d3m_visibility;
-//  THE PLAN (geometry only: faces + face_index_map; d3m_edge_plan can build it right after the forward pass)
+//  THE PLAN (geometry only: faces + face_index_map; d3m_edge_plan can build it right after the forward pass): in ONE pass,
+//     k_edge_scatter alone writing every line's records into a fixed slice of the blob (struct EdgePlan), or COUNTED:
 //   1. k_edge_count_window   a workgroup iteration takes 42 visible faces x 6 (edge, axis) lanes; a lane crosses the
 //                     consecutive lines d0_from..d0_to, so it adds +1 / -1 at the ends of its range in an LDS array
 //                     indexed by the line, a running sum turns the touched window into counts, and every counted
@@ -28,8 +29,8 @@
 //                     record into a segment clipped to the extent, walks it if short, queues it in LDS if long; the
 //                     queued segments are ordered by length and walked sixteen per wave (four lanes each) with the
 //                     factored distance.  The walks never touch global memory;
-//      k_edge_overflow  crossings that got no record because the workspace is smaller than the scene needs are walked
-//                     from global memory by one thread each; leaves at once otherwise;
+//      k_edge_overflow  crossings without a usable record (a workspace smaller than the scene needs, a line fuller than its
+//                     one-pass slice) are walked from global memory by one thread each; leaves at once otherwise;
 //   6. k_edge_gather  six lanes per visible face fetch their crossings' results (xpos) and add them in order; stored to
 //                     grad_faces or accumulated into the vertex gradient (VertexTarget).
 // Deterministic up to the final vertex atomics.  The reference OVERWRITES the 9 entries of every front-facing face
@@ -122,7 +123,7 @@ struct EdgeGradArgs {
     __device__ __forceinline__ int extent_lo(size_t line) const { return nz_lo_inv ? S - nz_lo_inv[line] : 0; }
     __device__ __forceinline__ int extent_hi(size_t line) const { return nz_hi1 ? nz_hi1[line] - 1 : S - 1; }
     // alpha only: the lines k_edge_lines_alpha (in front of k_edge_lines) LEFT to it -- those of many contributing pixels --
-    // as a list and its length (EdgePlan::alloc[2]: zero when the plan is built, handed back zeroed by k_edge_gather); NULL =
+    // as a list and its length (EdgePlan::alloc[EG_ALLOC_LEFT]: zero when the plan is built, handed back zeroed by k_edge_gather); NULL =
     // no such pass ran, k_edge_lines takes every line
     int* line_left;
     int* n_left;
@@ -626,22 +627,64 @@ struct EdgePlan {
     int* visible_list;   // [B*F]   their compacted indices                > (or one built in the workspace)
     int* n_visible;      // [1]                                            /
     int2* lane_cross;    // [6*B*F] per (visible face, edge, axis) lane: first crossing within its workgroup, count
-    int* lane_block;     // [ceil(B*F/42)+1] crossings per k_edge_count workgroup iteration, then (in place) their scan
-    int* line_count;     // [B*2*S] crossings on each line (zeroed per call)
-    int* line_cursor;    // [B*2*S] records written so far under each line (zeroed per call)
-    int2* line_slice;    // [B*2*S] (first record, number of records) of the line's slice of xrec
-    int* alloc;          // [0] total crossings (written by the block scan), [1] slice cursor (zeroed per call)
+    int* lane_block;     // [ceil(B*F/42)+1] first crossing of every workgroup iteration (counted form: its count first)
+    int* line_cursor;    // [B*2*S] records written so far under each line (zeroed per call; the counted form counts
+                         //         the line's crossings in it first, and k_alloc_plan zeroes it again)
+    int2* line_slice;    // [B*2*S] counted form: (first record, number of crossings) of the line's slice of xrec
+    int* alloc;          // [EG_ALLOC_INTS] counters (zeroed per call): EG_ALLOC_*
     uint4* xrec;         // [cap]
-    float2* results;     // [2 * cap] written by the line kernel (record order) or the overflow kernel (crossing order)
-    int* xpos;           // [cap]     record position of every crossing (plan complete only)
-    int cap;             // crossings the record / result arrays can hold; the rest is walked by k_edge_overflow
+    float2* results;     // [2 * cap] written by the line kernel, in record order
+    int* xpos;           // [cap]     record position of every crossing (-1: none)
+    int cap;             // crossings the record / result arrays can hold
+    int cap_line;        // > 0: ONE-PASS form, line l owns records [l * cap_line, (l + 1) * cap_line); 0: counted form
 };
 
-// The records are written iff ALL the batch's crossings fit (uniform over a launch): they are then dense and complete,
-// xrec[0 .. alloc[0]), grouped by line.  Otherwise (a workspace smaller than the scene needs) k_edge_overflow walks
-// every crossing the slow way.
+// The two forms of the plan (the host picks one per blob: edge_plan_form).
+//   COUNTED   k_edge_count(_window) counts the crossings of every workgroup iteration and every line, k_alloc_plan turns the
+//             counts into bases and dense slices, k_edge_scatter writes the records.  The records are written iff ALL the
+//             batch's crossings fit (alloc[EG_ALLOC_TOTAL] <= cap, uniform over a launch); otherwise k_edge_overflow walks
+//             every crossing the slow way.
+//   ONE-PASS  k_edge_scatter alone: a workgroup iteration takes its crossing base with one returning atomic on one of
+//             EG_PLAN_CURSORS cursors (iteration blk on cursor blk % EG_PLAN_CURSORS, each owning a 1/EG_PLAN_CURSORS share
+//             of the crossing indices; bases only need to be stable, not ascending; the cursors lie 256 bytes apart: the
+//             first iterations of every workgroup take theirs at the same moment, and same-line atomics serialise), and a
+//             record goes to the fixed slice
+//             line * cap_line + its rank under the line's cursor -- no counts, no allocation pass, no slice look-up.
+//             A cursor that runs past its share sets EG_ALLOC_FULL: no record is used and k_edge_overflow walks every
+//             crossing, as in the counted form.  A line with more crossings to record than cap_line SPILLS (EG_ALLOC_SPILL):
+//             k_edge_overflow walks all of the line's crossings, and sets their positions to -1 (k_edge_gather then ignores
+//             the results the line kernels left for the cap_line of them that got a record).  Spilling whole lines, not single crossings, keeps the results independent of which crossings won
+//             the line's cursor: every count involved is a sum, the same in every run.
+enum : int {
+    EG_ALLOC_TOTAL = 0,       // counted: crossings of the batch (k_alloc_plan)
+    EG_ALLOC_SLICES = 1,      // counted: slice cursor
+    EG_ALLOC_LEFT = 2,        // k_edge_lines_alpha's list of left lines (EdgeGradArgs::n_left)
+    EG_ALLOC_SPILL = 3,       // one-pass: 1 when some line holds more crossings than cap_line
+    EG_ALLOC_FULL = 4,        // one-pass: 1 when some cursor ran past its share of the crossing indices
+    EG_ALLOC_CURSORS = 64     // one-pass: the iterations' crossing cursors, EG_CURSOR_STRIDE ints apart
+};
+constexpr int EG_PLAN_CURSORS = 32, EG_CURSOR_STRIDE = 64;
+constexpr int EG_ALLOC_INTS = EG_ALLOC_CURSORS + EG_PLAN_CURSORS * EG_CURSOR_STRIDE;
 
-__device__ __forceinline__ bool plan_complete(const EdgePlan& w) { return w.alloc[0] <= w.cap; }
+// the records are used (else k_edge_overflow walks every crossing)
+__device__ __forceinline__ bool plan_records(const EdgePlan& w) {
+    return w.cap_line ? w.alloc[EG_ALLOC_FULL] == 0 : w.alloc[EG_ALLOC_TOTAL] <= w.cap;
+}
+// ... and every crossing that wants one has one: k_edge_overflow has nothing to do
+__device__ __forceinline__ bool plan_complete(const EdgePlan& w) {
+    return plan_records(w) && (w.cap_line == 0 || w.alloc[EG_ALLOC_SPILL] == 0);
+}
+// a one-pass line with more crossings than its slice (n = its cursor): walked by k_edge_overflow instead
+__device__ __forceinline__ bool line_spilled(const EdgePlan& w, int n) { return w.cap_line > 0 && n > w.cap_line; }
+// the records under a line and where they start: its fixed slice (one-pass) or its counted slice.  A spilled line's records
+// are walked all the same (k_edge_overflow then takes their crossings' positions back)
+__device__ __forceinline__ int line_records(const EdgePlan& w, size_t line) {
+    const int n = w.line_cursor[line];
+    return w.cap_line ? min(n, w.cap_line) : n;
+}
+__device__ __forceinline__ int line_first_record(const EdgePlan& w, size_t line) {
+    return w.cap_line ? (int)line * w.cap_line : w.line_slice[line].x;
+}
 
 // ---- the lines of one workgroup iteration, counted in LDS ---------------------------------------------------------
 // A (face, edge, axis) lane crosses the CONSECUTIVE lines d0_from .. d0_to of its axis, and the 42 neighbouring faces of
@@ -716,7 +759,7 @@ __global__ void __launch_bounds__(256) k_edge_count_window(FS fs, int is, EdgePl
                 run = __builtin_amdgcn_readlane(incl, 63);
                 if (in) {
                     win.cnt(axis)[d0] = 0;
-                    if (incl > 0) atomicAdd(&w.line_count[((size_t)view * 2 + axis) * is + d0], incl);
+                    if (incl > 0) atomicAdd(&w.line_cursor[((size_t)view * 2 + axis) * is + d0], incl);
                 }
             }
         }
@@ -724,7 +767,7 @@ __global__ void __launch_bounds__(256) k_edge_count_window(FS fs, int is, EdgePl
         if (on && n_cross > 0 && (t.bn_axis[threadIdx.x] >> 1) != view) {
             const int l = threadIdx.x;
             const size_t line0 = ((size_t)(t.bn_axis[l] >> 1) * 2 + (t.bn_axis[l] & 1)) * is + t.d0_from[l];
-            for (int k = 0; k < n_cross; k++) atomicAdd(&w.line_count[line0 + k], 1);
+            for (int k = 0; k < n_cross; k++) atomicAdd(&w.line_cursor[line0 + k], 1);
         }
         __syncthreads();                                    // the tables are rewritten by the next iteration
     }
@@ -757,7 +800,7 @@ __global__ void __launch_bounds__(256) k_edge_count(FS fs, int is, EdgePlan w) {
             }
             // neighbouring crossings fall on the same lines: one atomic per distinct line of the wave (uniform call site)
             const unsigned long long same = wave_match_any((uint32_t)line, c < total);
-            if (c < total && lane_id() == __builtin_ctzll(same)) atomicAdd(&w.line_count[line], __popcll(same));
+            if (c < total && lane_id() == __builtin_ctzll(same)) atomicAdd(&w.line_cursor[line], __popcll(same));
         }
         __syncthreads();                                    // the table is rewritten by the next iteration
     }
@@ -785,17 +828,18 @@ __global__ void __launch_bounds__(256) k_alloc_ranges(const int* __restrict__ co
 
 // ---- 2'. both allocations of the plan in ONE launch ---------------------------------------------------------------
 // The count pass leaves two arrays of counts: crossings per workgroup iteration (lane_block: the scatter and gather
-// passes need each iteration's first crossing) and crossings per line (line_count: the scatter pass needs each line's
-// slice of the records).  Neither needs its slices in index order -- only disjoint --, so both are allocated order-free:
+// passes need each iteration's first crossing) and crossings per line (counted into line_cursor: the scatter pass needs
+// each line's slice of the records, and takes the cursor back zeroed).  Neither needs its slices in index order -- only disjoint --, so both are allocated order-free:
 // 256 entries per workgroup, one returning atomic each (a few dozen per launch on one address, not thousands).  Round 3
 // ran an ordered single-workgroup scan for the first (k_scan_small, 11 us of one workgroup on an otherwise idle chip) and
 // k_alloc_ranges for the second; with the step's kernels on one stream that was 15 us of its critical path, now 5.
 // Workgroups [0, blocks_a) take lane_block (in place: count -> first crossing; the grid is sized for EVERY face being
-// visible, the workgroups past ceil(*n_visible / faces per iteration) leave at once), the rest line_count -> line_slice.
-// cursor_a ends as the number of crossings (EdgePlan::alloc[0]: plan_complete()).
+// visible, the workgroups past ceil(*n_visible / faces per iteration) leave at once), the rest line_count -> line_slice
+// (and line_count back to zero: it is the scatter pass's line cursor).
+// cursor_a ends as the number of crossings (EdgePlan::alloc[EG_ALLOC_TOTAL]: plan_records()).
 __global__ void __launch_bounds__(256) k_alloc_plan(int* __restrict__ lane_block, const int* __restrict__ n_visible, int per_block,
                                                    int* __restrict__ cursor_a, int blocks_a,
-                                                   const int* __restrict__ line_count, int2* __restrict__ line_slice,
+                                                   int* __restrict__ line_count, int2* __restrict__ line_slice,
                                                    int* __restrict__ cursor_b, long n_lines) {
     __shared__ int s_wave[4];
     __shared__ int s_base;
@@ -817,7 +861,7 @@ __global__ void __launch_bounds__(256) k_alloc_plan(int* __restrict__ lane_block
     if (i < n) {
         const int at = s_base + s_wave[wv] + incl - c;
         if (first) lane_block[i] = at;
-        else line_slice[i] = make_int2(at, c);
+        else { line_slice[i] = make_int2(at, c); line_count[i] = 0; }
     }
 }
 
@@ -827,11 +871,14 @@ __global__ void __launch_bounds__(256) k_alloc_plan(int* __restrict__ lane_block
 // `parts` (>= 1): the rounds of one block of faces are dealt to that many workgroups -- a coarse mesh has few blocks (722
 // triangles: 35) of faces with dozens of crossings per edge, i.e. a few workgroups with thirty rounds of dependent look-ups
 // each while the rest of the chip idles (125 us); the host sets it from the batch's face count (1 for ordinary meshes).
-template <class FS>
+// ONE_PASS (w.cap_line > 0, parts == 1): the pass also publishes the lanes' crossing counts and takes the iteration's
+// crossing base itself (see EdgePlan); a record's place is computed from its line, not loaded.
+template <class FS, bool ONE_PASS>
 __global__ void __launch_bounds__(256) k_edge_scatter(FS fs, const int32_t* __restrict__ face_index_map, int is, EdgePlan w,
                                                      int parts) {
     __shared__ LaneTable t;
     __shared__ float s_slope[3][256];
+    __shared__ int s_cbase;
     const int n_blocks = (*w.n_visible + EG_FACES_PER_BLOCK - 1) / EG_FACES_PER_BLOCK;
     const int n_units = n_blocks * parts;
     const XcdOrder xo(n_units);
@@ -842,28 +889,43 @@ __global__ void __launch_bounds__(256) k_edge_scatter(FS fs, const int32_t* __re
         bool on;
         int pos = 0, ea = 0, n_cross = 0;
         const int total = publish_lanes(fs, w.visible_list, w.n_visible, blk, is, t, on, pos, ea, n_cross);
-        const long cbase = w.lane_block[blk];               // scanned: first crossing of this workgroup
+        if constexpr (ONE_PASS) {
+            if (threadIdx.x < EG_FACES_PER_BLOCK * 6 && blk * EG_FACES_PER_BLOCK + (int)threadIdx.x / 6 < *w.n_visible)
+                w.lane_cross[(size_t)blk * EG_FACES_PER_BLOCK * 6 + threadIdx.x] = make_int2(t.pre[threadIdx.x], n_cross);
+            if (threadIdx.x == 0) {
+                const int r = blk % EG_PLAN_CURSORS;
+                const long share = w.cap / EG_PLAN_CURSORS;
+                const long at = (long)r * share + atomicAdd(&w.alloc[EG_ALLOC_CURSORS + r * EG_CURSOR_STRIDE], total);
+                const bool fits = at + total <= (long)(r + 1) * share;
+                if (!fits) w.alloc[EG_ALLOC_FULL] = 1;
+                else w.lane_block[blk] = (int)at;
+                s_cbase = fits ? (int)at : -1;
+            }
+        }
         {   // the lane's slopes, once (see EdgeSlopes)
             const int l = threadIdx.x;
             const EdgeSlopes sl = edge_slopes(t.p[0][l], t.p[1][l], t.p[2][l], t.p[3][l], t.p[4][l], t.p[5][l]);
             s_slope[0][l] = sl.s01; s_slope[1][l] = sl.s02; s_slope[2][l] = sl.s12;
         }
         __syncthreads();
-        for (int c0 = part * 256; c0 < total; c0 += parts * 256) {
+        // scanned: first crossing of this workgroup (one-pass: < 0 when its cursor's share is full -- nothing is used then)
+        const long cbase = ONE_PASS ? (long)s_cbase : (long)w.lane_block[blk];
+        const bool records = ONE_PASS ? cbase >= 0 : plan_records(w);            // (uniform)
+        for (int c0 = part * 256; records && c0 < total; c0 += parts * 256) {
             const int c = c0 + threadIdx.x;
             const bool active = c < total;
             int l = 0;
             size_t line = 0;
-            int2 slice = make_int2(0, 0);
+            int slice_x = 0;
             if (active) {
                 l = crossing_lane(t, c);
                 line = ((size_t)(t.bn_axis[l] >> 1) * 2 + (t.bn_axis[l] & 1)) * is + t.d0_from[l] + (c - t.pre[l]);
-                slice = w.line_slice[line];
+                if (!ONE_PASS) slice_x = w.line_slice[line].x;
             }
             // the geometry first: a crossing that is outside the image or whose walks cannot contribute takes no place
             XGeom g;
             bool wants = false;
-            if (active && plan_complete(w)) {
+            if (active) {
                 const int bn = t.bn_axis[l] >> 1, axis = t.bn_axis[l] & 1, d0 = t.d0_from[l] + (c - t.pre[l]);
                 const int32_t* view = face_index_map + (size_t)bn * is * is;
                 g = crossing_geometry(t.p[0][l], t.p[1][l], t.p[2][l], t.p[3][l], t.p[4][l], t.p[5][l],
@@ -878,22 +940,31 @@ __global__ void __launch_bounds__(256) k_edge_scatter(FS fs, const int32_t* __re
             if (wants && lane_id() == leader) cursor_base = atomicAdd(&w.line_cursor[line], n);
             const int in_line = __shfl(cursor_base, leader, 64) + mask_rank(same);
             if (wants) {
-                w.xrec[(size_t)slice.x + in_line] = geometry_to_record(g, t.fn[l]);
-                w.xpos[cbase + c] = slice.x + in_line;
+                if (ONE_PASS && in_line >= w.cap_line) {          // the line's slice is full: the line spills
+                    w.xpos[cbase + c] = -1;
+                    w.alloc[EG_ALLOC_SPILL] = 1;
+                } else {
+                    const size_t at = ONE_PASS ? line * (size_t)w.cap_line + in_line : (size_t)slice_x + in_line;
+                    w.xrec[at] = geometry_to_record(g, t.fn[l]);
+                    w.xpos[cbase + c] = (int)at;
+                }
             }
         }
         __syncthreads();
     }
 }
 
-// ---- 4. crossings that have no record: walked by the owning thread, straight from global memory ---------------
+// ---- 4. crossings without a usable record: walked by one thread each, straight from global memory ---------------
 // Only when the workspace is too small for the scene (default capacity: eg_default_crossings, two crossings per face of the
-// batch or three per raster pixel).
-// Leaves at once otherwise.  Results: the crossing's own slots when it has them, else the lane's overflow sum.
+// batch or three per raster pixel): every crossing when the plan holds no records, else those of the lines that spilled.
+// Leaves at once otherwise.  Each lane's sum over its walked crossings, added in crossing order (outward then inward, as
+// k_edge_gather adds the results), is STORED to lane_partial for every lane: the same bits in every run.
 template <class FS>
 __global__ void __launch_bounds__(256) k_edge_overflow(FS fs, EdgeGradArgs a, EdgePlan w, float2* __restrict__ lane_partial) {
     if (plan_complete(w)) return;                           // every crossing has a record: k_edge_lines did it all (uniform exit)
     __shared__ LaneTable t;
+    __shared__ float4 s_r[256];
+    const bool records = plan_records(w);
     const int is = a.S;
     const float two_over_is = 2.0f / (float)is;
     const int n_blocks = (*w.n_visible + EG_FACES_PER_BLOCK - 1) / EG_FACES_PER_BLOCK;
@@ -904,34 +975,47 @@ __global__ void __launch_bounds__(256) k_edge_overflow(FS fs, EdgeGradArgs a, Ed
         bool on;
         int pos = 0, ea = 0, n_cross = 0;
         const int total = publish_lanes(fs, w.visible_list, w.n_visible, blk, is, t, on, pos, ea, n_cross);
-        const long cbase = w.lane_block[blk];
-        for (int c = threadIdx.x; c < total; c += 256) {
-            const int l = crossing_lane(t, c);
-            const int d0 = t.d0_from[l] + (c - t.pre[l]);
-            const int bn = t.bn_axis[l] >> 1, axis = t.bn_axis[l] & 1, fn = t.fn[l];
-            const size_t line = ((size_t)bn * 2 + axis) * is + d0;
-            const size_t base = (size_t)bn * is * is;
-            const XGeom xg = crossing_geometry(t.p[0][l], t.p[1][l], t.p[2][l], t.p[3][l], t.p[4][l], t.p[5][l],
-                                               edge_slopes(t.p[0][l], t.p[1][l], t.p[2][l], t.p[3][l], t.p[4][l], t.p[5][l]),
-                                               axis, fn, is, d0,
-                                               [&](int e0, int e1) { return __float_as_int(a.rec_dot(a.pixel(axis, base, e0, e1)).y); });
+        const long cbase = records ? (long)w.lane_block[blk] : 0;
+        const int me = threadIdx.x, my_first = t.pre[me], my_end = my_first + n_cross;
+        float2 acc = make_float2(0.0f, 0.0f);
+        for (int c0 = 0; c0 < total; c0 += 256) {
+            const int c = c0 + threadIdx.x;
+            float4 r = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (c < total) {
+                const int l = crossing_lane(t, c);
+                const int d0 = t.d0_from[l] + (c - t.pre[l]);
+                const int bn = t.bn_axis[l] >> 1, axis = t.bn_axis[l] & 1, fn = t.fn[l];
+                const size_t line = ((size_t)bn * 2 + axis) * is + d0;
+                if (!records || line_spilled(w, w.line_cursor[line])) {
+                    if (records) w.xpos[cbase + c] = -1;         // (this crossing's record, if it has one, is not used)
+                    const size_t base = (size_t)bn * is * is;
+                    const XGeom xg = crossing_geometry(t.p[0][l], t.p[1][l], t.p[2][l], t.p[3][l], t.p[4][l], t.p[5][l],
+                                                       edge_slopes(t.p[0][l], t.p[1][l], t.p[2][l], t.p[3][l], t.p[4][l], t.p[5][l]),
+                                                       axis, fn, is, d0,
+                                                       [&](int e0, int e1) { return __float_as_int(a.rec_dot(a.pixel(axis, base, e0, e1)).y); });
 #pragma unroll
-            for (int which = 0; which < 2; which++) {
-                float g0 = 0, g1 = 0;
-                Segment sg;
-                if (geometry_segment(xg, which, axis, d0, is, a.extent_lo(line), a.extent_hi(line), sg)) {
-                    const SegRef ref = load_ref(a, axis, base, sg.d0, sg.ref_pos);
-                    walk_inline(a, base, sg, sg.from, sg.to, ref, fn, two_over_is, g0, g1);
-                }
-                if (cbase + c < (long)w.cap) {
-                    w.results[2 * (cbase + c) + which] = make_float2(g0, g1);
-                } else if (g0 != 0 || g1 != 0) {
-                    const size_t lane_id6 = ((size_t)blk * EG_FACES_PER_BLOCK) * 6 + l;
-                    atomicAdd(&lane_partial[lane_id6].x, g0);
-                    atomicAdd(&lane_partial[lane_id6].y, g1);
+                    for (int which = 0; which < 2; which++) {
+                        float g0 = 0, g1 = 0;
+                        Segment sg;
+                        if (geometry_segment(xg, which, axis, d0, is, a.extent_lo(line), a.extent_hi(line), sg)) {
+                            const SegRef ref = load_ref(a, axis, base, sg.d0, sg.ref_pos);
+                            walk_inline(a, base, sg, sg.from, sg.to, ref, fn, two_over_is, g0, g1);
+                        }
+                        if (which == 0) { r.x = g0; r.y = g1; } else { r.z = g0; r.w = g1; }
+                    }
                 }
             }
+            s_r[threadIdx.x] = r;
+            __syncthreads();
+            for (int k = max(my_first, c0); k < min(my_end, c0 + 256); k++) {       // this lane's crossings of the round
+                const float4 q = s_r[k - c0];
+                acc.x += q.x; acc.y += q.y;
+                acc.x += q.z; acc.y += q.w;
+            }
+            __syncthreads();
         }
+        if (me < EG_FACES_PER_BLOCK * 6 && blk * EG_FACES_PER_BLOCK + me / 6 < *w.n_visible)
+            lane_partial[(size_t)blk * EG_FACES_PER_BLOCK * 6 + me] = acc;
         __syncthreads();
     }
 }
@@ -994,12 +1078,8 @@ __global__ void __launch_bounds__(WAVES * 64, 8) k_edge_lines(EdgeGradArgs a, Ed
     // (two workgroups = the same eight waves per SIMD, where 8-wave workgroups would leave the CU at four or six)
     constexpr int EG_LINE_THREADS = WAVES * 64, EG_QUEUE = EG_LINE_THREADS, EG_LINE_WAVES = WAVES;
     extern __shared__ __attribute__((aligned(16))) float s_line[];
-    if (!plan_complete(w)) {          // no records at all: k_edge_overflow walks every crossing; zero the sums it adds to
-        const long n = (long)*w.n_visible * 6;
-        for (long i = (long)blockIdx.x * EG_LINE_THREADS + threadIdx.x; i < n; i += (long)gridDim.x * EG_LINE_THREADS)
-            lane_partial[i] = make_float2(0.0f, 0.0f);
-        return;
-    }
+    (void)lane_partial;
+    if (!plan_records(w)) return;     // no records at all: k_edge_overflow walks every crossing (uniform exit)
     __shared__ __attribute__((aligned(16))) uint32_t s_items[EG_LINE_THREADS * EG_ITEM_DW];
     __shared__ int s_hist[33];
     __shared__ unsigned short s_order[EG_LINE_THREADS];
@@ -1025,7 +1105,7 @@ __global__ void __launch_bounds__(WAVES * 64, 8) k_edge_lines(EdgeGradArgs a, Ed
     // of 16) -- dealt to different XCDs every one of them is fetched into up to 8 L2s (1.74 GB of HBM-side traffic per
     // launch for 0.3 GB of maps).  XCD x takes the contiguous lines [x*per, (x+1)*per).
     auto do_line = [&](const size_t line) {                   // (b*2 + axis)*S + d0
-    const int n_x = __builtin_amdgcn_readfirstlane(w.line_cursor[line]);      // crossing records under this line
+    const int n_x = __builtin_amdgcn_readfirstlane(line_records(w, line));    // crossing records under this line
     if (n_x <= 0) return;                                     // nothing to do (uniform exit)
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // the lane number where it is needed, from the thread index behind an opaque copy: a `lane` kept live through the set-up
@@ -1035,7 +1115,7 @@ __global__ void __launch_bounds__(WAVES * 64, 8) k_edge_lines(EdgeGradArgs a, Ed
     const int axis = (int)((line / is) & 1);
     const size_t bn = line / ((size_t)2 * is);
     const size_t view_base = bn * is * is;
-    const int x_first = __builtin_amdgcn_readfirstlane(w.line_slice[line].x);
+    const int x_first = __builtin_amdgcn_readfirstlane(line_first_record(w, line));
     const uint4* xrec = w.xrec + (size_t)x_first;
     const float two_over_is = 2.0f / (float)is;
     // only the line's non-zero-gradient extent is staged: every segment is clipped to it (geometry_segment)
@@ -1473,16 +1553,16 @@ __global__ void __launch_bounds__(EGA_THREADS) k_edge_lines_alpha(EdgeGradArgs a
     extern __shared__ __attribute__((aligned(16))) float s_aline[];
     __shared__ unsigned short s_raw[2][EGA_LIST], s_pos[2][EGA_LIST];     // [0]: counts against alpha_ref = 1, [1]: against 0
     __shared__ int s_n[2], s_odd;
-    if (!plan_complete(w)) return;                            // (k_edge_lines / k_edge_overflow handle that case)
+    if (!plan_records(w)) return;                             // (k_edge_overflow handles that case)
     const int is = a.S;
     const XcdOrder xo((int)a.n_lines);
     const size_t line = (size_t)xo.unit((int)blockIdx.x);     // (b*2 + axis)*S + d0
     if (line >= a.n_lines) return;
-    const int n_x = __builtin_amdgcn_readfirstlane(w.line_cursor[line]);
+    const int n_x = __builtin_amdgcn_readfirstlane(line_records(w, line));
     if (n_x <= 0) return;
+    const int x_first = __builtin_amdgcn_readfirstlane(line_first_record(w, line));
     const int d0 = (int)(line % is), axis = (int)((line / is) & 1);
     const size_t bn = line / ((size_t)2 * is), view_base = bn * is * is;
-    const int x_first = __builtin_amdgcn_readfirstlane(w.line_slice[line].x);
     const int p_lo = __builtin_amdgcn_readfirstlane(a.extent_lo(line));
     const int p_hi = __builtin_amdgcn_readfirstlane(a.extent_hi(line));
     float* s_al = s_aline;                                    // [S] alpha of the whole line (a walk's reference pixel may lie
@@ -1594,12 +1674,13 @@ __global__ void __launch_bounds__(256) k_edge_gather(FS fs, EdgePlan w, const fl
                                                     const float* __restrict__ go, float* __restrict__ grad_faces,
                                                     VertexTarget vt, int parts) {
     __shared__ float2 s_g[256];
-    if (blockIdx.x == 0 && threadIdx.x == 0) w.alloc[2] = 0;    // (k_edge_lines_alpha's list of left lines: EdgeGradArgs::n_left)
+    if (blockIdx.x == 0 && threadIdx.x == 0) w.alloc[EG_ALLOC_LEFT] = 0;    // (k_edge_lines_alpha's list of left lines)
     const int n_vis = *w.n_visible;
     const int n_blocks = (n_vis + EG_FACES_PER_BLOCK - 1) / EG_FACES_PER_BLOCK;
     const int n_units = n_blocks * parts;
     const XcdOrder xo(n_units);
-    const bool complete = plan_complete(w);      // results in record order (found through xpos), else in crossing order
+    // results in record order, found through xpos; what k_edge_overflow walked is in lane_partial
+    const bool records = plan_records(w), complete = plan_complete(w);
     const float go_abs = go ? fabsf(*go) : 1.0f; // the magnitude of the factor the records lacked (EdgeGradArgs::go)
     for (int i = blockIdx.x; xo.more(i); i += gridDim.x) {
         const int unit = xo.unit(i);
@@ -1610,16 +1691,16 @@ __global__ void __launch_bounds__(256) k_edge_gather(FS fs, EdgePlan w, const fl
         const bool on = t < EG_FACES_PER_BLOCK * 6 && pos < n_vis;
         float2 g = make_float2(0.0f, 0.0f);
         if (on) {
-            const int2 lc = w.lane_cross[(size_t)pos * 6 + ea];
             if (!complete && part == 0) g = lane_partial[(size_t)pos * 6 + ea];
             // slots (2c, 2c+1) of the lane's crossings c, contiguous and 16-byte aligned: one float4 per crossing, four
-            // crossings requested per round, added in slot order; crossings past cap were folded into lane_partial
-            const long c_first = (long)w.lane_block[blk] + lc.x, c_last = min(c_first + (long)lc.y, (long)w.cap);
+            // crossings requested per round, added in slot order
+            const int2 lc = records ? w.lane_cross[(size_t)pos * 6 + ea] : make_int2(0, 0);
+            const long c_first = records ? (long)w.lane_block[blk] + lc.x : 0, c_last = min(c_first + (long)lc.y, (long)w.cap);
             const float4* res4 = (const float4*)w.results;
             for (long c = c_first + 4 * part; c < c_last; c += 4 * parts) {
                 long at[4];
 #pragma unroll
-                for (int j = 0; j < 4; j++) at[j] = (complete && c + j < c_last) ? (long)w.xpos[c + j] : c + j;
+                for (int j = 0; j < 4; j++) at[j] = c + j < c_last ? (long)w.xpos[c + j] : -1;
                 float4 r[4];
 #pragma unroll
                 for (int j = 0; j < 4; j++)       // (at < 0: the crossing got no record because its walks cannot contribute)
@@ -1811,9 +1892,10 @@ inline hipError_t run_visibility(const int32_t* face_index_map, const Visibility
     return hipGetLastError();
 }
 
-// count -> crossing base per workgroup -> record slice per line -> records (geometry only: see struct EdgePlan)
+// the plan in one pass, or count -> crossing base per workgroup -> record slice per line -> records (geometry only: see
+// struct EdgePlan)
 struct EdgePlanLayout {
-    size_t off_line_count, off_line_cursor, off_alloc, off_extents, zero_bytes;     // the zeroed prefix
+    size_t off_line_cursor, off_alloc, off_extents, zero_bytes;     // the zeroed prefix
     size_t off_lane_cross, off_lane_block, off_line_slice, off_xrec;   // xrec | results follow, sized by capacity
     size_t fixed_bytes;
 };
@@ -1832,9 +1914,8 @@ inline EdgePlanLayout edge_plan_layout(int B, int F, int S) {
     const size_t nf = (size_t)B * F, nl = (size_t)B * 2 * S;
     EdgePlanLayout L;
     size_t o = 0;
-    L.off_line_count = o;  o += eg_align(nl * 4);
     L.off_line_cursor = o; o += eg_align(nl * 4);
-    L.off_alloc = o;       o += 256;
+    L.off_alloc = o;       o += eg_align((size_t)EG_ALLOC_INTS * 4);
     // room for the lines' non-zero-gradient extents (nz_lo_inv | nz_hi1, [B,2,S] ints each, 256-byte aligned) of a fused fit
     // objective: they must be zero before the pass that fills them, and a caller that builds the plan BEFORE that pass on the
     // same stream (d3m_edge_plan_extents_offset) gets them cleared by the plan's own clear instead of by a launch of its own
@@ -1853,6 +1934,34 @@ inline size_t edge_plan_bytes(int B, int F, int S) {
     return edge_plan_min_bytes(B, F, S) + eg_align(eg_default_crossings(B, F, S) * EG_BYTES_PER_CROSSING);
 }
 
+// The form of a plan of `cap` crossings (EdgePlan): the one-pass form's slice per line (> 0), or 0 for the counted form.
+// One-pass where the slices are comfortably larger than a line's crossings -- at least one per pixel of the line (the
+// default blob grants 1.5 per pixel at 512^2 and above; tools_dev/plan_stats.py) -- and a line that outgrows its slice
+// anyway spills to k_edge_overflow.  Counted beyond EG_WINDOW_MAX_S, for small blobs, and for
+// batches of few faces (their scatter pass deals a block's crossings to several workgroups, which cannot share one
+// base).  d3m_set_edge_plan_form (A/B runs and tests; D3M_EG_PLAN_FORM sets the initial value): 1 = always counted,
+// 2 = one-pass wherever it can run at all (any slice of at least one record).  The builder and the readers of a plan call
+// this with the same arguments.
+inline std::atomic<int> g_edge_plan_form{-1};       // -1: not yet read from the environment
+inline int edge_plan_form_forced() {
+    int f = g_edge_plan_form.load(std::memory_order_relaxed);
+    if (f < 0) {
+        f = d3m_env_int("D3M_EG_PLAN_FORM", 0);
+        f = (f == 1 || f == 2) ? f : 0;
+        int expected = -1;
+        if (!g_edge_plan_form.compare_exchange_strong(expected, f)) f = expected;
+    }
+    return f;
+}
+inline int edge_plan_form(int B, int F, int S, size_t cap) {
+    const long nf = (long)B * F, nl = (long)B * 2 * S;
+    const long blocks = (nf + EG_FACES_PER_BLOCK - 1) / EG_FACES_PER_BLOCK;
+    const long cap_line = (long)cap / nl;
+    const int forced = edge_plan_form_forced();
+    if (forced == 1 || S > EG_WINDOW_MAX_S || blocks < 2048 || cap_line < (forced == 2 ? 1 : S)) return 0;
+    return (int)cap_line;                                   // (cap <= 0x3FFFFF00)
+}
+
 // the plan as laid out in `blob` (flags / list / count come from a visibility blob)
 inline bool edge_plan_view(void* blob, size_t bytes, const VisibilityView& v, int B, int F, int S, EdgePlan& w) {
     const EdgePlanLayout L = edge_plan_layout(B, F, S);
@@ -1862,7 +1971,6 @@ inline bool edge_plan_view(void* blob, size_t bytes, const VisibilityView& v, in
     cap = cap > 64 ? cap - 32 : 0;                             // slack for the 256-byte alignments below
     if (cap > 0x3FFFFF00) cap = 0x3FFFFF00;                    // 2 * cap result slots are indexed with an int
     w.visible = v.flags; w.visible_list = v.list; w.n_visible = v.count;
-    w.line_count = (int*)(p + L.off_line_count);
     w.line_cursor = (int*)(p + L.off_line_cursor);
     w.alloc = (int*)(p + L.off_alloc);
     w.lane_cross = (int2*)(p + L.off_lane_cross);
@@ -1872,6 +1980,7 @@ inline bool edge_plan_view(void* blob, size_t bytes, const VisibilityView& v, in
     w.results = (float2*)(p + eg_align(L.off_xrec + cap * 16));
     w.xpos = (int*)(p + eg_align(eg_align(L.off_xrec + cap * 16) + cap * 16));
     w.cap = (int)cap;
+    w.cap_line = edge_plan_form(B, F, S, cap);
     return true;
 }
 
@@ -1886,20 +1995,25 @@ inline hipError_t run_edge_plan(FS fs, const int32_t* face_index_map, const Edge
     const long nf = (long)B * fs.num_faces(), nl = (long)B * 2 * S;
     const long g6_full = (nf + EG_FACES_PER_BLOCK - 1) / EG_FACES_PER_BLOCK;
     const dim3 g6((unsigned)(g6_full < 8192 ? (g6_full + 7) / 8 * 8 : 8192));      // a multiple of 8: see XcdOrder
+    const int parts = g6_full >= 2048 ? 1 : (int)std::min<long>(8, 2048 / std::max<long>(1, g6_full));
+    const dim3 g_scatter((unsigned)std::min<long>(8192, (g6_full * parts + 7) / 8 * 8));
+    if (w.cap_line) {                                       // one pass (edge_plan_form: parts == 1)
+        LAUNCH("k_edge_scatter", (k_edge_scatter<FS, true>), g_scatter, dim3(256), st, fs, face_index_map, S, w, 1);
+        return hipGetLastError();
+    }
     const bool window = S <= EG_WINDOW_MAX_S;               // the workgroups' lines fit LDS
     if (window) LAUNCH_SMEM("k_edge_count", k_edge_count_window<FS>, g6, dim3(256), (size_t)2 * (S + 1) * 4, st, fs, S, w);
     else LAUNCH("k_edge_count", k_edge_count<FS>, g6, dim3(256), st, fs, S, w);
     const int blocks_a = (int)((g6_full + 255) / 256);
     LAUNCH("k_alloc_plan", k_alloc_plan, dim3((unsigned)(blocks_a + (nl + 255) / 256)), dim3(256), st, w.lane_block,
-           (const int*)w.n_visible, EG_FACES_PER_BLOCK, w.alloc, blocks_a, (const int*)w.line_count, w.line_slice, w.alloc + 1, nl);
+           (const int*)w.n_visible, EG_FACES_PER_BLOCK, w.alloc + EG_ALLOC_TOTAL, blocks_a, w.line_cursor, w.line_slice,
+           w.alloc + EG_ALLOC_SLICES, nl);
     // (the scatter pass keeps the by-key form: with the ranks taken from LDS cursors it was slower, 0.173 vs 0.150 ms)
     // (few blocks of faces: their rounds dealt to several workgroups each -- see the kernel)
     // (round 6: the same dealing decided on the DEVICE from the number of listed faces -- a small batch of a fine mesh leaves
     //  most of this grid idle too -- bought nothing: 4 views of the headline mesh 31 -> 33 us with two parts, 38 with four;
     //  the pass is a chain of dependent look-ups per round, and more workgroups only repeat its set-up.  docs/EXPERIMENTS.md E)
-    const int parts = g6_full >= 2048 ? 1 : (int)std::min<long>(8, 2048 / std::max<long>(1, g6_full));
-    const dim3 g_scatter((unsigned)std::min<long>(8192, (g6_full * parts + 7) / 8 * 8));
-    LAUNCH("k_edge_scatter", k_edge_scatter<FS>, g_scatter, dim3(256), st, fs, face_index_map, S, w, parts);
+    LAUNCH("k_edge_scatter", (k_edge_scatter<FS, false>), g_scatter, dim3(256), st, fs, face_index_map, S, w, parts);
     return hipGetLastError();
 }
 
@@ -2025,7 +2139,7 @@ int run_edge_grad(FS fs, PixelMaps m, float* grad_faces, VertexTarget vt, const 
     // takes what that pass leaves
     if (!m.use_rgb && m.use_alpha && a.sparse_max > 0 && edge_lines_alpha_lds(S) <= 64 * 1024) {
         a.line_left = (int*)(p + L.off_line_left);
-        a.n_left = w.alloc + 2;
+        a.n_left = w.alloc + EG_ALLOC_LEFT;
         LAUNCH_SMEM("k_edge_lines_alpha", k_edge_lines_alpha, glines, dim3(EGA_THREADS), edge_lines_alpha_lds(S), st, a, w);
     }
     // (behind that pass k_edge_lines strides over its list of left lines with a small grid)

@@ -255,6 +255,13 @@ D3M_EXPORT int d3m_set_deterministic(int on) {
     return D3M_OK;
 }
 D3M_EXPORT int d3m_get_deterministic(void) { return deterministic_mode() ? 1 : 0; }
+D3M_EXPORT int d3m_set_edge_plan_form(int form) {
+    if (form < 0 || form > 2) return D3M_ERR_INVALID;
+    (void)edge_plan_form_forced();
+    g_edge_plan_form.store(form);
+    return D3M_OK;
+}
+D3M_EXPORT int d3m_get_edge_plan_form(void) { return edge_plan_form_forced(); }
 // Which form of coverage a launch takes (d3m_set_coverage_form: forced).  Sub-pixel triangles (more than two per three
 // raster pixels: BASELINE config 5) bid whatever the batch; big batches of ordinary meshes (more than BID_MAX_TILES blocks
 // of 8 x 8 pixels: the headline's 32 views) go through per-tile lists; small batches bid -- UNLESS the mesh is coarse (round

@@ -91,6 +91,13 @@ int d3m_get_coverage_form(void);
  * environment variable D3M_DETERMINISTIC=1 sets the initial value.  Returns D3M_ERR_INVALID for values other than 0 / 1. */
 int d3m_set_deterministic(int on);
 int d3m_get_deterministic(void);
+/* Which form of the edge plan (d3m_edge_plan, and the plan d3m_backward_pixel_map builds itself) a blob takes: 0 = by its
+ * size and the batch (the one-pass form where every line's fixed slice holds at least one crossing per pixel of the line,
+ * the counted form otherwise), 1 = always the counted form, 2 = the one-pass form wherever it can run at all.  Process-wide,
+ * read at every launch: a plan must be built and used under the same setting.  The environment variable
+ * D3M_EG_PLAN_FORM=0/1/2 sets the initial value.  Returns D3M_ERR_INVALID for any other value. */
+int d3m_set_edge_plan_form(int form);
+int d3m_get_edge_plan_form(void);
 /* The per-vertex sums of the deterministic mode (deep3dmap_amd/neural_renderer/rasterize.py, "DETERMINISTIC"): the adjoint
  * of vertices_to_faces + fill_back (NR/vertices_to_faces.py:16-22, NR/renderer.py:86) GATHERED per vertex in a fixed order
  * instead of scattered with float atomics.  adj_offsets [V+1], adj_items [3 F]: CSR adjacency of ONE index tensor tri [F,3]

@@ -1,4 +1,8 @@
-"""Statistics of the edge gradient's plan on the headline workload (GPU box): crossings per line, outward / inward walks."""
+"""Statistics of the edge gradient's plan (GPU box): crossings recorded per line against the one-pass form's fixed slice
+(cap_line), and the records' walks, for the headline and the other configurations' meshes.
+
+    python tools_dev/plan_stats.py            # every case below, one block each
+"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -6,47 +10,65 @@ from deep3dmap_amd import neural_renderer as nr, synthetic, _lib
 from deep3dmap_amd.neural_renderer import rasterize_ops as ops
 from deep3dmap_amd.neural_renderer.mesh_ops import gather_faces
 from deep3dmap_amd.neural_renderer.rasterize import _raster_forward
-B, S, n = 8, 512, 225
-v, tri = synthetic.grid_mesh(n)
-eyes = torch.from_numpy(synthetic.camera_ring(32)[:B]).cuda()
-vt = torch.from_numpy(v).cuda()[None].expand(B, -1, -1).contiguous()
-ft = torch.from_numpy(tri).cuda()[None].expand(B, -1, -1).contiguous()
-faces = gather_faces(nr.look_at(vt, eyes, _perspective_angle=30), ft, True)
-m, _ = _raster_forward(faces, None, S, 0.1, 100.0, 1e-3, None, False, True, True, False)
-F = faces.shape[1]
-vis = ops.visibility(m["face_index_map"], F)
-plan = ops.edge_plan(faces, m["face_index_map"], vis, S)
-torch.cuda.synchronize()
-nl = B * 2 * S
+
+CASES = [("headline: 32 views @512^2, 100 k triangles", 32, 512, 225),
+         ("config 4 shard: 8 views @512^2", 8, 512, 225),
+         ("config 4 shard: 4 views @512^2", 4, 512, 225),
+         ("config 5: 8 views @1024^2, 1 M triangles", 8, 1024, 709),
+         ("coarse mesh: 32 views @512^2, 722 triangles", 32, 512, 20)]
+
 al = lambda x: (x + 255) // 256 * 256
-raw = plan.cpu().numpy()
-line_count = raw[:nl * 4].view(np.int32)
-off_cursor = al(nl * 4)
-cursor = raw[off_cursor:off_cursor + nl * 4].view(np.int32)
-off_alloc = off_cursor + al(nl * 4)
-alloc = raw[off_alloc:off_alloc + 8].view(np.int32)
-nf = B * F
-off_lane_cross = off_alloc + 256
-off_lane_block = off_lane_cross + al(nf * 6 * 8)
-off_slice = off_lane_block + al((nf // 42 + 2) * 4)
-off_xrec = off_slice + al(nl * 8)
-total = int(alloc[0])
-print("crossings", total, "per view", total / B, "lines with crossings", int((cursor > 0).sum()), "of", nl)
-act = cursor[cursor > 0]
-print("crossings per active line: mean %.1f median %d p90 %d max %d" % (act.mean(), np.median(act), np.percentile(act, 90), act.max()))
-print("chunks of 256:", int(np.ceil(act / 256).sum()), " thread-slots used in set-up: %.2f" % (2 * act.sum() / (np.ceil(act / 256).sum() * 512)))
-slices = raw[off_slice:off_slice + nl * 8].view(np.int32).reshape(nl, 2)
-idx = np.concatenate([np.arange(c) + s0 for (s0, n0), c in zip(slices, cursor) if c > 0])
-print("records written %d of %d crossings (%.3f): the rest is outside the image or cannot contribute" % (len(idx), total, len(idx) / total))
-cap_bytes = len(raw) - off_xrec
-x = raw[off_xrec:off_xrec + (idx.max() + 1) * 32].view(np.uint32).reshape(-1, 8)[idx]
-bits = x[:, 3] & 0xFF
-d1_in = (x[:, 3] >> 8).astype(np.int64)
-alive, owner, oriented = (bits & 1) != 0, (bits & 16) != 0, (bits & 32) != 0
-in_from, in_to = (x[:, 4] & 0xFFFF).astype(np.int64), (x[:, 4] >> 16).astype(np.int64)
-print("of the records: outward walks (owner) %.3f  inward oriented %.3f" % ((alive & owner).mean(), (alive & oriented).mean()))
-il = (in_to - in_from + 1)[alive]
-print("inward length (unclipped): mean %.2f  <=6: %.3f  max %d" % (il.mean(), (il <= 6).mean(), il.max()))
-dirpos = (bits & 2) != 0
-ol = np.where(dirpos, S - 1 - d1_in, d1_in)[alive & owner]
-print("outward length to the border (unclipped): mean %.1f" % ol.mean())
+
+
+def stats(title, B, S, n):
+    v, tri = synthetic.grid_mesh(n)
+    eyes = torch.from_numpy(synthetic.camera_ring(32)[:B]).cuda()
+    vt = torch.from_numpy(v).cuda()[None].expand(B, -1, -1).contiguous()
+    ft = torch.from_numpy(tri).cuda()[None].expand(B, -1, -1).contiguous()
+    faces = gather_faces(nr.look_at(vt, eyes, _perspective_angle=30), ft, True)
+    m, _ = _raster_forward(faces, None, S, 0.1, 100.0, 1e-3, None, False, True, True, False)
+    F = faces.shape[1]
+    vis = ops.visibility(m["face_index_map"], F)
+    plan = ops.edge_plan(faces, m["face_index_map"], vis, S)
+    torch.cuda.synchronize()
+    raw = plan.cpu().numpy()
+    nl, nf = B * 2 * S, B * F
+    # layout (d3m_edge_grad.h, edge_plan_layout): line_cursor | alloc (256 B + 32 cursors 256 B apart) | extents (2 x) | lane_cross | lane_block |
+    # line_slice | xrec [cap] | results [2 cap] | xpos [cap]
+    cursor = raw[:nl * 4].view(np.int32)
+    off_alloc = al(nl * 4)
+    alloc = raw[off_alloc:off_alloc + 256 + 32 * 256].view(np.int32)
+    cursors = alloc[64::64][:32]                 # EG_ALLOC_CURSORS, EG_CURSOR_STRIDE, EG_PLAN_CURSORS
+    off_xrec = off_alloc + 256 + 32 * 256 + 2 * al(nl * 4) + al(nf * 6 * 8) + al((nf // 42 + 2) * 4) + al(nl * 8)
+    cap = (len(raw) - off_xrec - 512) // 36
+    cap = cap - 32 if cap > 64 else 0
+    one_pass = int(cursors.sum()) > 0
+    total = int(cursors.sum()) if one_pass else int(alloc[0])
+    cap_line = cap // nl if one_pass else 0
+    act = cursor[cursor > 0]
+    print("==", title)
+    print("  form %s  cap %d  cap_line %d (%.2f per pixel of a line)  crossings %d  records %d (%.3f)" %
+          ("one-pass" if one_pass else "counted", cap, cap_line, cap_line / S, total, int(cursor.sum()),
+           cursor.sum() / max(total, 1)))
+    print("  records per line: lines with any %d of %d; mean over all lines %.1f, over those %.1f; median %d p90 %d p99 %d max %d" %
+          (act.size, nl, cursor.mean(), act.mean(), np.median(act), np.percentile(act, 90), np.percentile(act, 99), act.max()))
+    if one_pass:
+        print("  lines over their slice: %d; spill flag %d, full flag %d; max / cap_line %.2f" %
+              (int((cursor > cap_line).sum()), int(alloc[3]), int(alloc[4]), act.max() / cap_line))
+        idx = np.concatenate([np.arange(min(c, cap_line)) + l * cap_line for l, c in enumerate(cursor) if c > 0])
+    else:
+        off_slice = off_xrec - al(nl * 8)
+        slices = raw[off_slice:off_slice + nl * 8].view(np.int32).reshape(nl, 2)
+        idx = np.concatenate([np.arange(c) + s0 for (s0, _), c in zip(slices, cursor) if c > 0])
+    x = raw[off_xrec:off_xrec + (int(idx.max()) + 1) * 16].view(np.uint32).reshape(-1, 4)[idx]
+    bits = x[:, 3] & 0x3F
+    alive, owner, oriented = (bits & 1) != 0, (bits & 16) != 0, (bits & 32) != 0
+    in_from, in_to = (x[:, 2] & 0xFFFF).astype(np.int64), (x[:, 2] >> 16).astype(np.int64)
+    print("  of the records: outward walks (owner) %.3f  inward oriented %.3f  inward length mean %.2f" %
+          ((alive & owner).mean(), (alive & oriented).mean(), (in_to - in_from + 1)[alive].mean()))
+
+
+if __name__ == "__main__":
+    for case in CASES:
+        stats(*case)
+        torch.cuda.empty_cache()
