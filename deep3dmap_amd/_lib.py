@@ -184,6 +184,9 @@ _SIGNATURES = {
     "d3m_mesh_get_correspondence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _SZ, _P]),
     "d3m_load_textures": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "d3m_create_texture_image": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
+    "d3m_textures_from_image": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "d3m_uv_texture_taps": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "d3m_uv_texture_adjoint": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _L, _I, _I, _P]),
 }
 
 _lib = None

@@ -2062,6 +2062,72 @@ D3M_EXPORT int d3m_load_textures(const float* image, const int32_t* is_update, c
     return check_launch();
 }
 
+D3M_EXPORT int d3m_textures_from_image(const float* image, int image_batch, const float* faces_uv, const int32_t* face_mask,
+                                       const float* base, int base_batch, float* textures, int num_faces, int texture_size,
+                                       int image_height, int image_width, int texture_wrapping, int use_bilinear,
+                                       d3m_stream_t stream) {
+    if (!image || !faces_uv || !textures) return D3M_ERR_INVALID;
+    if (image_batch <= 0 || image_batch > 65535 || num_faces <= 0 || texture_size < 2 || image_height <= 0 ||
+        image_width <= 0)
+        return D3M_ERR_INVALID;
+    if (texture_wrapping < 0 || texture_wrapping > 3) return D3M_ERR_INVALID;
+    if ((long)texture_size * texture_size * texture_size > 0x7FFFFFFF) return D3M_ERR_INVALID;
+    if (base && base_batch != 1 && base_batch != image_batch) return D3M_ERR_INVALID;
+    const long n = (long)num_faces * texture_size * texture_size * texture_size;
+    LAUNCH("k_textures_from_image", k_textures_from_image, dim3(blocks_for(n, 256), image_batch), dim3(256),
+           (hipStream_t)stream, image, face_mask, faces_uv, base, base_batch, textures, n, texture_size, image_height,
+           image_width, texture_wrapping, use_bilinear ? 1 : 0);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_uv_texture_taps(const float* faces_uv, const int32_t* face_mask, int num_faces, int texture_size,
+                                   int image_height, int image_width, int texture_wrapping, int use_bilinear,
+                                   int32_t* pixel, float* weight, d3m_stream_t stream) {
+    if (!faces_uv || !pixel || !weight) return D3M_ERR_INVALID;
+    if (num_faces <= 0 || texture_size < 2 || image_height <= 0 || image_width <= 0) return D3M_ERR_INVALID;
+    if (texture_wrapping < 0 || texture_wrapping > 3) return D3M_ERR_INVALID;
+    const long n = (long)num_faces * texture_size * texture_size * texture_size;
+    // entry, pixel and row indices are int32
+    if (n * (use_bilinear ? 4 : 1) > 0x7FFFFFFF || (long)image_height * image_width >= 0x7FFFFFFF) return D3M_ERR_INVALID;
+    LAUNCH("k_uv_texture_taps", k_uv_texture_taps, dim3(blocks_for(n, 256)), dim3(256), (hipStream_t)stream, faces_uv,
+           face_mask, n, texture_size, image_height, image_width, texture_wrapping, use_bilinear ? 1 : 0, pixel, weight);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_uv_texture_adjoint(const int32_t* row_ptr, const int32_t* entries, const int32_t* chunks, int num_chunks,
+                                      const int32_t* long_rows, const int32_t* long_chunk_ptr, int num_long_rows,
+                                      int long_row, int lanes_per_row, const float* grad_textures, float* partials,
+                                      float* grad_image, int batch_size, long num_texels, int image_height,
+                                      int image_width, d3m_stream_t stream) {
+    if (!row_ptr || !grad_textures || !grad_image) return D3M_ERR_INVALID;
+    if (batch_size <= 0 || batch_size > 65535 || num_texels <= 0 || image_height <= 0 || image_width <= 0 ||
+        long_row < 0 || num_chunks < 0 || num_long_rows < 0)
+        return D3M_ERR_INVALID;
+    if (lanes_per_row != 1 && lanes_per_row != 2 && lanes_per_row != 4 && lanes_per_row != 8 && lanes_per_row != 16)
+        return D3M_ERR_INVALID;
+    if ((long)image_height * image_width >= 0x7FFFFFFF) return D3M_ERR_INVALID;
+    if (num_long_rows > 0 && (!long_rows || !long_chunk_ptr || num_chunks == 0)) return D3M_ERR_INVALID;
+    if (num_chunks > 0 && (!chunks || !partials || !entries)) return D3M_ERR_INVALID;
+    const int n_pixels = image_height * image_width;
+    hipStream_t st = (hipStream_t)stream;
+    if (num_chunks > 0)
+        LAUNCH("k_uv_adjoint_chunks", k_uv_adjoint_chunks, dim3(num_chunks, batch_size), dim3(UV_ADJ_BLOCK), st,
+               (const int2*)entries, (const int2*)chunks, num_chunks, grad_textures, num_texels, partials);
+#define UV_ROWS(L)                                                                                                       \
+    LAUNCH("k_uv_adjoint_rows", k_uv_adjoint_rows<L>, dim3(blocks_for((long)n_pixels * L, 256), batch_size), dim3(256), st, \
+           row_ptr, (const int2*)entries, long_rows, long_chunk_ptr, num_long_rows, long_row, partials, num_chunks,       \
+           grad_textures, num_texels, grad_image, n_pixels)
+    switch (lanes_per_row) {
+        case 1: UV_ROWS(1); break;
+        case 2: UV_ROWS(2); break;
+        case 4: UV_ROWS(4); break;
+        case 8: UV_ROWS(8); break;
+        case 16: UV_ROWS(16); break;
+    }
+#undef UV_ROWS
+    return check_launch();
+}
+
 D3M_EXPORT int d3m_create_texture_image(const float* vertices_all, const float* textures, float* image, int num_faces,
                                         int texture_size_in, int image_height, int image_width, int tile_width,
                                         float eps, d3m_stream_t stream) {

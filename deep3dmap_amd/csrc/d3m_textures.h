@@ -20,6 +20,82 @@ __device__ __forceinline__ float wrap_uv(float v, int wrapping) {
     return v;
 }
 
+// Barycentric direction of texel r of a ts^3 cube (LTK:42-50); the reference divides in double and stores f32.
+// Texel 0 has direction (0,0,0): it is not normalised, so its position is (0,0) whatever the face -- pixel (0,0) with
+// weight 1, the one pixel that every face reads.
+__device__ __forceinline__ void texel_direction(int r, int ts, float& dim0, float& dim1, float& dim2) {
+    dim0 = (float)((r / (ts * ts)) / (ts - 1.));
+    dim1 = (float)(((r / ts) % ts) / (ts - 1.));
+    dim2 = (float)((r % ts) / (ts - 1.));
+    if (0 < dim0 + dim1 + dim2) {
+        const float sum = dim0 + dim1 + dim2;
+        dim0 /= sum; dim1 /= sum; dim2 /= sum;
+    }
+}
+
+// The image taps of texel r of the face whose uv corners are face_uv[6] (not yet wrapped): the map image -> cubes is
+// tex[k] = sum_j image[pix[j]][k] * w[j], accumulated in j order from 0 (bilinear: the four taps p00, p10, p01, p11 of
+// LTK; on the last row / column two of them are the same pixel).  Nearest: one tap of weight 1, read as a copy.  Returns
+// the number of taps; 0 under CLAMP_TO_BORDER (the reference writes zeros).  Pixel indices are y * W + x.
+struct TexelTaps {
+    long pix[4];
+    float w[4];
+};
+
+__device__ __forceinline__ int texel_taps(const float* __restrict__ face_uv, int r, int ts, int image_height,
+                                          int image_width, int wrapping, int use_bilinear, TexelTaps& t) {
+    if (wrapping == D3M_WRAP_CLAMP_TO_BORDER) return 0;        // LTK:97,109
+    float dim0, dim1, dim2;
+    texel_direction(r, ts, dim0, dim1, dim2);
+    float uv[6];
+#pragma unroll
+    for (int k = 0; k < 6; k++) uv[k] = wrap_uv(face_uv[k], wrapping);
+    const float pos_x = (uv[0] * dim0 + uv[2] * dim1 + uv[4] * dim2) * (float)(image_width - 1);
+    const float pos_y = (uv[1] * dim0 + uv[3] * dim1 + uv[5] * dim2) * (float)(image_height - 1);
+    if (use_bilinear) {
+        const int xi = (int)pos_x, yi = (int)pos_y;
+        const float wx1 = pos_x - (float)xi, wx0 = 1 - wx1, wy1 = pos_y - (float)yi, wy0 = 1 - wy1;
+        // (int)(pos_y + 1), not yi + 1: the f32 sum can round up to the next integer (LTK)
+        const int y1 = min((int)(pos_y + 1), image_height - 1), x1 = min(xi + 1, image_width - 1);
+        t.pix[0] = (long)yi * image_width + xi; t.w[0] = wx0 * wy0;
+        t.pix[1] = (long)y1 * image_width + xi; t.w[1] = wx0 * wy1;
+        t.pix[2] = (long)yi * image_width + x1; t.w[2] = wx1 * wy0;
+        t.pix[3] = (long)y1 * image_width + x1; t.w[3] = wx1 * wy1;
+        return 4;
+    }
+    t.pix[0] = (long)(int)roundf(pos_y) * image_width + (int)roundf(pos_x);
+    t.w[0] = 1.0f;
+    return 1;
+}
+
+// One texel: tex[0..2] from image [H, W, 3] (the arithmetic of LTK, shared by every kernel that samples a uv image).
+__device__ __forceinline__ void load_texel(const float* __restrict__ image, const float* __restrict__ face_uv, int r,
+                                           int ts, int image_height, int image_width, int wrapping, int use_bilinear,
+                                           float* __restrict__ tex) {
+    TexelTaps t;
+    const int n = texel_taps(face_uv, r, ts, image_height, image_width, wrapping, use_bilinear, t);
+    if (n == 0) {
+        tex[0] = 0; tex[1] = 0; tex[2] = 0;
+    } else if (n == 4) {
+        const float* p00 = image + t.pix[0] * 3;
+        const float* p10 = image + t.pix[1] * 3;
+        const float* p01 = image + t.pix[2] * 3;
+        const float* p11 = image + t.pix[3] * 3;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            float c = 0;
+            c += p00[k] * t.w[0];
+            c += p10[k] * t.w[1];
+            c += p01[k] * t.w[2];
+            c += p11[k] * t.w[3];
+            tex[k] = c;
+        }
+    } else {
+        const float* p = image + t.pix[0] * 3;
+        tex[0] = p[0]; tex[1] = p[1]; tex[2] = p[2];
+    }
+}
+
 // One lane per texel of textures [F, ts, ts, ts, 3]; faces with is_update == 0 are left untouched.
 __global__ void __launch_bounds__(256) k_load_textures(const float* __restrict__ image,
                                                        const int32_t* __restrict__ is_update,
@@ -32,45 +108,155 @@ __global__ void __launch_bounds__(256) k_load_textures(const float* __restrict__
     const int fn = (int)(i / ts3);
     if (is_update[fn] == 0) return;
     const int r = (int)(i - (long)fn * ts3);
-    // barycentric direction of this texel (LTK:42-50); the reference divides in double and stores f32
-    float dim0 = (float)((r / (ts * ts)) / (ts - 1.));
-    float dim1 = (float)(((r / ts) % ts) / (ts - 1.));
-    float dim2 = (float)((r % ts) / (ts - 1.));
-    if (0 < dim0 + dim1 + dim2) {
-        const float sum = dim0 + dim1 + dim2;
-        dim0 /= sum; dim1 /= sum; dim2 /= sum;
-    }
-    float* tex = textures + i * 3;
-    if (wrapping == D3M_WRAP_CLAMP_TO_BORDER) {                 // LTK:97,109: the reference writes zeros
-        tex[0] = 0; tex[1] = 0; tex[2] = 0;
+    load_texel(image, faces + (long)fn * 6, r, ts, image_height, image_width, wrapping, use_bilinear, textures + i * 3);
+}
+
+// ---- learnable uv images: image [B, H, W, 3] -> cubes [B, F, ts, ts, ts, 3] and its adjoint ----------------------------
+// One lane per texel of every view into a FRESH output: faces with mask[f] == 0 (mask NULL: none) copy base (batch 1 or B;
+// NULL: zeros), the others are load_texel of view b's image -- bit for bit what k_load_textures writes.
+__global__ void __launch_bounds__(256) k_textures_from_image(const float* __restrict__ image,
+                                                             const int32_t* __restrict__ mask,
+                                                             const float* __restrict__ faces_uv,
+                                                             const float* __restrict__ base, int base_batch,
+                                                             float* __restrict__ textures, long n_texels, int ts,
+                                                             int image_height, int image_width, int wrapping,
+                                                             int use_bilinear) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int b = blockIdx.y;
+    if (i >= n_texels) return;
+    const int ts3 = ts * ts * ts;
+    const int fn = (int)(i / ts3);
+    float* tex = textures + ((long)b * n_texels + i) * 3;
+    if (mask && mask[fn] == 0) {
+        if (base) {
+            const float* src = base + ((base_batch > 1 ? (long)b * n_texels : 0) + i) * 3;
+            tex[0] = src[0]; tex[1] = src[1]; tex[2] = src[2];
+        } else {
+            tex[0] = 0; tex[1] = 0; tex[2] = 0;
+        }
         return;
     }
-    float uv[6];
+    const int r = (int)(i - (long)fn * ts3);
+    load_texel(image + (long)b * image_height * image_width * 3, faces_uv + (long)fn * 6, r, ts, image_height,
+               image_width, wrapping, use_bilinear, tex);
+}
+
+// The transpose's entries before sorting: one lane per texel i writes its `taps` (4 bilinear, 1 nearest) entries
+// e = i * taps + j as (pixel[e], weight[e]).  Entries that add nothing -- zero weight, a face outside the mask,
+// CLAMP_TO_BORDER -- get pixel = H * W (past every row) and weight 0.  A stable sort by pixel then gives each pixel's
+// entries in ascending (texel, tap) order.
+__global__ void __launch_bounds__(256) k_uv_texture_taps(const float* __restrict__ faces_uv,
+                                                         const int32_t* __restrict__ mask, long n_texels, int ts,
+                                                         int image_height, int image_width, int wrapping,
+                                                         int use_bilinear, int32_t* __restrict__ pixel,
+                                                         float* __restrict__ weight) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_texels) return;
+    const int ts3 = ts * ts * ts;
+    const int fn = (int)(i / ts3);
+    const int taps = use_bilinear ? 4 : 1;
+    const int none = image_height * image_width;
+    TexelTaps t;
+    int n = 0;
+    if (!mask || mask[fn] != 0)
+        n = texel_taps(faces_uv + (long)fn * 6, (int)(i - (long)fn * ts3), ts, image_height, image_width, wrapping,
+                       use_bilinear, t);
 #pragma unroll
-    for (int k = 0; k < 6; k++) uv[k] = wrap_uv(faces[(long)fn * 6 + k], wrapping);
-    const float pos_x = (uv[0] * dim0 + uv[2] * dim1 + uv[4] * dim2) * (float)(image_width - 1);
-    const float pos_y = (uv[1] * dim0 + uv[3] * dim1 + uv[5] * dim2) * (float)(image_height - 1);
-    if (use_bilinear) {
-        const int xi = (int)pos_x, yi = (int)pos_y;
-        const float wx1 = pos_x - (float)xi, wx0 = 1 - wx1, wy1 = pos_y - (float)yi, wy0 = 1 - wy1;
-        const int y1 = min((int)(pos_y + 1), image_height - 1), x1 = min(xi + 1, image_width - 1);
-        const float* p00 = image + ((long)yi * image_width + xi) * 3;
-        const float* p10 = image + ((long)y1 * image_width + xi) * 3;
-        const float* p01 = image + ((long)yi * image_width + x1) * 3;
-        const float* p11 = image + ((long)y1 * image_width + x1) * 3;
+    for (int j = 0; j < 4; j++) {
+        if (j >= taps) break;
+        const bool keep = j < n && t.w[j] != 0.0f;
+        pixel[i * taps + j] = keep ? (int32_t)t.pix[j] : none;
+        weight[i * taps + j] = keep ? t.w[j] : 0.0f;
+    }
+}
+
+// The adjoint as a gather over the transpose (CSR, one row per pixel: row_ptr [H*W+1], entries [nnz] of (texel, weight
+// bits) in ascending texel order): grad_image[b, p, k] = sum over the row of w * grad_textures[b, texel, k], in row order.
+// Rows longer than long_row entries (pixel (0,0) gets one per face) are cut into chunks [start, end) of the entry array;
+// k_uv_adjoint_chunks reduces each chunk in a fixed order into partials [B, n_chunks, 3], and k_uv_adjoint_rows adds a
+// long row's chunk sums in chunk order.  No float atomics: the result is the same bits on every run.
+constexpr int UV_ADJ_BLOCK = 256;
+
+__global__ void __launch_bounds__(UV_ADJ_BLOCK) k_uv_adjoint_chunks(const int2* __restrict__ entries,
+                                                                    const int2* __restrict__ chunks, int n_chunks,
+                                                                    const float* __restrict__ grad_textures,
+                                                                    long n_texels, float* __restrict__ partials) {
+    const int c = blockIdx.x, b = blockIdx.y;
+    const int2 range = chunks[c];
+    const float* g = grad_textures + (long)b * n_texels * 3;
+    float acc[3] = {0, 0, 0};
+    for (int e = range.x + (int)threadIdx.x; e < range.y; e += UV_ADJ_BLOCK) {
+        const int2 en = entries[e];
+        const float w = __int_as_float(en.y);
+        const float* gt = g + (long)en.x * 3;
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float c = 0;
-            c += p00[k] * (wx0 * wy0);
-            c += p10[k] * (wx0 * wy1);
-            c += p01[k] * (wx1 * wy0);
-            c += p11[k] * (wx1 * wy1);
-            tex[k] = c;
+        for (int k = 0; k < 3; k++) acc[k] += w * gt[k];
+    }
+    // fixed-order reduction: a butterfly inside each wave, then the waves' sums in wave order
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+        for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+    __shared__ float wave_sum[UV_ADJ_BLOCK / 64][3];
+    const int wave = threadIdx.x / 64;
+    if ((threadIdx.x & 63) == 0) {
+        wave_sum[wave][0] = acc[0]; wave_sum[wave][1] = acc[1]; wave_sum[wave][2] = acc[2];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        float s = 0;
+#pragma unroll
+        for (int w = 0; w < UV_ADJ_BLOCK / 64; w++) s += wave_sum[w][threadIdx.x];
+        partials[((long)b * n_chunks + c) * 3 + threadIdx.x] = s;
+    }
+}
+
+// LPR lanes per row (a power of two up to 64, chosen from the layout's mean row length): lane `sub` of a row sums its
+// entries sub, sub + LPR, ... in order, then a butterfly over the row's lanes -- the order is fixed for a given LPR.
+template <int LPR>
+__global__ void __launch_bounds__(256) k_uv_adjoint_rows(const int32_t* __restrict__ row_ptr,
+                                                         const int2* __restrict__ entries,
+                                                         const int32_t* __restrict__ long_rows,
+                                                         const int32_t* __restrict__ long_chunk_ptr, int n_long,
+                                                         int long_row, const float* __restrict__ partials,
+                                                         int n_chunks, const float* __restrict__ grad_textures,
+                                                         long n_texels, float* __restrict__ grad_image, int n_pixels) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const int sub = (int)(t % LPR);
+    const int p = (int)min(t / LPR, (long)n_pixels);          // (lanes past the last row walk an empty row: no early exit
+    const int b = blockIdx.y;                                  //  before the shuffles)
+    const bool valid = p < n_pixels;
+    const int start = valid ? row_ptr[p] : 0, end = valid ? row_ptr[p + 1] : 0;
+    float acc[3] = {0, 0, 0};
+    if (end - start > long_row && n_long > 0) {
+        if (sub == 0) {
+            int lo = 0, hi = n_long - 1;                       // long_rows is ascending and holds p
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (long_rows[mid] < p) lo = mid + 1; else hi = mid;
+            }
+            const float* part = partials + (long)b * n_chunks * 3;
+            for (int c = long_chunk_ptr[lo]; c < long_chunk_ptr[lo + 1]; c++) {
+#pragma unroll
+                for (int k = 0; k < 3; k++) acc[k] += part[(long)c * 3 + k];
+            }
         }
     } else {
-        const int xi = (int)roundf(pos_x), yi = (int)roundf(pos_y);
-        const float* p = image + ((long)yi * image_width + xi) * 3;
-        tex[0] = p[0]; tex[1] = p[1]; tex[2] = p[2];
+        const float* g = grad_textures + (long)b * n_texels * 3;
+        for (int e = start + sub; e < end; e += LPR) {
+            const int2 en = entries[e];
+            const float w = __int_as_float(en.y);
+            const float* gt = g + (long)en.x * 3;
+#pragma unroll
+            for (int k = 0; k < 3; k++) acc[k] += w * gt[k];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+#pragma unroll
+        for (int off = LPR / 2; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+    if (valid && sub == 0) {
+        float* out = grad_image + ((long)b * n_pixels + p) * 3;
+        out[0] = acc[0]; out[1] = acc[1]; out[2] = acc[2];
     }
 }
 

@@ -6,6 +6,7 @@ from .obj_io import Mesh, load_obj, save_obj
 from .rasterize import (Rasterize, RasterizeFunction, rasterize, rasterize_depth, rasterize_rgbad,
                         rasterize_silhouettes)
 from .renderer import Renderer
+from .uv_textures import UVTextures, textures_from_image
 
 __version__ = '1.1.3'
 name = 'neural_renderer_pytorch'

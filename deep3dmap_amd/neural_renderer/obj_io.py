@@ -133,7 +133,10 @@ def load_textures_from_image(image, faces, textures, is_update, texture_wrapping
     return textures
 
 
-def _textures_of_scene(scene, obj_dir, filename_mtl, texture_size, texture_wrapping, use_bilinear):
+def _scene_layers(scene, obj_dir, filename_mtl, texture_size):
+    """What the textures of a scene are made of: (faces_uv [F,3,2], base [F,ts,ts,ts,3] -- 0.5 grey, then the Kd colour of
+    each material over its faces -- and [(material, image [H,W,3], faces [F] int32 0/1)] for every map_Kd, in .mtl order).
+    load_textures samples the images onto the base in that order; UVTextures (uv_textures.py) keeps them learnable."""
     dev = _device()
     F = scene.tri_tex.shape[0]
     # a corner without a texture coordinate indexes "vt 0" in the reference (one-based 0 -> -1 -> the LAST coordinate)
@@ -147,11 +150,19 @@ def _textures_of_scene(scene, obj_dir, filename_mtl, texture_size, texture_wrapp
         if m['Kd'] is not None:
             sel = torch.from_numpy(tri_name == name).to(dev)
             textures[sel] = torch.as_tensor(m['Kd'], dtype=torch.float32, device=dev)
+    images = []
     for name, m in mats.items():                          # ... then every image over the faces of its material
         if m['map_Kd'] is not None:
             image = torch.from_numpy(_read_image(os.path.join(obj_dir, m['map_Kd']))).to(dev)
             update = torch.from_numpy((tri_name == name).astype(np.int32)).to(dev)
-            load_textures_from_image(image, face_uv, textures, update, texture_wrapping_dict[texture_wrapping], use_bilinear)
+            images.append((name, image, update))
+    return face_uv, textures, images
+
+
+def _textures_of_scene(scene, obj_dir, filename_mtl, texture_size, texture_wrapping, use_bilinear):
+    face_uv, textures, images = _scene_layers(scene, obj_dir, filename_mtl, texture_size)
+    for _, image, update in images:
+        load_textures_from_image(image, face_uv, textures, update, texture_wrapping_dict[texture_wrapping], use_bilinear)
     return textures
 
 

@@ -794,6 +794,37 @@ int d3m_warp_resample_backward(const float* depth, const float* inv_K, int inv_K
 int d3m_load_textures(const float* image, const int32_t* is_update, const float* faces_uv, float* textures,
                       int num_faces, int texture_size, int image_height, int image_width, int texture_wrapping,
                       int use_bilinear, d3m_stream_t stream);
+/* Learnable uv images: the map image -> cubes of d3m_load_textures as a function of the image, and its adjoint.
+ * image [image_batch, H, W, 3] (row 0 = bottom, texture space), faces_uv [F, 3, 2], face_mask [F] i32 (NULL: every
+ * face), base [base_batch, F, ts, ts, ts, 3] (base_batch 1 or image_batch; NULL: zeros).  WRITES textures
+ * [image_batch, F, ts, ts, ts, 3]: the faces with face_mask != 0 sample view b's image with the arithmetic of
+ * d3m_load_textures (the same bits), the others copy base.  D3M_ERR_INVALID: NULL image / faces_uv / textures, a size
+ * <= 0, texture_size < 2, image_batch > 65535, texture_wrapping outside 0..3, base_batch neither 1 nor image_batch. */
+int d3m_textures_from_image(const float* image, int image_batch, const float* faces_uv, const int32_t* face_mask,
+                            const float* base, int base_batch, float* textures, int num_faces, int texture_size,
+                            int image_height, int image_width, int texture_wrapping, int use_bilinear, d3m_stream_t stream);
+/* The device part of the transpose's build: texel i = f * ts^3 + r writes its taps (4 bilinear, 1 nearest) as entries
+ * e = i * taps + j: pixel [F*ts^3*taps] i32 = y * W + x, weight [F*ts^3*taps] f32 -- texture[i][k] = sum over j of
+ * image[pixel][k] * weight, accumulated in j order.  Entries that add nothing (zero weight, face_mask[f] == 0,
+ * CLAMP_TO_BORDER) get pixel = H * W and weight 0.  A stable sort by pixel gives the CSR d3m_uv_texture_adjoint walks.
+ * D3M_ERR_INVALID: NULL faces_uv / pixel / weight, a size <= 0, texture_size < 2, texture_wrapping outside 0..3,
+ * F*ts^3*taps or H*W beyond int32. */
+int d3m_uv_texture_taps(const float* faces_uv, const int32_t* face_mask, int num_faces, int texture_size, int image_height,
+                        int image_width, int texture_wrapping, int use_bilinear, int32_t* pixel, float* weight,
+                        d3m_stream_t stream);
+/* The adjoint (no float atomics, the same bits on every run): WRITES grad_image [batch_size, H, W, 3] from grad_textures
+ * [batch_size, num_texels, 3] through the transpose row_ptr [H*W+1] i32, entries [nnz, 2] i32 (texel, weight's f32
+ * bits), each row in ascending texel order.  Rows of more than long_row entries are listed in long_rows [num_long_rows]
+ * (ascending); the chunks of long row l are chunks[long_chunk_ptr[l] .. long_chunk_ptr[l+1]), each an entry range
+ * [start, end) i32x2, reduced in a fixed order into partials [batch_size, num_chunks, 3] f32 (scratch) and added in chunk
+ * order.  The other rows are walked by lanes_per_row (1, 2, 4, 8 or 16) lanes each: lane s sums entries s, s +
+ * lanes_per_row, ... and the lanes' sums are combined by a butterfly -- a fixed order for a given lanes_per_row.
+ * D3M_ERR_INVALID: NULL row_ptr / grad_textures / grad_image, a size <= 0, batch_size > 65535, long_row < 0,
+ * lanes_per_row not a listed value, long rows without chunks, chunks without entries or partials. */
+int d3m_uv_texture_adjoint(const int32_t* row_ptr, const int32_t* entries, const int32_t* chunks, int num_chunks,
+                           const int32_t* long_rows, const int32_t* long_chunk_ptr, int num_long_rows, int long_row,
+                           int lanes_per_row, const float* grad_textures, float* partials, float* grad_image,
+                           int batch_size, long num_texels, int image_height, int image_width, d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
