@@ -187,6 +187,8 @@ _SIGNATURES = {
     "d3m_textures_from_image": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "d3m_uv_texture_taps": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "d3m_uv_texture_adjoint": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _L, _I, _I, _P]),
+    "d3m_vertex_color_textures": (_I, [_P, _I, _P, _P, _I, _I, _P]),
+    "d3m_vertex_color_textures_backward": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -9,6 +9,7 @@
 #include "d3m_launch.h"
 #include "d3m_aux.h"
 #include "d3m_textures.h"
+#include "d3m_vertex_colors.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -2125,6 +2126,39 @@ D3M_EXPORT int d3m_uv_texture_adjoint(const int32_t* row_ptr, const int32_t* ent
         case 16: UV_ROWS(16); break;
     }
 #undef UV_ROWS
+    return check_launch();
+}
+
+// Learnable per-vertex colours (d3m_vertex_colors.h): colours -> 2x2x2 cubes of an indexed mesh, and the fixed-order adjoint.
+D3M_EXPORT int d3m_vertex_color_textures(const float* colors, int color_batch, const int32_t* tri, float* textures,
+                                         int num_vertices, int num_tri, d3m_stream_t stream) {
+    if (!colors || !tri || !textures) return D3M_ERR_INVALID;
+    if (color_batch <= 0 || color_batch > 65535 || num_vertices <= 0 || num_tri <= 0) return D3M_ERR_INVALID;
+    const long n = (long)num_tri * 8;
+    LAUNCH("k_vertex_color_textures", k_vertex_color_textures, dim3(blocks_for(n, 256), color_batch), dim3(256),
+           (hipStream_t)stream, colors, tri, textures, num_vertices, n);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_vertex_color_textures_backward(const float* grad_textures, const int32_t* adj_offsets,
+                                                  const int32_t* adj_items, const int32_t* chunks, int num_chunks,
+                                                  const int32_t* long_rows, const int32_t* long_chunk_ptr,
+                                                  int num_long_rows, int long_row, float* partials, float* grad_colors,
+                                                  int batch_size, int num_vertices, int num_tri, d3m_stream_t stream) {
+    if (!grad_textures || !adj_offsets || !adj_items || !grad_colors) return D3M_ERR_INVALID;
+    if (batch_size <= 0 || batch_size > 65535 || num_vertices <= 0 || num_tri <= 0 || long_row < 0 || num_chunks < 0 ||
+        num_long_rows < 0)
+        return D3M_ERR_INVALID;
+    if ((long)num_tri * 3 > 0x7FFFFFFF) return D3M_ERR_INVALID;        // items are int32
+    if (num_long_rows > 0 && (!long_rows || !long_chunk_ptr || num_chunks == 0)) return D3M_ERR_INVALID;
+    if (num_chunks > 0 && (!chunks || !partials)) return D3M_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (num_chunks > 0)
+        LAUNCH("k_vertex_color_adjoint_chunks", k_vertex_color_adjoint_chunks, dim3(num_chunks, batch_size),
+               dim3(VC_ADJ_BLOCK), st, adj_items, (const int2*)chunks, num_chunks, grad_textures, (long)num_tri, partials);
+    LAUNCH("k_vertex_color_adjoint_rows", k_vertex_color_adjoint_rows, dim3(blocks_for((long)num_vertices * 3, 256), batch_size),
+           dim3(256), st, adj_offsets, adj_items, long_rows, long_chunk_ptr, num_long_rows, long_row, partials, num_chunks,
+           grad_textures, (long)num_tri, grad_colors, num_vertices);
     return check_launch();
 }
 

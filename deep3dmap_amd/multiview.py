@@ -101,18 +101,37 @@ class MultiViewFit:
     returns their gradient.  No other rank renders these views, so that gradient is exact on this rank and is not
     exchanged; it is written inside the (captured) step into a persistent buffer, and in-place updates of `eyes` between
     replays are read at replay.
+
+    vertex_colors [V,3] instead of textures (pass textures=None): the texture parameter is one colour per vertex; the
+    step computes the cubes from the colours (nr.textures_from_vertex_colors) and reduces this rank's cube gradient to
+    [V,3] with the fixed-order adjoint BEFORE the exchange, so the flat buffer is [loss | 3V | 3V] instead of
+    [loss | 3V | 24F] and step() returns grad_colors [V,3] in the textures' place.
     """
 
     def __init__(self, vertices, triangles, textures, eyes, image_size=512, anti_aliasing=False, rank=0,
                  world_size=1, optimise_textures=True, device="cuda", objective_in_renderer=True, view_groups=1,
-                 split_exchange=None, loss_form="linked", optimise_cameras=False):
+                 split_exchange=None, loss_form="linked", optimise_cameras=False, vertex_colors=None):
         self.device = torch.device(device)
+        if (vertex_colors is None) == (textures is None):
+            raise ValueError("MultiViewFit: give either textures or vertex_colors (the other one None)")
         self.rank, self.world_size = rank, world_size
         lo, hi = shard_views(len(eyes), rank, world_size)
         self.n_local = hi - lo
         self.vertices = torch.as_tensor(vertices, dtype=torch.float32).to(self.device).requires_grad_(True)
         self.triangles = torch.as_tensor(triangles, dtype=torch.int32).to(self.device)
-        self.textures = torch.as_tensor(textures, dtype=torch.float32).to(self.device).requires_grad_(optimise_textures)
+        self.textures = self.colors = self._color_adjacency = None
+        if vertex_colors is None:
+            self.textures = torch.as_tensor(textures, dtype=torch.float32).to(self.device).requires_grad_(optimise_textures)
+        else:
+            # (the split exchange was built to hide the cube gradient's all-reduce, and that part is gone)
+            if split_exchange:
+                raise ValueError("MultiViewFit: vertex_colors needs split_exchange=False (or None)")
+            split_exchange = False
+            self.colors = torch.as_tensor(vertex_colors, dtype=torch.float32).to(self.device).contiguous()
+            if tuple(self.colors.shape) != tuple(self.vertices.shape):
+                raise ValueError(f"vertex_colors must be {list(self.vertices.shape)}")
+            self.colors.requires_grad_(optimise_textures)
+            self._color_adjacency = nr.vertex_colors.AdjacencyCache(1)      # the fit holds its faces' adjacency itself
         self.eyes = torch.as_tensor(eyes, dtype=torch.float32)[lo:hi].to(self.device).contiguous()
         self.optimise_cameras = bool(optimise_cameras)
         self._grad_eyes = None
@@ -147,13 +166,14 @@ class MultiViewFit:
         self.mask_sum = None            # [1] device scalar: sum of the mask over ALL ranks' views
         self._mask_sum_local = None
         # the step's results, packed where they are produced (inside the captured step): [loss | grad_v | grad_t]
-        n_t = self.textures.numel() if optimise_textures else 0
+        n_t = self.texture_parameter.numel() if optimise_textures else 0
         self._flat = torch.zeros(1 + self.vertices.numel() + n_t, dtype=torch.float32, device=self.device)
         # ... by the rendering node itself where it can: the node's backward writes the two gradients, its forward the loss,
         # straight into these views of the flat buffer (render_fit_loss(grad_sink=...)); _forward_backward packs only what did not
         nv = self.vertices.numel()
         self._sink = (self._flat[1:1 + nv].view(1, *self.vertices.shape),
-                      self._flat[1 + nv:].view(1, *self.textures.shape) if n_t else None, self._flat[0:1])
+                      self._flat[1 + nv:].view(1, *self.textures.shape) if n_t and self.colors is None else None,
+                      self._flat[0:1])
         self._use_sink = False          # only the step's own forward + backward hands the buffers to the node (per call)
         # eager or replayed, always on one stream.  (Through a weak reference: a bound method would make fit -> runner ->
         # fit a cycle, and a fit with its captured graph, memory pool and streams should die with its last reference, not
@@ -191,9 +211,20 @@ class MultiViewFit:
         else:
             self._runner = CapturedStep(lambda: me()._forward_backward())
 
+    @property
+    def texture_parameter(self):
+        """What optimise_textures optimises: the cubes [F,ts,ts,ts,3], or the vertex colours [V,3]."""
+        return self.textures if self.colors is None else self.colors
+
+    def _cubes(self):
+        """The texture cubes [1,F,ts,ts,ts,3] the render nodes take."""
+        if self.colors is None:
+            return self.textures[None]
+        return nr.textures_from_vertex_colors(self.colors, self.triangles, cache=self._color_adjacency)
+
     def render(self, vertices=None, textures=None):
         v = self.vertices if vertices is None else vertices
-        t = self.textures if textures is None else textures
+        t = self._cubes() if textures is None else textures[None]
         # the drop-in form (render, then the objective on the images): the objective is REGISTERED with the renderer, whose
         # pass then leaves value and walk records behind for multiview_fit_loss to find (Renderer.fit_targets)
         self.renderer.fit_targets = None
@@ -201,7 +232,7 @@ class MultiViewFit:
             rgb_t, depth_t, alpha_t = self.targets
             self.renderer.fit_targets = (rgb_t, depth_t, alpha_t, alpha_t, self.mask_sum)
         # one mesh, one texture set, n_local cameras (renderer.eye is [n_local, 3]): batch-1 inputs are shared
-        return self.renderer(v[None], self.triangles[None], t[None])
+        return self.renderer(v[None], self.triangles[None], t)
 
     @torch.no_grad()
     def set_targets_from(self, target_vertices):
@@ -239,15 +270,16 @@ class MultiViewFit:
             rgb_t, depth_t, alpha_t = self.targets
             if self.keep_images and self.images is None:        # persistent buffers (a captured step writes in place)
                 self.images = tuple(torch.empty_like(t) for t in (rgb_t, depth_t, alpha_t))
-            return r.render_fit_loss(self.vertices[None], self.triangles[None], self.textures[None],
+            return r.render_fit_loss(self.vertices[None], self.triangles[None], self._cubes(),
                                      (rgb_t, depth_t, alpha_t, alpha_t, self.mask_sum),
                                      images_out=self.images if self.keep_images else None,
                                      grad_sink=self._sink if self._use_sink else None)
         return self.loss(*self.render())
 
     def _forward_backward(self):
+        tex = self.texture_parameter
         self.vertices.grad = None
-        self.textures.grad = None
+        tex.grad = None
         self.eyes.grad = None
         # backward runs right behind forward, on the same stream and inside the same capture: only HERE may the forward
         # leave its side branch (visibility list, edge plan, the loss's last reduction step) open for backward to join.
@@ -263,10 +295,11 @@ class MultiViewFit:
             self.renderer.defer_plan_join = False
             self._use_sink = False
         # [loss | grad_v | grad_t] in the persistent buffer the collective runs on: already there when the rendering node
-        # produced them in place (grad_sink); packed here (part of the captured step) otherwise
+        # produced them in place (grad_sink); packed here (part of the captured step) otherwise -- as the colour gradient
+        # is: the cubes' gradient stays on this rank, its adjoint's [V,3] goes into the buffer
         parts = [loss.detach().reshape(1), self.vertices.grad.reshape(-1)]
-        if self.textures.requires_grad:
-            parts.append(self.textures.grad.reshape(-1))
+        if tex.requires_grad:
+            parts.append(tex.grad.reshape(-1))
         at = 0
         for part in parts:
             dst = self._flat[at:at + part.numel()]
@@ -311,7 +344,7 @@ class MultiViewFit:
         """Capture forward + loss + backward of one step into a HIP graph (see deep3dmap_amd/graph.py).
         Vertices / textures / targets are updated IN PLACE between replays."""
         self.vertices.grad = None
-        self.textures.grad = None
+        self.texture_parameter.grad = None
         self.eyes.grad = None
         self._runner.capture(warmup)
         if self.split_exchange:
@@ -338,7 +371,8 @@ class MultiViewFit:
 
     def step(self):
         """forward + loss + backward + all-reduce.  Returns (loss, grad_vertices, grad_textures) of the WHOLE objective
-        (all ranks' cameras) as views of the persistent flat buffer, valid until the next step; with optimise_cameras also
+        (all ranks' cameras) as views of the persistent flat buffer, valid until the next step -- with vertex_colors the
+        third is grad_colors [V,3]; with optimise_cameras also
         grad_eyes [n_local,3], the objective's gradient with respect to this rank's eyes (a persistent buffer as well)."""
         nv = self.vertices.numel()
         if self.split_exchange:
@@ -350,7 +384,8 @@ class MultiViewFit:
         else:
             flat = allreduce_sum_(self._runner())
         gv = flat[1:1 + nv].view_as(self.vertices)
-        gt = flat[1 + nv:].view_as(self.textures) if self.textures.requires_grad else None
+        tex = self.texture_parameter
+        gt = flat[1 + nv:].view_as(tex) if tex.requires_grad else None
         if self.optimise_cameras:
             return flat[0], gv, gt, self._grad_eyes
         return flat[0], gv, gt

@@ -7,6 +7,7 @@ from .rasterize import (Rasterize, RasterizeFunction, rasterize, rasterize_depth
                         rasterize_silhouettes)
 from .renderer import Renderer
 from .uv_textures import UVTextures, textures_from_image
+from .vertex_colors import VertexColors, textures_from_vertex_colors
 
 __version__ = '1.1.3'
 name = 'neural_renderer_pytorch'

@@ -47,6 +47,8 @@ class TransposeCache:
     registered with rasterize_ops._captured_refs, so the captured step that replays it keeps it alive after eviction
     (graph.CapturedStep.capture claims it).  A build inside a capture raises: the warm-up step builds it."""
 
+    what = "textures_from_image: the uv layout's transpose"         # (names the payload in the capture error)
+
     def __init__(self, size=CACHE_SIZE):
         self.size = int(size)
         self._items = OrderedDict()
@@ -56,7 +58,7 @@ class TransposeCache:
         capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
         if hit is None:
             if capturing:
-                raise RuntimeError("textures_from_image: the uv layout's transpose is not built yet and cannot be built "
+                raise RuntimeError(f"{self.what} is not built yet and cannot be built "
                                    "inside a stream capture (it synchronises); run the step once eagerly first "
                                    "(graph.CapturedStep.capture's warm-up steps do)")
             hit = (build(), tuple(holders))

@@ -1,0 +1,188 @@
+"""Learnable per-vertex colours: `textures_from_vertex_colors` (colours [V,3] of an indexed mesh -> per-face 2x2x2 texture
+cubes, differentiable with respect to the colours) and `VertexColors` (the colours as a parameter).
+
+The cube of a face is core.renderer_utils.vcolor_to_texture_cube of its three corner colours, evaluated by
+d3m_vertex_color_textures in the association of get_textures_from_im (the same bits on an image's grid mesh).  On the
+plane w0 + w1 + w2 = 1 its trilinear sample is the barycentric mix of the corner colours, so the render nodes draw smooth,
+Gouraud-like colour through the sampler they have.
+
+The adjoint is a gather over the CSR adjacency of the faces (a vertex's items 3 f + c in ascending order: what
+d3m_vertex_gather walks), reduced by d3m_vertex_color_textures_backward in a fixed order -- no float atomics, the same bits
+on every run.  A hub vertex (a fan apex, a pole) must not make one lane walk thousands of items: rows longer than LONG_ROW
+items are cut into chunks of CHUNK items, each reduced by a workgroup, and the chunk sums are added in chunk order.  The
+adjacency is built once per (faces tensor, version, V) with torch operators -- where the indices are checked against V --
+and kept in a bounded LRU cache of its own."""
+from collections import namedtuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import _lib
+from .uv_textures import TransposeCache
+
+LONG_ROW = 64           # rows with more items go through the chunked reduction
+CHUNK = 1024            # items per chunk (one workgroup of 256 lanes)
+CACHE_SIZE = 8          # adjacencies kept (least recently used goes)
+
+Adjacency = namedtuple("Adjacency", "offsets items tri chunks long_rows long_chunk_ptr num_vertices num_faces")
+Adjacency.__doc__ = """The faces of one mesh as the kernels read them: tri [F,3] i32, the CSR offsets [V+1] i32 and items [3F]
+i32 (item = 3 f + c, ascending per vertex), chunks [C,2] i32 item ranges of the long rows, long_rows [L] i32 (ascending) and
+long_chunk_ptr [L+1] i32."""
+
+
+class AdjacencyCache(TransposeCache):
+    """uv_textures.TransposeCache for adjacencies: a bounded LRU whose entries also hold the caller's faces tensor (the key
+    names it by address and version); handed out inside a stream capture an entry is registered with
+    rasterize_ops._captured_refs, and a build inside a capture raises."""
+    what = "textures_from_vertex_colors: the faces' adjacency"
+
+    def __init__(self, size=CACHE_SIZE):
+        super().__init__(size)
+
+
+_cache = AdjacencyCache()
+
+
+def _faces_key(faces, num_vertices):
+    return (faces.data_ptr(), faces._version, tuple(faces.shape), faces.dtype, str(faces.device), int(num_vertices))
+
+
+def build_adjacency(faces, num_vertices):
+    """The Adjacency of faces [F,3] (int32 or int64, any device) over num_vertices vertices.  Raises ValueError for an
+    index outside [0, num_vertices).  Synchronises (the range check, the long rows): never inside a capture."""
+    V = int(num_vertices)
+    dev = faces.device
+    flat = faces.reshape(-1).long()
+    lo, hi = int(flat.min()), int(flat.max())
+    if lo < 0 or hi >= V:
+        raise ValueError(f"faces: vertex indices must be in [0, {V}) (found {lo if lo < 0 else hi})")
+    # stable: a vertex's items keep ascending order
+    items = torch.argsort(flat, stable=True).to(torch.int32).contiguous()
+    counts = torch.bincount(flat, minlength=V)
+    offsets = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(counts, 0)
+    # the long rows and their chunks (few: hubs)
+    long_rows = torch.nonzero(counts > LONG_ROW).flatten()
+    starts = offsets[long_rows].cpu().numpy()
+    ends = offsets[long_rows + 1].cpu().numpy()
+    n_ch = (ends - starts + CHUNK - 1) // CHUNK
+    long_chunk_ptr = np.zeros(len(starts) + 1, np.int64)
+    long_chunk_ptr[1:] = np.cumsum(n_ch)
+    chunk_start = np.repeat(starts, n_ch) + CHUNK * (np.arange(int(long_chunk_ptr[-1])) - np.repeat(long_chunk_ptr[:-1], n_ch))
+    chunks = np.stack([chunk_start, np.minimum(chunk_start + CHUNK, np.repeat(ends, n_ch))], 1).astype(np.int32)
+    return Adjacency(offsets.to(torch.int32), items, faces.reshape(-1, 3).to(torch.int32).contiguous(),
+                     torch.from_numpy(chunks.reshape(-1, 2)).to(dev), long_rows.to(torch.int32).contiguous(),
+                     torch.from_numpy(long_chunk_ptr.astype(np.int32)).to(dev), V, int(flat.numel() // 3))
+
+
+def vertex_adjacency(faces, num_vertices, cache=None):
+    """The cached Adjacency of a faces tensor (built on the first call with this tensor at its current version)."""
+    cache = _cache if cache is None else cache
+    return cache.get(_faces_key(faces, num_vertices), lambda: build_adjacency(faces, num_vertices), holders=(faces,))
+
+
+def vertex_color_adjoint(adjacency, grad_textures):
+    """grad_colors [B,V,3] of grad_textures [B,F,2,2,2,3] through the adjacency (d3m_vertex_color_textures_backward)."""
+    A = adjacency
+    g = grad_textures.to(torch.float32).contiguous()
+    if g.dim() != 6 or tuple(g.shape[1:]) != (A.num_faces, 2, 2, 2, 3) or g.device != A.offsets.device:
+        raise ValueError(f"grad_textures must be [B, {A.num_faces}, 2, 2, 2, 3] on {A.offsets.device}")
+    B = g.shape[0]
+    grad_colors = torch.empty(B, A.num_vertices, 3, dtype=torch.float32, device=g.device)
+    n_chunks = A.chunks.shape[0]
+    partials = torch.empty(B, n_chunks, 3, dtype=torch.float32, device=g.device) if n_chunks else None
+    _lib.check(_lib.lib().d3m_vertex_color_textures_backward(
+        _lib.ptr(g), _lib.ptr(A.offsets), _lib.ptr(A.items), _lib.ptr(A.chunks) if n_chunks else None, n_chunks,
+        _lib.ptr(A.long_rows) if n_chunks else None, _lib.ptr(A.long_chunk_ptr) if n_chunks else None,
+        A.long_rows.shape[0], LONG_ROW, _lib.ptr(partials), _lib.ptr(grad_colors), B, A.num_vertices, A.num_faces,
+        _lib.stream_ptr()), "d3m_vertex_color_textures_backward")
+    return grad_colors
+
+
+class _VertexColorTextures(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, colors, adjacency, batched):
+        cols = (colors if batched else colors[None]).contiguous()
+        B, A = cols.shape[0], adjacency
+        out = torch.empty(B, A.num_faces, 2, 2, 2, 3, dtype=torch.float32, device=cols.device)
+        _lib.check(_lib.lib().d3m_vertex_color_textures(_lib.ptr(cols), B, _lib.ptr(A.tri), _lib.ptr(out), A.num_vertices,
+                                                        A.num_faces, _lib.stream_ptr()), "d3m_vertex_color_textures")
+        ctx.adjacency, ctx.batched = adjacency, batched
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad_colors = vertex_color_adjoint(ctx.adjacency, grad_out)
+        return (grad_colors if ctx.batched else grad_colors[0]), None, None
+
+
+def _checked_faces(faces):
+    if not torch.is_tensor(faces) or faces.dtype not in (torch.int32, torch.int64):
+        raise ValueError("faces must be an int32 or int64 tensor")
+    if not ((faces.dim() == 2 or (faces.dim() == 3 and faces.shape[0] == 1)) and faces.shape[-1] == 3 and faces.shape[-2] >= 1):
+        raise ValueError("faces must be [num_faces, 3] or [1, num_faces, 3]")
+    return faces
+
+
+def textures_from_vertex_colors(colors, faces, cache=None):
+    """Per-face texture cubes of per-vertex colours, differentiable with respect to `colors`.
+
+    colors [V,3] or [B,V,3] f32 on the device; faces [F,3] or [1,F,3] int32 / int64 on the same device, a constant.
+    Returns [1,F,2,2,2,3] (or [B,F,2,2,2,3]): the cube of face f is vcolor_to_texture_cube of its corner colours, and
+    rendering it draws the barycentric mix of the three colours.  The first call with a faces tensor builds its adjacency
+    (outside any stream capture; a ValueError for an index outside [0, V)) and later calls reuse it; `cache`: the
+    AdjacencyCache to keep it in (default: the module's)."""
+    if not torch.is_tensor(colors) or colors.dim() not in (2, 3) or colors.shape[-1] != 3 or colors.shape[-2] < 1:
+        raise ValueError("colors must be [num_vertices, 3] or [B, num_vertices, 3]")
+    if colors.dtype != torch.float32:
+        raise ValueError("colors must be float32")
+    faces = _checked_faces(faces)
+    batched = colors.dim() == 3
+    if batched and not 1 <= colors.shape[0] <= 65535:
+        raise ValueError("1 to 65535 colour sets per call")
+    if not colors.is_cuda or faces.device != colors.device:
+        raise ValueError("colors and faces must be on one GPU device")
+    adjacency = vertex_adjacency(faces, colors.shape[-2], cache)
+    return _VertexColorTextures.apply(colors, adjacency, batched)
+
+
+class VertexColors(nn.Module):
+    """The colours of a mesh's vertices as a learnable parameter: `colors` [V,3] (parameter), `faces` [F,3] (buffer);
+    forward() returns the texture cubes [1,F,2,2,2,3].  The module keeps the adjacency of its faces itself, so whatever
+    holds the module (a captured step) keeps the adjacency."""
+
+    def __init__(self, colors, faces):
+        super().__init__()
+        colors = torch.as_tensor(colors)
+        if colors.dim() != 2 or colors.shape[1] != 3 or colors.shape[0] < 1:
+            raise ValueError("colors must be [num_vertices, 3]")
+        faces = _checked_faces(torch.as_tensor(faces))
+        self.colors = nn.Parameter(colors.detach().to(torch.float32).contiguous().clone())
+        self.register_buffer("faces", faces.detach().reshape(-1, 3).contiguous().clone())
+        self._adjacency = AdjacencyCache(1)
+
+    @classmethod
+    def from_textures(cls, textures, faces, num_vertices):
+        """Colours read off texture cubes [F,ts,ts,ts,3] (or [1,F,...]; any ts >= 2, e.g. load_obj(load_texture=True)'s):
+        a vertex's colour is the mean, over its incident faces, of the corner texel the cube gives that corner -- (ts-1,0,0),
+        (0,ts-1,0), (0,0,ts-1) for slot 0, 1, 2; a vertex of no face gets 0.  A one-off in eager torch."""
+        textures = torch.as_tensor(textures)
+        faces = _checked_faces(torch.as_tensor(faces)).reshape(-1, 3)
+        if textures.dim() == 6 and textures.shape[0] == 1:
+            textures = textures[0]
+        F, V = faces.shape[0], int(num_vertices)
+        ts = textures.shape[1] if textures.dim() == 5 else 0
+        if ts < 2 or tuple(textures.shape) != (F, ts, ts, ts, 3):
+            raise ValueError(f"textures must be [{F}, ts, ts, ts, 3] with ts >= 2")
+        flat = faces.reshape(-1).long().to(textures.device)
+        if int(flat.min()) < 0 or int(flat.max()) >= V:
+            raise ValueError(f"faces: vertex indices must be in [0, {V})")
+        t = textures.detach().to(torch.float32)
+        corners = torch.stack([t[:, ts - 1, 0, 0], t[:, 0, ts - 1, 0], t[:, 0, 0, ts - 1]], 1).reshape(-1, 3)
+        total = torch.zeros(V, 3, dtype=torch.float32, device=t.device).index_add_(0, flat, corners)
+        count = torch.bincount(flat, minlength=V).clamp(min=1).to(torch.float32)
+        return cls(total / count[:, None], faces.to(t.device))
+
+    def forward(self):
+        return textures_from_vertex_colors(self.colors, self.faces, cache=self._adjacency)

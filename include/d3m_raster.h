@@ -825,6 +825,28 @@ int d3m_uv_texture_adjoint(const int32_t* row_ptr, const int32_t* entries, const
                            const int32_t* long_rows, const int32_t* long_chunk_ptr, int num_long_rows, int long_row,
                            int lanes_per_row, const float* grad_textures, float* partials, float* grad_image,
                            int batch_size, long num_texels, int image_height, int image_width, d3m_stream_t stream);
+/* Learnable per-vertex colours of an indexed mesh: the map colours -> 2x2x2 cubes and its adjoint.
+ * colors [color_batch, V, 3], tri [F, 3] i32 (every index in [0, V): the caller checks).  WRITES textures
+ * [color_batch, F, 2, 2, 2, 3]: texel idx of face f, channel k, is (C[idx][0] c0 + C[idx][1] c1) + C[idx][2] c2 with
+ * cj = colors[b, tri[f][j], k] and C the 8x3 table of vcolor_to_texture_cube (deep3dmap/core/renderer/utils.py:84-94) --
+ * the association of d3m_textures_from_im, the same bits on the grid mesh of an image.
+ * D3M_ERR_INVALID: NULL colors / tri / textures, a size <= 0, color_batch > 65535. */
+int d3m_vertex_color_textures(const float* colors, int color_batch, const int32_t* tri, float* textures, int num_vertices,
+                              int num_tri, d3m_stream_t stream);
+/* The adjoint (no float atomics, the same bits on every run): WRITES every element of grad_colors [batch_size, V, 3] from
+ * grad_textures [batch_size, F, 2, 2, 2, 3] through the CSR adjacency d3m_vertex_gather walks (adj_offsets [V+1], adj_items
+ * [3 F], item = 3 f + c ascending per vertex): the sum, in item order, of each item's term t = sum over idx ascending of
+ * C[idx][c] * grad_textures[b, f, idx, k]; a vertex of no face gets 0.  Rows of more than long_row items are listed in
+ * long_rows [num_long_rows] (ascending); the chunks of long row l are chunks[long_chunk_ptr[l] .. long_chunk_ptr[l+1]), each
+ * an item range [start, end) i32x2, reduced in a fixed order into partials [batch_size, num_chunks, 3] f32 (scratch) and
+ * added in chunk order.
+ * D3M_ERR_INVALID: NULL grad_textures / adj_offsets / adj_items / grad_colors, a size <= 0, batch_size > 65535,
+ * long_row < 0, 3 F beyond int32, long rows without chunks, chunks without partials. */
+int d3m_vertex_color_textures_backward(const float* grad_textures, const int32_t* adj_offsets, const int32_t* adj_items,
+                                       const int32_t* chunks, int num_chunks, const int32_t* long_rows,
+                                       const int32_t* long_chunk_ptr, int num_long_rows, int long_row, float* partials,
+                                       float* grad_colors, int batch_size, int num_vertices, int num_tri,
+                                       d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
