@@ -39,6 +39,15 @@ class D3MLight(ctypes.Structure):
                 ("direction", _P), ("ia_batch", _I), ("id_batch", _I), ("ca_batch", _I), ("cd_batch", _I), ("dir_batch", _I)]
 
 
+class D3MMeshTopology(ctypes.Structure):
+    """d3m_mesh_topology (include/d3m_raster.h): the neighbour CSR, the wing records and the wing CSR of a faces tensor."""
+    _fields_ = ([(n, _P) for n in ("nbr_offsets", "nbr_items", "wings", "wing_offsets", "wing_items", "nbr_chunks",
+                                   "nbr_long_rows", "nbr_long_chunk_ptr", "wing_chunks", "wing_long_rows",
+                                   "wing_long_chunk_ptr")] +
+                [(n, _I) for n in ("num_vertices", "num_edges", "num_wings", "num_nbr_chunks", "num_nbr_long_rows",
+                                   "num_wing_chunks", "num_wing_long_rows", "long_row")])
+
+
 class D3MFitTargets(ctypes.Structure):
     _fields_ = [("rgb_target", _P), ("depth_target", _P), ("alpha_target", _P), ("mask", _P), ("scratch", _P),
                 ("loss", _P), ("grad_rgb_map", _P), ("grad_alpha_map", _P), ("grad_depth_map", _P), ("grad_loss", _P),
@@ -189,6 +198,8 @@ _SIGNATURES = {
     "d3m_uv_texture_adjoint": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _L, _I, _I, _P]),
     "d3m_vertex_color_textures": (_I, [_P, _I, _P, _P, _I, _I, _P]),
     "d3m_vertex_color_textures_backward": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
+    "d3m_mesh_regularizer_scratch_floats": (_SZ, [_I, ctypes.POINTER(D3MMeshTopology)]),
+    "d3m_mesh_regularizer": (_I, [_P, _I, ctypes.POINTER(D3MMeshTopology), _F, _F, _F, _F, _P, _SZ, _P, _P, _P, _I, _P]),
 }
 
 _lib = None

@@ -10,6 +10,7 @@
 #include "d3m_aux.h"
 #include "d3m_textures.h"
 #include "d3m_vertex_colors.h"
+#include "d3m_mesh_reg.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -2159,6 +2160,76 @@ D3M_EXPORT int d3m_vertex_color_textures_backward(const float* grad_textures, co
     LAUNCH("k_vertex_color_adjoint_rows", k_vertex_color_adjoint_rows, dim3(blocks_for((long)num_vertices * 3, 256), batch_size),
            dim3(256), st, adj_offsets, adj_items, long_rows, long_chunk_ptr, num_long_rows, long_row, partials, num_chunks,
            grad_textures, (long)num_tri, grad_colors, num_vertices);
+    return check_launch();
+}
+
+// Mesh shape regularisers (d3m_mesh_reg.h): Laplacian, edge length and normal consistency, value and gradient.
+struct MeshRegLayout { size_t delta, row_partials, mean_partials, value_partials, total; int row_blocks; };
+static bool mesh_reg_layout(int B, const d3m_mesh_topology* t, MeshRegLayout& l) {
+    if (!t || B <= 0 || B > 65535 || t->num_vertices <= 0 || t->num_edges < 0 || t->num_wings < 0 || t->long_row < 0 ||
+        t->num_nbr_chunks < 0 || t->num_nbr_long_rows < 0 || t->num_wing_chunks < 0 || t->num_wing_long_rows < 0)
+        return false;
+    if (t->num_edges > 0x3FFFFFFF || t->num_wings > 0x1FFFFFFF) return false;         // items are int32
+    l.row_blocks = blocks_for((long)t->num_vertices, MR_BLOCK);
+    l.delta = 0;                                                                        // float4 per vertex
+    l.row_partials = l.delta + (size_t)B * t->num_vertices * 4;                         // float4 per chunk
+    l.mean_partials = l.row_partials + (size_t)B * ((size_t)t->num_nbr_chunks + t->num_wing_chunks) * 4;
+    l.value_partials = l.mean_partials + (size_t)B * t->num_nbr_chunks * 3;
+    l.total = l.value_partials + (size_t)B * l.row_blocks;
+    return true;
+}
+
+D3M_EXPORT size_t d3m_mesh_regularizer_scratch_floats(int batch_size, const d3m_mesh_topology* topology) {
+    MeshRegLayout l;
+    return mesh_reg_layout(batch_size, topology, l) ? l.total : 0;
+}
+
+D3M_EXPORT int d3m_mesh_regularizer(const float* vertices, int batch_size, const d3m_mesh_topology* topology,
+                                    float w_laplacian, float w_edge, float edge_target, float w_normal, float* scratch,
+                                    size_t scratch_floats, const float* grad_scale, float* loss_out, float* grad_vertices,
+                                    int accumulate, d3m_stream_t stream) {
+    MeshRegLayout l;
+    if (!vertices || !loss_out || !scratch || !mesh_reg_layout(batch_size, topology, l)) return D3M_ERR_INVALID;
+    if (!(w_laplacian >= 0.f) || !(w_edge >= 0.f) || !(w_normal >= 0.f) || !(edge_target >= 0.f)) return D3M_ERR_INVALID;
+    if (scratch_floats < l.total || ((uintptr_t)scratch & 15)) return D3M_ERR_INVALID;
+    const d3m_mesh_topology& t = *topology;
+    const bool lap = w_laplacian > 0.f, edge = w_edge > 0.f && t.num_edges > 0, nc = w_normal > 0.f && t.num_wings > 0;
+    if ((lap || edge) && (!t.nbr_offsets || (t.num_edges > 0 && !t.nbr_items))) return D3M_ERR_INVALID;
+    if (nc && (!t.wings || !t.wing_offsets || !t.wing_items || ((uintptr_t)t.wings & 15))) return D3M_ERR_INVALID;
+    if (t.num_nbr_long_rows > 0 && (!t.nbr_long_rows || !t.nbr_long_chunk_ptr || t.num_nbr_chunks == 0)) return D3M_ERR_INVALID;
+    if (t.num_wing_long_rows > 0 && (!t.wing_long_rows || !t.wing_long_chunk_ptr || t.num_wing_chunks == 0)) return D3M_ERR_INVALID;
+    if ((t.num_nbr_chunks > 0 && (!t.nbr_chunks || t.num_nbr_long_rows == 0)) ||
+        (t.num_wing_chunks > 0 && (!t.wing_chunks || t.num_wing_long_rows == 0)))
+        return D3M_ERR_INVALID;
+    MeshRegArgs a;
+    a.t = t;
+    a.x = vertices;
+    a.delta = lap ? reinterpret_cast<float4*>(scratch + l.delta) : nullptr;
+    a.row_partials = scratch + l.row_partials;
+    a.mean_partials = scratch + l.mean_partials;
+    a.value_partials = scratch + l.value_partials;
+    a.c_lap = lap ? (float)((double)w_laplacian / t.num_vertices) : 0.f;
+    a.c_edge = edge ? (float)((double)w_edge / t.num_edges) : 0.f;
+    a.c_nc = nc ? (float)((double)w_normal / t.num_wings) : 0.f;
+    a.edge_target = edge_target;
+    a.grad_scale = grad_scale;
+    a.loss_out = loss_out;
+    a.grad = grad_vertices;
+    a.accumulate = accumulate != 0;
+    hipStream_t st = (hipStream_t)stream;
+    // (the chunk passes only where a term reads the rows they cover)
+    const bool nbr_rows = edge || (lap && grad_vertices);
+    const int row_chunks = (nbr_rows || nc) ? t.num_nbr_chunks + t.num_wing_chunks : 0;
+    if (lap) {
+        if (t.num_nbr_chunks > 0)
+            LAUNCH("k_mesh_reg_mean_chunks", k_mesh_reg_mean_chunks, dim3(t.num_nbr_chunks, batch_size), dim3(MR_BLOCK), st, a);
+        LAUNCH("k_mesh_reg_delta", k_mesh_reg_delta, dim3(l.row_blocks, batch_size), dim3(MR_BLOCK), st, a);
+    }
+    if (row_chunks > 0)
+        LAUNCH("k_mesh_reg_row_chunks", k_mesh_reg_row_chunks, dim3(row_chunks, batch_size), dim3(MR_BLOCK), st, a);
+    LAUNCH("k_mesh_reg_rows", k_mesh_reg_rows, dim3(l.row_blocks, batch_size), dim3(MR_BLOCK), st, a);
+    LAUNCH("k_mesh_reg_finish", k_mesh_reg_finish, dim3(batch_size), dim3(MR_BLOCK), st, (const float*)a.value_partials,
+           l.row_blocks, loss_out, a.accumulate);
     return check_launch();
 }
 

@@ -106,11 +106,17 @@ class MultiViewFit:
     step computes the cubes from the colours (nr.textures_from_vertex_colors) and reduces this rank's cube gradient to
     [V,3] with the fixed-order adjoint BEFORE the exchange, so the flat buffer is [loss | 3V | 3V] instead of
     [loss | 3V | 24F] and step() returns grad_colors [V,3] in the textures' place.
+
+    regularizer: a dict of nr.mesh_regularizer's weights (laplacian, edge, edge_target, normal) or an nr.MeshRegularizer of
+    this mesh: the shape prior of the vertices.  It is one term of the whole objective, not one per camera: RANK 0 alone
+    adds its value to the loss and its gradient to the vertex gradient inside the step, before the exchange, so the
+    all-reduce(SUM) carries it exactly once and R ranks still equal one rank.  step()'s return value keeps its form.
     """
 
     def __init__(self, vertices, triangles, textures, eyes, image_size=512, anti_aliasing=False, rank=0,
                  world_size=1, optimise_textures=True, device="cuda", objective_in_renderer=True, view_groups=1,
-                 split_exchange=None, loss_form="linked", optimise_cameras=False, vertex_colors=None):
+                 split_exchange=None, loss_form="linked", optimise_cameras=False, vertex_colors=None,
+                 regularizer=None):
         self.device = torch.device(device)
         if (vertex_colors is None) == (textures is None):
             raise ValueError("MultiViewFit: give either textures or vertex_colors (the other one None)")
@@ -132,6 +138,21 @@ class MultiViewFit:
                 raise ValueError(f"vertex_colors must be {list(self.vertices.shape)}")
             self.colors.requires_grad_(optimise_textures)
             self._color_adjacency = nr.vertex_colors.AdjacencyCache(1)      # the fit holds its faces' adjacency itself
+        self._reg_weights = self._reg_topology = None
+        if regularizer is not None:
+            from .neural_renderer import mesh_regularizers as mr
+            if isinstance(regularizer, mr.MeshRegularizer):
+                if tuple(regularizer.faces.shape) != tuple(self.triangles.shape) or \
+                        not torch.equal(regularizer.faces.to(self.triangles), self.triangles):
+                    raise ValueError("MultiViewFit: the MeshRegularizer's faces are not this mesh's triangles")
+                regularizer = regularizer.weights
+            unknown = set(regularizer) - {"laplacian", "edge", "edge_target", "normal"}
+            if unknown:
+                raise ValueError(f"MultiViewFit: regularizer has no weight {sorted(unknown)}")
+            self._reg_weights = mr._checked_weights(*(regularizer.get(k, 0.0) for k in ("laplacian", "edge", "edge_target", "normal")))
+            # (built here, outside any capture; the fit holds its faces' topology itself)
+            self._reg_cache = mr.TopologyCache(1)
+            self._reg_topology = mr.mesh_topology(self.triangles, self.vertices.shape[0], cache=self._reg_cache)
         self.eyes = torch.as_tensor(eyes, dtype=torch.float32)[lo:hi].to(self.device).contiguous()
         self.optimise_cameras = bool(optimise_cameras)
         self._grad_eyes = None
@@ -308,7 +329,25 @@ class MultiViewFit:
             at += part.numel()
         if self.optimise_cameras:
             self._grad_eyes.copy_(self.eyes.grad)       # (this rank's views only: exact here, not exchanged)
+        self._add_regularizer()
         return self._flat
+
+    def _add_regularizer(self):
+        """Rank 0 adds the shape prior's value to _flat[0] and its gradient to the vertex part (d3m_mesh_regularizer's
+        accumulate form), inside the step and before the exchange: the SUM over the ranks then holds it once."""
+        if self._reg_topology is None or self.rank != 0:
+            return
+        from .neural_renderer.mesh_regularizers import evaluate
+        nv = self.vertices.numel()
+        evaluate(self.vertices.detach()[None], self._reg_topology, self._reg_weights, loss_out=self._flat[0:1],
+                 grad_out=self._flat[1:1 + nv].view(1, *self.vertices.shape), accumulate=True)
+
+    def regularizer_loss(self):
+        """The shape prior's value alone ([] tensor; for logging), or None without a regularizer."""
+        if self._reg_topology is None:
+            return None
+        from .neural_renderer.mesh_regularizers import evaluate
+        return evaluate(self.vertices.detach()[None], self._reg_topology, self._reg_weights, want_grad=False)[0][0]
 
     # ---- the step in two parts (split_exchange) --------------------------------------------------------------------
     def _forward_and_texture_side(self):
@@ -338,6 +377,7 @@ class MultiViewFit:
         for part, dst in ((gv, self._flat[1:1 + nv]), (gt, self._flat[1 + nv:])):
             if part.data_ptr() != dst.data_ptr():       # (not reached with a valid grad_sink; kept for safety)
                 dst.copy_(part.reshape(-1))
+        self._add_regularizer()         # (travels with [loss | vertex gradient], the second collective)
         return self._flat
 
     def capture_graph(self, warmup=3):

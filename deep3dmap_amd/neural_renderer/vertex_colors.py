@@ -48,6 +48,22 @@ def _faces_key(faces, num_vertices):
     return (faces.data_ptr(), faces._version, tuple(faces.shape), faces.dtype, str(faces.device), int(num_vertices))
 
 
+def long_row_chunks(offsets, counts):
+    """(chunks [C,2] i32, long_rows [L] i32, long_chunk_ptr [L+1] i32) of a CSR (offsets [R+1] i64, counts [R]): the rows of
+    more than LONG_ROW items (few: hubs), ascending, each cut into item ranges [start, end) of CHUNK items in row order."""
+    dev = offsets.device
+    long_rows = torch.nonzero(counts > LONG_ROW).flatten()
+    starts = offsets[long_rows].cpu().numpy()
+    ends = offsets[long_rows + 1].cpu().numpy()
+    n_ch = (ends - starts + CHUNK - 1) // CHUNK
+    long_chunk_ptr = np.zeros(len(starts) + 1, np.int64)
+    long_chunk_ptr[1:] = np.cumsum(n_ch)
+    chunk_start = np.repeat(starts, n_ch) + CHUNK * (np.arange(int(long_chunk_ptr[-1])) - np.repeat(long_chunk_ptr[:-1], n_ch))
+    chunks = np.stack([chunk_start, np.minimum(chunk_start + CHUNK, np.repeat(ends, n_ch))], 1).astype(np.int32)
+    return (torch.from_numpy(chunks.reshape(-1, 2)).to(dev), long_rows.to(torch.int32).contiguous(),
+            torch.from_numpy(long_chunk_ptr.astype(np.int32)).to(dev))
+
+
 def build_adjacency(faces, num_vertices):
     """The Adjacency of faces [F,3] (int32 or int64, any device) over num_vertices vertices.  Raises ValueError for an
     index outside [0, num_vertices).  Synchronises (the range check, the long rows): never inside a capture."""
@@ -62,18 +78,9 @@ def build_adjacency(faces, num_vertices):
     counts = torch.bincount(flat, minlength=V)
     offsets = torch.zeros(V + 1, dtype=torch.int64, device=dev)
     offsets[1:] = torch.cumsum(counts, 0)
-    # the long rows and their chunks (few: hubs)
-    long_rows = torch.nonzero(counts > LONG_ROW).flatten()
-    starts = offsets[long_rows].cpu().numpy()
-    ends = offsets[long_rows + 1].cpu().numpy()
-    n_ch = (ends - starts + CHUNK - 1) // CHUNK
-    long_chunk_ptr = np.zeros(len(starts) + 1, np.int64)
-    long_chunk_ptr[1:] = np.cumsum(n_ch)
-    chunk_start = np.repeat(starts, n_ch) + CHUNK * (np.arange(int(long_chunk_ptr[-1])) - np.repeat(long_chunk_ptr[:-1], n_ch))
-    chunks = np.stack([chunk_start, np.minimum(chunk_start + CHUNK, np.repeat(ends, n_ch))], 1).astype(np.int32)
+    chunks, long_rows, long_chunk_ptr = long_row_chunks(offsets, counts)
     return Adjacency(offsets.to(torch.int32), items, faces.reshape(-1, 3).to(torch.int32).contiguous(),
-                     torch.from_numpy(chunks.reshape(-1, 2)).to(dev), long_rows.to(torch.int32).contiguous(),
-                     torch.from_numpy(long_chunk_ptr.astype(np.int32)).to(dev), V, int(flat.numel() // 3))
+                     chunks, long_rows, long_chunk_ptr, V, int(flat.numel() // 3))
 
 
 def vertex_adjacency(faces, num_vertices, cache=None):

@@ -847,6 +847,39 @@ int d3m_vertex_color_textures_backward(const float* grad_textures, const int32_t
                                        const int32_t* long_chunk_ptr, int num_long_rows, int long_row, float* partials,
                                        float* grad_colors, int batch_size, int num_vertices, int num_tri,
                                        d3m_stream_t stream);
+/* Shape regularisers of an indexed mesh (no float atomics, the same bits on every run).  The topology of the faces, device
+ * arrays of i32 built once by the caller (neural_renderer/mesh_regularizers.py; every index in range: the caller checks):
+ * the E unique edges as a neighbour CSR (nbr_offsets [V+1], nbr_items [2E]: the distinct neighbours of a vertex, ascending);
+ * the P wing records wings [P,4] = (a, b, c, d): an edge a < b and the third vertices c, d of two faces on it; the wing CSR
+ * (wing_offsets [V+1], wing_items [4P]: item = 4 p + role, role 0..3 for a, b, c, d, ascending per vertex).  Rows of more
+ * than long_row items of either CSR are listed in *_long_rows (ascending) with their chunks (item ranges [start, end) i32x2)
+ * chunks[long_chunk_ptr[l] .. long_chunk_ptr[l+1]), as for d3m_vertex_color_textures_backward. */
+typedef struct d3m_mesh_topology {
+    const int32_t *nbr_offsets, *nbr_items, *wings, *wing_offsets, *wing_items;
+    const int32_t *nbr_chunks, *nbr_long_rows, *nbr_long_chunk_ptr;
+    const int32_t *wing_chunks, *wing_long_rows, *wing_long_chunk_ptr;
+    int num_vertices, num_edges, num_wings;
+    int num_nbr_chunks, num_nbr_long_rows, num_wing_chunks, num_wing_long_rows;
+    int long_row;
+} d3m_mesh_topology;
+/* Floats of scratch d3m_mesh_regularizer needs for batch_size vertex sets (0 for an invalid argument). */
+size_t d3m_mesh_regularizer_scratch_floats(int batch_size, const d3m_mesh_topology* topology);
+/* loss[b] = w_laplacian L_lap + w_edge L_edge + w_normal L_nc of vertices [batch_size, V, 3], and its gradient:
+ *   L_lap  = (1/V) sum_v |x_v - mean of v's neighbours|^2 (a vertex without neighbours adds 0),
+ *   L_edge = (1/E) sum_e (|x_a - x_b| - edge_target)^2 (the gradient of an edge of length 0 is 0),
+ *   L_nc   = (1/P) sum_p (1 - cos(n0, n1)), n0 = (b-a) x (c-a), n1 = -(b-a) x (d-a) (a record with a zero normal adds 0).
+ * A term of weight 0 is not evaluated; a term whose count (E, P) is 0 is 0.  WRITES loss_out [batch_size] and every element
+ * of grad_vertices [batch_size, V, 3] (times grad_scale[b], a device array of batch_size floats; NULL: 1); with
+ * accumulate != 0 both are ADDED to what is there.  grad_vertices NULL: the value only.  scratch: 16-byte aligned,
+ * scratch_floats >= d3m_mesh_regularizer_scratch_floats().  At most 3 launches (k_mesh_reg_delta, k_mesh_reg_rows,
+ * k_mesh_reg_finish), 2 more on a mesh with long rows (k_mesh_reg_mean_chunks, k_mesh_reg_row_chunks).
+ * D3M_ERR_INVALID, before any launch: NULL vertices / topology / loss_out / scratch / a NULL array of the topology that the
+ * enabled terms read, a size <= 0 (V; E and P < 0), batch_size > 65535, a negative (or NaN) weight or edge_target, 2E or 4P
+ * beyond int32, long rows without chunks, chunks without their ranges, a scratch that is too small or misaligned. */
+int d3m_mesh_regularizer(const float* vertices, int batch_size, const d3m_mesh_topology* topology, float w_laplacian,
+                         float w_edge, float edge_target, float w_normal, float* scratch, size_t scratch_floats,
+                         const float* grad_scale, float* loss_out, float* grad_vertices, int accumulate,
+                         d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
