@@ -200,6 +200,9 @@ _SIGNATURES = {
     "d3m_vertex_color_textures_backward": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
     "d3m_mesh_regularizer_scratch_floats": (_SZ, [_I, ctypes.POINTER(D3MMeshTopology)]),
     "d3m_mesh_regularizer": (_I, [_P, _I, ctypes.POINTER(D3MMeshTopology), _F, _F, _F, _F, _P, _SZ, _P, _P, _P, _I, _P]),
+    "d3m_morphable_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "d3m_morphable_scratch_floats": (_SZ, [_I, _I, _I]),
+    "d3m_morphable_backward": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

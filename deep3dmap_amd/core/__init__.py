@@ -1,6 +1,8 @@
 """Mirror of the deep3dmap modules that sit directly on the rasterization path:
 deep3dmap/core/renderer/renderer_nr.py (NrRenderer), deep3dmap/core/renderer/renderer_pt3d.py (Pt3dRenderer),
-deep3dmap/core/renderer/utils.py (their helpers) and the losses of deep3dmap/core/utils/utils.py."""
+deep3dmap/core/renderer/utils.py (their helpers), the losses of deep3dmap/core/utils/utils.py and
+deep3dmap/core/all3dmm/bfm_tools.py (param2points_bfm)."""
+from .bfm_tools import param2points_bfm
 from .losses import multiview_fit_loss, photometric_loss, silhouette_loss, smooth_loss
 from .renderer_nr import NrRenderer
 from .renderer_pt3d import Pt3dRenderer

@@ -11,6 +11,7 @@
 #include "d3m_textures.h"
 #include "d3m_vertex_colors.h"
 #include "d3m_mesh_reg.h"
+#include "d3m_morphable.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -2230,6 +2231,60 @@ D3M_EXPORT int d3m_mesh_regularizer(const float* vertices, int batch_size, const
     LAUNCH("k_mesh_reg_rows", k_mesh_reg_rows, dim3(l.row_blocks, batch_size), dim3(MR_BLOCK), st, a);
     LAUNCH("k_mesh_reg_finish", k_mesh_reg_finish, dim3(batch_size), dim3(MR_BLOCK), st, (const float*)a.value_partials,
            l.row_blocks, loss_out, a.accumulate);
+    return check_launch();
+}
+
+// Linear morphable model (d3m_morphable.h): vertices from coefficients, and the fixed-order adjoint.
+static bool morphable_sizes(int B, int R, int K) {
+    return B >= 1 && B <= 4096 && K >= 1 && K <= 1024 && R >= 1 && (long)R * K < 0x80000000L;
+}
+static inline bool misaligned4(const void* p) { return ((uintptr_t)p & 3) != 0; }
+
+D3M_EXPORT size_t d3m_morphable_scratch_floats(int batch_size, int num_rows, int num_components) {
+    if (!morphable_sizes(batch_size, num_rows, num_components)) return 0;
+    return (size_t)blocks_for((long)num_rows, MB_ROWS) * batch_size * num_components;
+}
+
+D3M_EXPORT int d3m_morphable_forward(const float* basis, const float* coeffs, const float* mean, const float* scale, float* out,
+                                     int batch_size, int num_rows, int num_components, d3m_stream_t stream) {
+    if (!basis || !coeffs || !out || !morphable_sizes(batch_size, num_rows, num_components)) return D3M_ERR_INVALID;
+    if (misaligned4(basis) || misaligned4(coeffs) || misaligned4(mean) || misaligned4(scale) || misaligned4(out))
+        return D3M_ERR_INVALID;
+    const int vec = (num_components % 4 == 0) && (((uintptr_t)basis & 15) == 0);
+    const dim3 grid(blocks_for((long)num_rows, MB_FWD_ROWS), blocks_for((long)batch_size, MB_SETS));
+    hipStream_t st = (hipStream_t)stream;
+#define MB_FWD(NB)                                                                                                         \
+    LAUNCH("k_morphable_forward", k_morphable_forward<NB>, grid, dim3(MB_BLOCK), st, basis, coeffs, mean, scale, out,      \
+           batch_size, num_rows, num_components, vec)
+    if (batch_size == 1) MB_FWD(1);
+    else if (batch_size <= 4) MB_FWD(4);
+    else MB_FWD(16);
+#undef MB_FWD
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_morphable_backward(const float* basis, const float* grad_out, const float* scale, const float* grad_scale,
+                                      float* scratch, size_t scratch_floats, float* grad_coeffs, int batch_size, int num_rows,
+                                      int num_components, int accumulate, d3m_stream_t stream) {
+    if (!basis || !grad_out || !grad_coeffs || !scratch || !morphable_sizes(batch_size, num_rows, num_components))
+        return D3M_ERR_INVALID;
+    if (misaligned4(basis) || misaligned4(grad_out) || misaligned4(scale) || misaligned4(grad_scale) || misaligned4(grad_coeffs) ||
+        ((uintptr_t)scratch & 15))
+        return D3M_ERR_INVALID;
+    const int n_chunks = blocks_for((long)num_rows, MB_ROWS);
+    if (scratch_floats < (size_t)n_chunks * batch_size * num_components) return D3M_ERR_INVALID;
+    const dim3 grid(n_chunks, blocks_for((long)num_components, MB_KW), blocks_for((long)batch_size, MB_SETS));
+    hipStream_t st = (hipStream_t)stream;
+#define MB_ADJ(NB)                                                                                                         \
+    LAUNCH("k_morphable_adjoint_chunks", k_morphable_adjoint_chunks<NB>, grid, dim3(MB_BLOCK), st, basis, grad_out, scratch, \
+           batch_size, num_rows, num_components)
+    if (batch_size == 1) MB_ADJ(1);
+    else if (batch_size <= 4) MB_ADJ(4);
+    else MB_ADJ(16);
+#undef MB_ADJ
+    LAUNCH("k_morphable_adjoint_finish", k_morphable_adjoint_finish, dim3(blocks_for((long)num_components, 64), batch_size),
+           dim3(MB_FINISH_GROUPS * 64), st, (const float*)scratch, n_chunks, scale, grad_scale, grad_coeffs, batch_size,
+           num_components, accumulate != 0);
     return check_launch();
 }
 

@@ -111,13 +111,39 @@ class MultiViewFit:
     this mesh: the shape prior of the vertices.  It is one term of the whole objective, not one per camera: RANK 0 alone
     adds its value to the loss and its gradient to the vertex gradient inside the step, before the exchange, so the
     all-reduce(SUM) carries it exactly once and R ranks still equal one rank.  step()'s return value keeps its form.
+
+    morphable=nr.MorphableModel, coeffs=[K] (pass vertices=None): the shape parameter is the model's coefficient vector.  The
+    step computes `fit.vertices` from `fit.coeffs` as its first work (inside the captured step: an in-place update of
+    `fit.coeffs` between replays is read at replay), the render node writes this rank's vertex gradient into a private
+    [3V] buffer, rank 0 adds the regulariser to it, and d3m_morphable_backward reduces it to K floats BEFORE the exchange
+    (the map is linear, so reducing first equals exchanging first): the flat buffer is [loss | K | texture or colour part]
+    and step() returns grad_coeffs [K] in grad_vertices' place.  split_exchange and optimise_cameras are refused with it.
     """
 
     def __init__(self, vertices, triangles, textures, eyes, image_size=512, anti_aliasing=False, rank=0,
                  world_size=1, optimise_textures=True, device="cuda", objective_in_renderer=True, view_groups=1,
                  split_exchange=None, loss_form="linked", optimise_cameras=False, vertex_colors=None,
-                 regularizer=None):
+                 regularizer=None, morphable=None, coeffs=None):
         self.device = torch.device(device)
+        if (morphable is None) != (coeffs is None) or (morphable is None) == (vertices is None):
+            raise ValueError("MultiViewFit: give either vertices, or morphable and coeffs with vertices=None")
+        self.morphable = self.coeffs = self._grad_v = None
+        if morphable is not None:
+            # (the split exchange's second collective carries [loss | vertex gradient], which is not exchanged here)
+            if split_exchange:
+                raise ValueError("MultiViewFit: morphable needs split_exchange=False (or None)")
+            if optimise_cameras:
+                raise ValueError("MultiViewFit: morphable and optimise_cameras are not supported together")
+            split_exchange = False
+            coeffs = torch.as_tensor(coeffs, dtype=torch.float32)
+            if tuple(coeffs.shape) != (morphable.num_components,):
+                raise ValueError(f"coeffs must be [{morphable.num_components}]")
+            self.morphable = morphable
+            # (the model's buffers on this fit's device; the caller's module stays where it is)
+            self._model = tuple(None if t is None else t.detach().to(self.device)
+                                for t in (morphable.basis, morphable.mean, morphable.scale))
+            self.coeffs = coeffs.detach().to(self.device).contiguous()
+            vertices = torch.zeros(morphable.num_vertices, 3)
         if (vertex_colors is None) == (textures is None):
             raise ValueError("MultiViewFit: give either textures or vertex_colors (the other one None)")
         self.rank, self.world_size = rank, world_size
@@ -125,6 +151,9 @@ class MultiViewFit:
         self.n_local = hi - lo
         self.vertices = torch.as_tensor(vertices, dtype=torch.float32).to(self.device).requires_grad_(True)
         self.triangles = torch.as_tensor(triangles, dtype=torch.int32).to(self.device)
+        if self.morphable is not None:
+            self._grad_v = torch.zeros(self.vertices.numel(), dtype=torch.float32, device=self.device)
+            self._vertices_from_coeffs()
         self.textures = self.colors = self._color_adjacency = None
         if vertex_colors is None:
             self.textures = torch.as_tensor(textures, dtype=torch.float32).to(self.device).requires_grad_(optimise_textures)
@@ -186,13 +215,15 @@ class MultiViewFit:
         self.targets = None
         self.mask_sum = None            # [1] device scalar: sum of the mask over ALL ranks' views
         self._mask_sum_local = None
-        # the step's results, packed where they are produced (inside the captured step): [loss | grad_v | grad_t]
+        # the step's results, packed where they are produced (inside the captured step): [loss | grad_v | grad_t], or
+        # [loss | grad_coeffs | grad_t] with a morphable model (the vertex gradient then lives in a buffer of this rank's)
         n_t = self.texture_parameter.numel() if optimise_textures else 0
-        self._flat = torch.zeros(1 + self.vertices.numel() + n_t, dtype=torch.float32, device=self.device)
+        self._n_shape = self.shape_parameter.numel()
+        self._flat = torch.zeros(1 + self._n_shape + n_t, dtype=torch.float32, device=self.device)
         # ... by the rendering node itself where it can: the node's backward writes the two gradients, its forward the loss,
         # straight into these views of the flat buffer (render_fit_loss(grad_sink=...)); _forward_backward packs only what did not
-        nv = self.vertices.numel()
-        self._sink = (self._flat[1:1 + nv].view(1, *self.vertices.shape),
+        nv = self._n_shape
+        self._sink = (self._vertex_gradient().view(1, *self.vertices.shape),
                       self._flat[1 + nv:].view(1, *self.textures.shape) if n_t and self.colors is None else None,
                       self._flat[0:1])
         self._use_sink = False          # only the step's own forward + backward hands the buffers to the node (per call)
@@ -231,6 +262,27 @@ class MultiViewFit:
                                         between=[lambda: me()._start_texture_exchange()])
         else:
             self._runner = CapturedStep(lambda: me()._forward_backward())
+
+    @property
+    def shape_parameter(self):
+        """What the step differentiates the shape by: the vertices [V,3], or the morphable model's coefficients [K]."""
+        return self.vertices if self.morphable is None else self.coeffs
+
+    def _vertex_gradient(self):
+        """Where this rank's vertex gradient [3V] is written: its part of the flat buffer, or the private buffer."""
+        return self._flat[1:1 + self.vertices.numel()] if self.morphable is None else self._grad_v
+
+    def _vertices_from_coeffs(self):
+        """fit.vertices = model(fit.coeffs), written in place (d3m_morphable_forward)."""
+        from .neural_renderer import morphable as mb
+        basis, mean, scale = self._model
+        mb.forward(self.coeffs[None], basis, mean, scale, out=self.vertices.detach().view(1, -1))
+
+    def _reduce_to_coeffs(self):
+        """_flat[1:1+K] = J^T of this rank's vertex gradient (d3m_morphable_backward): the step's last work on the shape."""
+        from .neural_renderer import morphable as mb
+        basis, _, scale = self._model
+        mb.backward(self._grad_v.view(1, -1), basis, scale, out=self._flat[1:1 + self._n_shape].view(1, -1))
 
     @property
     def texture_parameter(self):
@@ -299,6 +351,8 @@ class MultiViewFit:
 
     def _forward_backward(self):
         tex = self.texture_parameter
+        if self.morphable is not None:
+            self._vertices_from_coeffs()
         self.vertices.grad = None
         tex.grad = None
         self.eyes.grad = None
@@ -318,18 +372,17 @@ class MultiViewFit:
         # [loss | grad_v | grad_t] in the persistent buffer the collective runs on: already there when the rendering node
         # produced them in place (grad_sink); packed here (part of the captured step) otherwise -- as the colour gradient
         # is: the cubes' gradient stays on this rank, its adjoint's [V,3] goes into the buffer
-        parts = [loss.detach().reshape(1), self.vertices.grad.reshape(-1)]
+        parts = [(loss.detach().reshape(1), self._flat[0:1]), (self.vertices.grad.reshape(-1), self._vertex_gradient())]
         if tex.requires_grad:
-            parts.append(tex.grad.reshape(-1))
-        at = 0
-        for part in parts:
-            dst = self._flat[at:at + part.numel()]
+            parts.append((tex.grad.reshape(-1), self._flat[1 + self._n_shape:]))
+        for part, dst in parts:
             if part.data_ptr() != dst.data_ptr():
                 dst.copy_(part)
-            at += part.numel()
         if self.optimise_cameras:
             self._grad_eyes.copy_(self.eyes.grad)       # (this rank's views only: exact here, not exchanged)
         self._add_regularizer()
+        if self.morphable is not None:
+            self._reduce_to_coeffs()
         return self._flat
 
     def _add_regularizer(self):
@@ -338,9 +391,8 @@ class MultiViewFit:
         if self._reg_topology is None or self.rank != 0:
             return
         from .neural_renderer.mesh_regularizers import evaluate
-        nv = self.vertices.numel()
         evaluate(self.vertices.detach()[None], self._reg_topology, self._reg_weights, loss_out=self._flat[0:1],
-                 grad_out=self._flat[1:1 + nv].view(1, *self.vertices.shape), accumulate=True)
+                 grad_out=self._vertex_gradient().view(1, *self.vertices.shape), accumulate=True)
 
     def regularizer_loss(self):
         """The shape prior's value alone ([] tensor; for logging), or None without a regularizer."""
@@ -373,7 +425,7 @@ class MultiViewFit:
     def _geometry_side(self):
         gv, gt = self._manual.backward_geometry_side()
         self._manual = None
-        nv = self.vertices.numel()
+        nv = self.vertices.numel()      # (the split exchange is off with a morphable model: the shape part is the vertices')
         for part, dst in ((gv, self._flat[1:1 + nv]), (gt, self._flat[1 + nv:])):
             if part.data_ptr() != dst.data_ptr():       # (not reached with a valid grad_sink; kept for safety)
                 dst.copy_(part.reshape(-1))
@@ -412,9 +464,9 @@ class MultiViewFit:
     def step(self):
         """forward + loss + backward + all-reduce.  Returns (loss, grad_vertices, grad_textures) of the WHOLE objective
         (all ranks' cameras) as views of the persistent flat buffer, valid until the next step -- with vertex_colors the
-        third is grad_colors [V,3]; with optimise_cameras also
+        third is grad_colors [V,3], with a morphable model the second is grad_coeffs [K]; with optimise_cameras also
         grad_eyes [n_local,3], the objective's gradient with respect to this rank's eyes (a persistent buffer as well)."""
-        nv = self.vertices.numel()
+        nv = self._n_shape
         if self.split_exchange:
             flat = self._runner()                   # ... during which the texture part's all-reduce was started
             rest = allreduce_sum_start(flat[:1 + nv])
@@ -423,7 +475,7 @@ class MultiViewFit:
             self._tex_work = None
         else:
             flat = allreduce_sum_(self._runner())
-        gv = flat[1:1 + nv].view_as(self.vertices)
+        gv = flat[1:1 + nv].view_as(self.shape_parameter)
         tex = self.texture_parameter
         gt = flat[1 + nv:].view_as(tex) if tex.requires_grad else None
         if self.optimise_cameras:

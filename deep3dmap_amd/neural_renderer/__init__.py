@@ -4,6 +4,7 @@ from .cameras import get_points_from_angles, look, look_at, perspective, project
 from .mesh_ops import lighting, vertices_to_faces
 from .mesh_regularizers import (MeshRegularizer, edge_length_loss, laplacian_loss, mesh_regularizer, mesh_topology,
                                normal_consistency_loss)
+from .morphable import MorphableModel, morphable_vertices
 from .obj_io import Mesh, load_obj, save_obj
 from .rasterize import (Rasterize, RasterizeFunction, rasterize, rasterize_depth, rasterize_rgbad,
                         rasterize_silhouettes)

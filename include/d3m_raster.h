@@ -880,6 +880,33 @@ int d3m_mesh_regularizer(const float* vertices, int batch_size, const d3m_mesh_t
                          float w_edge, float edge_target, float w_normal, float* scratch, size_t scratch_floats,
                          const float* grad_scale, float* loss_out, float* grad_vertices, int accumulate,
                          d3m_stream_t stream);
+/* The vertices of a linear morphable model and the adjoint of that map (no float atomics, the same bits on every run; f32
+ * VALU with explicit fused multiply-adds).  basis [num_rows, num_components] row-major (num_rows = 3 V from Python),
+ * coeffs [batch_size, num_components]; mean [num_rows] and scale [num_components] may be NULL (0 and 1).
+ * WRITES every element of out [batch_size, num_rows]:  out[b, r] = mean[r] + sum_k basis[r, k] * (scale[k] * coeffs[b, k]).
+ * One launch (k_morphable_forward); the basis is read once per 16 coefficient sets, with 16-byte loads when
+ * num_components % 4 == 0 and basis is 16-byte aligned.  The sum: a row's components in runs of 64, wave w of the workgroup
+ * adding components 16 w .. 16 w + 15 of every run in ascending order, then the four waves' sums in wave order, then mean.
+ * D3M_ERR_INVALID, before any launch: NULL basis / coeffs / out, a pointer that is not 4-byte aligned, batch_size outside
+ * [1, 4096], num_components outside [1, 1024], num_rows < 1, num_rows * num_components >= 2^31. */
+int d3m_morphable_forward(const float* basis, const float* coeffs, const float* mean, const float* scale, float* out,
+                          int batch_size, int num_rows, int num_components, d3m_stream_t stream);
+/* Floats of scratch d3m_morphable_backward needs: ceil(num_rows / 256) * batch_size * num_components (0 for sizes the
+ * entry points refuse). */
+size_t d3m_morphable_scratch_floats(int batch_size, int num_rows, int num_components);
+/* grad_coeffs[b, k] = grad_scale[b] * (scale[k] * sum_r basis[r, k] * grad_out[b, r]), grad_out [batch_size, num_rows];
+ * scale and grad_scale (device arrays) may be NULL (1).  WRITES every element of grad_coeffs [batch_size, num_components];
+ * with accumulate != 0 ADDS to what is there.  Two launches.  k_morphable_adjoint_chunks: a workgroup per chunk of 256
+ * consecutive rows and 64 components, a lane per component; wave w adds rows 64 w .. 64 w + 63 of the chunk in ascending
+ * order, the four waves' sums are added in wave order and stored with plain stores in scratch [chunks, batch_size,
+ * num_components].  k_morphable_adjoint_finish: 16 groups of ceil(chunks / 16) consecutive chunks each, added in ascending
+ * order, then the groups' sums in group order.  The basis is read once per 16 sets.  scratch: 16-byte aligned,
+ * scratch_floats >= d3m_morphable_scratch_floats().
+ * D3M_ERR_INVALID, before any launch: NULL basis / grad_out / grad_coeffs / scratch, a pointer that is not 4-byte aligned
+ * (scratch: 16), the sizes d3m_morphable_forward refuses, a scratch that is too small. */
+int d3m_morphable_backward(const float* basis, const float* grad_out, const float* scale, const float* grad_scale,
+                           float* scratch, size_t scratch_floats, float* grad_coeffs, int batch_size, int num_rows,
+                           int num_components, int accumulate, d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
