@@ -12,6 +12,7 @@
 #include "d3m_vertex_colors.h"
 #include "d3m_mesh_reg.h"
 #include "d3m_morphable.h"
+#include "d3m_pose.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -2285,6 +2286,74 @@ D3M_EXPORT int d3m_morphable_backward(const float* basis, const float* grad_out,
     LAUNCH("k_morphable_adjoint_finish", k_morphable_adjoint_finish, dim3(blocks_for((long)num_components, 64), batch_size),
            dim3(MB_FINISH_GROUPS * 64), st, (const float*)scratch, n_chunks, scale, grad_scale, grad_coeffs, batch_size,
            num_components, accumulate != 0);
+    return check_launch();
+}
+
+// Weak-perspective pose (d3m_pose.h): posed points, their uv and landmarks, and the fixed-order adjoint.
+static bool pose_sizes(int B, int V, int vb, int pose_stride, int L, const void* landmarks) {
+    return B >= 1 && B <= 4096 && V >= 1 && (long)B * V * 3 < 0x80000000L && (vb == 1 || vb == B) && pose_stride >= 7 &&
+           L >= 0 && L <= PS_MAX_LANDMARKS && (L == 0 || landmarks);
+}
+
+D3M_EXPORT void d3m_pose_tree_constants(int* out4) {
+    out4[0] = PS_BLOCK; out4[1] = PS_MAX_PARTS; out4[2] = PS_FINISH_SETS; out4[3] = PS_SUMS;
+}
+
+D3M_EXPORT size_t d3m_pose_scratch_floats(int batch_size, int num_vertices) {
+    if (!pose_sizes(batch_size, num_vertices, 1, 7, 0, nullptr)) return 0;
+    return (size_t)batch_size * pose_parts(num_vertices) * PS_SUMS;
+}
+
+D3M_EXPORT int d3m_pose_forward(const float* vertices, int vertices_batch, const float* pose, int pose_stride,
+                                float translation_scale, float angle_limit, float uv_size, const int32_t* landmarks,
+                                int num_landmarks, float* posed, float* uv, float* landmark_points, int batch_size,
+                                int num_vertices, d3m_stream_t stream) {
+    if (!vertices || !pose || !pose_sizes(batch_size, num_vertices, vertices_batch, pose_stride, num_landmarks, landmarks))
+        return D3M_ERR_INVALID;
+    if (!posed && !uv && !landmark_points) return D3M_ERR_INVALID;
+    if ((uv && !(uv_size > 0.f)) || (landmark_points && num_landmarks == 0)) return D3M_ERR_INVALID;
+    if (misaligned4(vertices) || misaligned4(pose) || misaligned4(landmarks) || misaligned4(posed) || misaligned4(uv) ||
+        misaligned4(landmark_points))
+        return D3M_ERR_INVALID;
+    const long items = ((posed || uv) ? num_vertices : 0) + (landmark_points ? num_landmarks : 0);
+    LAUNCH("k_pose_forward", k_pose_forward, dim3(pose_parts(items), batch_size), dim3(PS_BLOCK), (hipStream_t)stream,
+           vertices, vertices_batch, pose, pose_stride, translation_scale, angle_limit, uv_size, landmarks, num_landmarks,
+           posed, uv, landmark_points, num_vertices);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_pose_backward(const float* vertices, int vertices_batch, const float* pose, int pose_stride,
+                                 float translation_scale, float angle_limit, float uv_size, const int32_t* landmarks,
+                                 int num_landmarks, const float* grad_posed, const float* grad_uv,
+                                 const float* grad_landmark_points, float* scratch, size_t scratch_floats,
+                                 float* grad_vertices, float* grad_pose, int batch_size, int num_vertices,
+                                 d3m_stream_t stream) {
+    if (!vertices || !pose || !pose_sizes(batch_size, num_vertices, vertices_batch, pose_stride, num_landmarks, landmarks))
+        return D3M_ERR_INVALID;
+    if (!grad_vertices && !grad_pose) return D3M_ERR_INVALID;
+    if ((grad_uv && !(uv_size > 0.f)) || (grad_landmark_points && num_landmarks == 0)) return D3M_ERR_INVALID;
+    if (misaligned4(vertices) || misaligned4(pose) || misaligned4(landmarks) || misaligned4(grad_posed) ||
+        misaligned4(grad_uv) || misaligned4(grad_landmark_points) || misaligned4(scratch) || misaligned4(grad_vertices) ||
+        misaligned4(grad_pose))
+        return D3M_ERR_INVALID;
+    const bool dense = grad_posed || grad_uv;               // a gradient at every posed point
+    const bool chunks = grad_vertices || dense;             // (grad_vertices is written in full even when they are zeros)
+    const int parts = dense && grad_pose ? pose_parts(num_vertices) : 0;        // (landmark terms alone enter in the finish)
+    if (parts > 0 && (!scratch || scratch_floats < (size_t)batch_size * parts * PS_SUMS)) return D3M_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    if (chunks)
+        LAUNCH("k_pose_backward_chunks", k_pose_backward_chunks,
+               dim3(pose_parts(num_vertices), vertices_batch > 1 ? batch_size : 1), dim3(PS_BLOCK), st, vertices,
+               vertices_batch, pose, pose_stride, angle_limit, uv_size, grad_posed, grad_uv, grad_vertices,
+               parts > 0 ? scratch : (float*)nullptr, batch_size, num_vertices);
+    const int pose_blocks = grad_pose ? blocks_for((long)batch_size, PS_FINISH_SETS) : 0;
+    const int lm_blocks = !(grad_landmark_points && grad_vertices) ? 0
+                          : (vertices_batch > 1 ? blocks_for(3L * batch_size, PS_FINISH_SETS) : 1);
+    if (pose_blocks + lm_blocks > 0)
+        LAUNCH("k_pose_backward_finish", k_pose_backward_finish, dim3(pose_blocks + lm_blocks), dim3(PS_FINISH_SETS), st,
+               vertices, vertices_batch, pose, pose_stride, translation_scale, angle_limit, landmarks, num_landmarks,
+               grad_landmark_points, (const float*)scratch, parts, grad_vertices, grad_pose, batch_size, num_vertices,
+               pose_blocks);
     return check_launch();
 }
 

@@ -907,6 +907,47 @@ size_t d3m_morphable_scratch_floats(int batch_size, int num_rows, int num_compon
 int d3m_morphable_backward(const float* basis, const float* grad_out, const float* scale, const float* grad_scale,
                            float* scratch, size_t scratch_floats, float* grad_coeffs, int batch_size, int num_rows,
                            int num_components, int accumulate, d3m_stream_t stream);
+/* The weak-perspective pose of a point set, and its adjoint (no float atomics, the same bits on every run; plain f32).
+ * vertices [vertices_batch, num_vertices, 3] with vertices_batch 1 (shared by all sets) or batch_size; pose: batch_size rows
+ * of 7 floats (s, three angles, t), pose_stride floats apart (>= 7; read in place).  With a = clamp(angles, -angle_limit,
+ * +angle_limit) (angle_limit <= 0: no clamp) and R = Rx(a0) Ry(a1) Rz(a2):
+ *   posed[b, v] = s_b (R_b x[v]) + translation_scale t_b                           [batch_size, num_vertices, 3]
+ *   uv[b, v]    = (posed_x / uv_size, 1 - posed_y / uv_size)                        [batch_size, num_vertices, 2]
+ *   landmark_points[b, l] = posed[b, landmarks[l]]                                  [batch_size, num_landmarks, 3]
+ * Each of the three outputs may be NULL (not computed), not all three; with only landmark_points the launch is
+ * O(batch_size * num_landmarks).  landmarks: int32 indices in [0, num_vertices) -- NOT checked here -- and may repeat.
+ * One launch (k_pose_forward); R_b is computed once per workgroup.
+ * D3M_ERR_INVALID, before any launch: NULL vertices / pose, all outputs NULL, uv with uv_size <= 0, landmark_points with
+ * num_landmarks 0, num_landmarks outside [0, 1024] or > 0 with NULL landmarks, batch_size outside [1, 4096], num_vertices
+ * < 1, batch_size * num_vertices * 3 >= 2^31, vertices_batch neither 1 nor batch_size, pose_stride < 7, a pointer that is
+ * not 4-byte aligned. */
+int d3m_pose_forward(const float* vertices, int vertices_batch, const float* pose, int pose_stride, float translation_scale,
+                     float angle_limit, float uv_size, const int32_t* landmarks, int num_landmarks, float* posed, float* uv,
+                     float* landmark_points, int batch_size, int num_vertices, d3m_stream_t stream);
+/* The constants that fix d3m_pose_backward's summation tree: out4 = (vertices per chunk, the cap of parts per set, sets per
+ * finish workgroup, sums per set). */
+void d3m_pose_tree_constants(int* out4);
+/* Floats of scratch d3m_pose_backward needs: batch_size * min(ceil(num_vertices / 256), 64) * 12 (0 for sizes the entry
+ * points refuse). */
+size_t d3m_pose_scratch_floats(int batch_size, int num_vertices);
+/* The adjoint of d3m_pose_forward.  grad_posed / grad_uv / grad_landmark_points (shapes of the outputs) may each be NULL
+ * (zeros); G[b, v] = grad_posed + (grad_uv.x / uv_size, -grad_uv.y / uv_size, 0) + the landmark gradients pointing at v.
+ * WRITES every element of grad_vertices [vertices_batch, num_vertices, 3] = s_b R_b^T G[b, v] (vertices_batch 1: summed over
+ * the sets in ascending order) and of grad_pose [batch_size, 7] (dense) = (<M_b, R_b>, s_b <M_b, dR_b/da_k> where
+ * -angle_limit <= angle_k <= angle_limit and 0 elsewhere, translation_scale n_b) with M_b = sum_v G (x) x, n_b = sum_v G;
+ * either may be NULL (not computed), not both.  At most two launches.  k_pose_backward_chunks: workgroup p of a set's
+ * min(ceil(num_vertices / 256), 64) takes the vertices 256 p + lane, + 256 parts, ... in ascending order per lane, adds the
+ * lanes of a wave, then the four waves in order, and stores one partial per (set, p) in scratch; it writes grad_vertices
+ * from the same read.  k_pose_backward_finish: a lane per set adds the partials in ascending p, then the landmark terms in
+ * ascending l, and applies the Euler adjoint; the landmark gradients are added to grad_vertices by one lane per (set,
+ * coordinate) walking l in ascending order (vertices_batch 1: summed over the sets in ascending order first).
+ * scratch_floats >= d3m_pose_scratch_floats() when grad_pose is given together with grad_posed or grad_uv.
+ * D3M_ERR_INVALID, before any launch: what d3m_pose_forward refuses of the inputs, grad_uv with uv_size <= 0,
+ * grad_landmark_points with num_landmarks 0, both outputs NULL, a scratch that is needed and NULL or too small. */
+int d3m_pose_backward(const float* vertices, int vertices_batch, const float* pose, int pose_stride, float translation_scale,
+                      float angle_limit, float uv_size, const int32_t* landmarks, int num_landmarks, const float* grad_posed,
+                      const float* grad_uv, const float* grad_landmark_points, float* scratch, size_t scratch_floats,
+                      float* grad_vertices, float* grad_pose, int batch_size, int num_vertices, d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
