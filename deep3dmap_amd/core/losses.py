@@ -8,6 +8,16 @@ from ..neural_renderer._util import f32c
 EPS = 1e-7
 
 
+def _broadcast(name, t, shape, one_channel=False):
+    """t expanded to `shape` by torch's broadcasting rules; NotImplementedError for per-channel values where the kernel
+    takes one channel, ValueError for what does not broadcast"""
+    if one_channel and t.dim() == len(shape) and t.shape[1] != 1:
+        raise NotImplementedError(f"photometric_loss: {name} must have one channel")
+    if t.dim() > len(shape) or any(k != 1 and k != n for k, n in zip(t.shape[::-1], shape[::-1])):
+        raise ValueError(f"photometric_loss: {name} of shape {tuple(t.shape)} does not broadcast to {tuple(shape)}")
+    return t.expand(shape)
+
+
 class _Photometric(torch.autograd.Function):
     @staticmethod
     def forward(ctx, im1, im2, mask, conf_sigma):
@@ -18,10 +28,14 @@ class _Photometric(torch.autograd.Function):
             if t is not None and need:
                 raise NotImplementedError(f"photometric_loss: no gradient with respect to {name} (detach it, or compose "
                                           "the loss from tensor ops)")
-        a, b = f32c(im1), f32c(im2)
-        B, C, H, W = a.shape
-        m = f32c(mask) if mask is not None else None
-        s = f32c(conf_sigma) if conf_sigma is not None else None
+        # the kernel reads im2 as [B,C,H,W] and mask / conf_sigma as [B,1,H,W]: broadcast here what the reference's tensor
+        # algebra broadcasts (im1 - im2, conf_sigma + EPS, mask.expand_as), and refuse the rest before anything is launched
+        if im1.dim() != 4:
+            raise ValueError(f"photometric_loss: im1 must be [B,C,H,W], got {tuple(im1.shape)}")
+        B, C, H, W = im1.shape
+        a, b = f32c(im1), f32c(_broadcast("im2", im2, (B, C, H, W)))
+        m = f32c(_broadcast("mask", mask, (B, 1, H, W), True)) if mask is not None else None
+        s = f32c(_broadcast("conf_sigma", conf_sigma, (B, 1, H, W), True)) if conf_sigma is not None else None
         loss = torch.empty((), dtype=torch.float32, device=a.device)
         need = ctx.needs_input_grad[0]
         grad = torch.empty_like(a) if need else None
@@ -40,13 +54,14 @@ class _Photometric(torch.autograd.Function):
 
 def photometric_loss(im1, im2, mask=None, conf_sigma=None):
     """Masked mean L1, optionally the Laplacian NLL with per-pixel sigma (utils.py:105-114).
-    im1/im2 [B,C,H,W]; mask / conf_sigma [B,1,H,W] (broadcast over channels).  Gradient flows to im1."""
+    im1 [B,C,H,W]; im2 anything that broadcasts to it; mask / conf_sigma anything that broadcasts to [B,1,H,W] (one
+    channel, applied to every channel of the images).  Gradient flows to im1."""
     if im1.dim() == 3:
         im1, im2 = im1[:, None], im2[:, None]
     if mask is not None and mask.dim() == 3:
         mask = mask[:, None]
-    if mask is not None and mask.shape[1] != 1:
-        raise NotImplementedError("photometric_loss: mask must have one channel")
+    if conf_sigma is not None and conf_sigma.dim() == 3:
+        conf_sigma = conf_sigma[:, None]
     return _Photometric.apply(im1, im2, mask, conf_sigma)
 
 
