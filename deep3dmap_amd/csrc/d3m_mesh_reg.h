@@ -13,14 +13,15 @@
 //
 // Passes: k_mesh_reg_delta (delta and 1/deg of every vertex into scratch; only with the Laplacian), k_mesh_reg_rows (the
 // gathered gradient and the workgroup's value), k_mesh_reg_finish.  Rows of more than long_row items (a pole, a fan apex)
-// go through the chunk kernels in both directions: k_mesh_reg_mean_chunks (the hub's neighbour sum for delta) and
-// k_mesh_reg_row_chunks (its gathered gradient and value); chunk sums are added in chunk order.
+// go through the chunks of d3m_row_gather.h, which states the order, in both directions: k_mesh_reg_mean_chunks (the hub's
+// neighbour sum for delta) and k_mesh_reg_row_chunks (its gathered gradient and value).
 #pragma once
 #include "d3m_aux.h"
+#include "d3m_row_gather.h"
 
 namespace d3m {
 
-constexpr int MR_BLOCK = 256;
+constexpr int MR_BLOCK = RG_BLOCK;
 
 struct MeshRegArgs {
     d3m_mesh_topology t;
@@ -46,25 +47,14 @@ __device__ __forceinline__ mr3 mr_sub(mr3 a, mr3 b) { return {a.x - b.x, a.y - b
 __device__ __forceinline__ mr3 mr_cross(mr3 a, mr3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ float mr_dot(mr3 a, mr3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 
-// index of the long row `v` in long_rows (ascending, holds v)
-__device__ __forceinline__ int mr_find_long(const int32_t* __restrict__ long_rows, int n_long, int v) {
-    int lo = 0, hi = n_long - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (long_rows[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+// the long-row tables of the neighbour CSR and of the wing CSR
+__device__ __forceinline__ LongRows mr_nbr_longs(const d3m_mesh_topology& t) {
+    return {reinterpret_cast<const int2*>(t.nbr_chunks), t.nbr_long_rows, t.nbr_long_chunk_ptr, t.num_nbr_chunks,
+            t.num_nbr_long_rows, t.long_row};
 }
-
-// the long row that owns chunk `ch`: the last l with long_chunk_ptr[l] <= ch
-__device__ __forceinline__ int mr_chunk_owner(const int32_t* __restrict__ long_rows, const int32_t* __restrict__ long_chunk_ptr,
-                                              int n_long, int ch) {
-    int lo = 0, hi = n_long - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (long_chunk_ptr[mid] <= ch) lo = mid; else hi = mid - 1;
-    }
-    return long_rows[lo];
+__device__ __forceinline__ LongRows mr_wing_longs(const d3m_mesh_topology& t) {
+    return {reinterpret_cast<const int2*>(t.wing_chunks), t.wing_long_rows, t.wing_long_chunk_ptr, t.num_wing_chunks,
+            t.num_wing_long_rows, t.long_row};
 }
 
 // One item of v's neighbour row: what neighbour u adds to v's gradient (x, y, z) and to the value (w).
@@ -120,34 +110,27 @@ __device__ __forceinline__ float4 mr_wing_term(const MeshRegArgs& a, const float
 }
 
 __device__ __forceinline__ void mr_add(float4& acc, float4 t) { acc.x += t.x; acc.y += t.y; acc.z += t.z; acc.w += t.w; }
+__device__ __forceinline__ void mr_add(float (&acc)[4], float4 t) { acc[0] += t.x; acc[1] += t.y; acc[2] += t.z; acc[3] += t.w; }
 
-// fixed-order sum over the workgroup: a butterfly inside each wave, then the waves' sums in wave order (valid in lane 0)
-__device__ __forceinline__ float mr_block_sum(float v, float* wave_sum) {
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.f;
-#pragma unroll
-    for (int w = 0; w < MR_BLOCK / 64; w++) s += wave_sum[w];
-    __syncthreads();
-    return s;
+// adds the chunk sums (gradient, value) of the long row `v` onto acc
+__device__ __forceinline__ void mr_add_long_row(const LongRows& t, int v, const float* __restrict__ part, float4& acc) {
+    float s[4] = {acc.x, acc.y, acc.z, acc.w};
+    rg_add_chunk_sums(t, rg_find_long(t, v), part, s);
+    acc = make_float4(s[0], s[1], s[2], s[3]);
 }
 
 // ---- the hubs' neighbour sums: one workgroup per chunk of a long neighbour row ------------------------------------------
 __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_mean_chunks(MeshRegArgs a) {
-    __shared__ float wave_sum[MR_BLOCK / 64];
     const int ch = blockIdx.x, b = blockIdx.y;
-    const int2 range = reinterpret_cast<const int2*>(a.t.nbr_chunks)[ch];
     const float* x = a.x + (size_t)b * a.t.num_vertices * 3;
-    mr3 acc = {0.f, 0.f, 0.f};
-    for (int e = range.x + (int)threadIdx.x; e < range.y; e += MR_BLOCK) {
+    float sum[3];
+    rg_chunk_sum(mr_nbr_longs(a.t).chunks[ch], sum, [&](int e, float (&acc)[3]) {
         const mr3 xu = mr_load(x, a.t.nbr_items[e]);
-        acc.x += xu.x; acc.y += xu.y; acc.z += xu.z;
-    }
-    const float sx = mr_block_sum(acc.x, wave_sum), sy = mr_block_sum(acc.y, wave_sum), sz = mr_block_sum(acc.z, wave_sum);
+        acc[0] += xu.x; acc[1] += xu.y; acc[2] += xu.z;
+    });
     if (threadIdx.x == 0) {
         float* out = a.mean_partials + ((size_t)b * a.t.num_nbr_chunks + ch) * 3;
-        out[0] = sx; out[1] = sy; out[2] = sz;
+        out[0] = sum[0]; out[1] = sum[1]; out[2] = sum[2];
     }
 }
 
@@ -159,54 +142,48 @@ __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_delta(MeshRegArgs a) {
     const int start = a.t.nbr_offsets[v], end = a.t.nbr_offsets[v + 1], deg = end - start;
     float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
     if (deg > 0) {
-        mr3 s = {0.f, 0.f, 0.f};
-        if (deg > a.t.long_row && a.t.num_nbr_long_rows > 0) {
-            const int l = mr_find_long(a.t.nbr_long_rows, a.t.num_nbr_long_rows, v);
-            const float* part = a.mean_partials + (size_t)b * a.t.num_nbr_chunks * 3;
-            for (int c = a.t.nbr_long_chunk_ptr[l]; c < a.t.nbr_long_chunk_ptr[l + 1]; c++) {
-                s.x += part[(size_t)c * 3]; s.y += part[(size_t)c * 3 + 1]; s.z += part[(size_t)c * 3 + 2];
-            }
+        const LongRows longs = mr_nbr_longs(a.t);
+        float s[3] = {0.f, 0.f, 0.f};
+        if (rg_is_long(longs, deg)) {
+            rg_add_chunk_sums(longs, rg_find_long(longs, v), a.mean_partials + (size_t)b * a.t.num_nbr_chunks * 3, s);
         } else {
             for (int e = start; e < end; e++) {
                 const mr3 xu = mr_load(x, a.t.nbr_items[e]);
-                s.x += xu.x; s.y += xu.y; s.z += xu.z;
+                s[0] += xu.x; s[1] += xu.y; s[2] += xu.z;
             }
         }
         const float inv = 1.0f / (float)deg;
         const mr3 xv = mr_load(x, v);
-        out = make_float4(xv.x - s.x * inv, xv.y - s.y * inv, xv.z - s.z * inv, inv);
+        out = make_float4(xv.x - s[0] * inv, xv.y - s[1] * inv, xv.z - s[2] * inv, inv);
     }
     a.delta[(size_t)b * V + v] = out;
 }
 
 // ---- the hubs' gathered gradient and value: one workgroup per chunk of a long neighbour row, then of a long wing row ----
 __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_row_chunks(MeshRegArgs a) {
-    __shared__ float wave_sum[MR_BLOCK / 64];
     const int ch = blockIdx.x, b = blockIdx.y, V = a.t.num_vertices;
     const float* x = a.x + (size_t)b * V * 3;
-    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
     if (ch < a.t.num_nbr_chunks) {
-        const int v = mr_chunk_owner(a.t.nbr_long_rows, a.t.nbr_long_chunk_ptr, a.t.num_nbr_long_rows, ch);
-        const int2 range = reinterpret_cast<const int2*>(a.t.nbr_chunks)[ch];
+        const LongRows longs = mr_nbr_longs(a.t);
+        const int v = rg_chunk_owner(longs, ch);
         const float4* delta = a.delta ? a.delta + (size_t)b * V : nullptr;
         const mr3 xv = mr_load(x, v);
-        for (int e = range.x + (int)threadIdx.x; e < range.y; e += MR_BLOCK) mr_add(acc, mr_nbr_term(a, x, delta, v, xv, a.t.nbr_items[e]));
+        rg_lane_sum(longs.chunks[ch], acc, [&](int e, float (&t)[4]) { mr_add(t, mr_nbr_term(a, x, delta, v, xv, a.t.nbr_items[e])); });
     } else if (a.c_nc > 0.f) {
-        const int2 range = reinterpret_cast<const int2*>(a.t.wing_chunks)[ch - a.t.num_nbr_chunks];
-        for (int e = range.x + (int)threadIdx.x; e < range.y; e += MR_BLOCK) mr_add(acc, mr_wing_term(a, x, a.t.wing_items[e]));
+        rg_lane_sum(mr_wing_longs(a.t).chunks[ch - a.t.num_nbr_chunks], acc,
+                    [&](int e, float (&t)[4]) { mr_add(t, mr_wing_term(a, x, a.t.wing_items[e])); });
     }
-    const float sx = mr_block_sum(acc.x, wave_sum), sy = mr_block_sum(acc.y, wave_sum), sz = mr_block_sum(acc.z, wave_sum),
-                sw = mr_block_sum(acc.w, wave_sum);
+    rg_block_sum(acc);
     if (threadIdx.x == 0) {
         float* out = a.row_partials + ((size_t)b * (a.t.num_nbr_chunks + a.t.num_wing_chunks) + ch) * 4;
-        out[0] = sx; out[1] = sy; out[2] = sz; out[3] = sw;
+        out[0] = acc[0]; out[1] = acc[1]; out[2] = acc[2]; out[3] = acc[3];
     }
 }
 
 // ---- rows: one lane per vertex walks its neighbour row and its wing row; the workgroup stores 768 contiguous floats and
 // one value partial ----------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_rows(MeshRegArgs a) {
-    __shared__ float wave_sum[MR_BLOCK / 64];
     __shared__ float staged[MR_BLOCK * 3];
     const int v = blockIdx.x * MR_BLOCK + threadIdx.x, b = blockIdx.y, V = a.t.num_vertices;
     const float* x = a.x + (size_t)b * V * 3;
@@ -221,29 +198,28 @@ __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_rows(MeshRegArgs a) {
             acc = make_float4(s * dv.x, s * dv.y, s * dv.z, a.c_lap * (dv.x * dv.x + dv.y * dv.y + dv.z * dv.z));
         }
         if (a.c_edge > 0.f || (a.c_lap > 0.f && a.grad)) {
+            const LongRows longs = mr_nbr_longs(a.t);
             const int start = a.t.nbr_offsets[v], end = a.t.nbr_offsets[v + 1];
-            if (end - start > a.t.long_row && a.t.num_nbr_long_rows > 0) {
-                const int l = mr_find_long(a.t.nbr_long_rows, a.t.num_nbr_long_rows, v);
-                for (int c = a.t.nbr_long_chunk_ptr[l]; c < a.t.nbr_long_chunk_ptr[l + 1]; c++)
-                    mr_add(acc, reinterpret_cast<const float4*>(part)[c]);
+            if (rg_is_long(longs, end - start)) {
+                mr_add_long_row(longs, v, part, acc);
             } else {
                 const mr3 xv = mr_load(x, v);
                 for (int e = start; e < end; e++) mr_add(acc, mr_nbr_term(a, x, delta, v, xv, a.t.nbr_items[e]));
             }
         }
         if (a.c_nc > 0.f) {
+            const LongRows longs = mr_wing_longs(a.t);
             const int start = a.t.wing_offsets[v], end = a.t.wing_offsets[v + 1];
-            if (end - start > a.t.long_row && a.t.num_wing_long_rows > 0) {
-                const int l = mr_find_long(a.t.wing_long_rows, a.t.num_wing_long_rows, v);
-                for (int c = a.t.wing_long_chunk_ptr[l]; c < a.t.wing_long_chunk_ptr[l + 1]; c++)
-                    mr_add(acc, reinterpret_cast<const float4*>(part)[a.t.num_nbr_chunks + c]);
+            if (rg_is_long(longs, end - start)) {
+                mr_add_long_row(longs, v, part + (size_t)a.t.num_nbr_chunks * 4, acc);
             } else {
                 for (int e = start; e < end; e++) mr_add(acc, mr_wing_term(a, x, a.t.wing_items[e]));
             }
         }
     }
-    const float value = mr_block_sum(acc.w, wave_sum);
-    if (threadIdx.x == 0) a.value_partials[(size_t)b * gridDim.x + blockIdx.x] = value;
+    float value[1] = {acc.w};
+    rg_block_sum(value);
+    if (threadIdx.x == 0) a.value_partials[(size_t)b * gridDim.x + blockIdx.x] = value[0];
     if (!a.grad) return;
     const float scale = a.grad_scale ? a.grad_scale[b] : 1.0f;
     staged[threadIdx.x * 3 + 0] = scale * acc.x;

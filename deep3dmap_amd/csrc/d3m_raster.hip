@@ -2098,6 +2098,14 @@ D3M_EXPORT int d3m_uv_texture_taps(const float* faces_uv, const int32_t* face_ma
     return check_launch();
 }
 
+// One CSR's long-row tables (d3m_row_gather.h) as an entry point receives them: counts that are not negative, long rows
+// and chunks only together, each with its arrays, and somewhere to put the chunk sums.
+static bool long_rows_ok(const void* chunks, int num_chunks, const void* long_rows, const void* long_chunk_ptr,
+                         int num_long_rows, const void* partials) {
+    if (num_chunks < 0 || num_long_rows < 0 || (num_chunks > 0) != (num_long_rows > 0)) return false;
+    return num_chunks == 0 || (chunks && long_rows && long_chunk_ptr && partials);
+}
+
 D3M_EXPORT int d3m_uv_texture_adjoint(const int32_t* row_ptr, const int32_t* entries, const int32_t* chunks, int num_chunks,
                                       const int32_t* long_rows, const int32_t* long_chunk_ptr, int num_long_rows,
                                       int long_row, int lanes_per_row, const float* grad_textures, float* partials,
@@ -2105,13 +2113,13 @@ D3M_EXPORT int d3m_uv_texture_adjoint(const int32_t* row_ptr, const int32_t* ent
                                       int image_width, d3m_stream_t stream) {
     if (!row_ptr || !grad_textures || !grad_image) return D3M_ERR_INVALID;
     if (batch_size <= 0 || batch_size > 65535 || num_texels <= 0 || image_height <= 0 || image_width <= 0 ||
-        long_row < 0 || num_chunks < 0 || num_long_rows < 0)
+        long_row < 0)
         return D3M_ERR_INVALID;
     if (lanes_per_row != 1 && lanes_per_row != 2 && lanes_per_row != 4 && lanes_per_row != 8 && lanes_per_row != 16)
         return D3M_ERR_INVALID;
     if ((long)image_height * image_width >= 0x7FFFFFFF) return D3M_ERR_INVALID;
-    if (num_long_rows > 0 && (!long_rows || !long_chunk_ptr || num_chunks == 0)) return D3M_ERR_INVALID;
-    if (num_chunks > 0 && (!chunks || !partials || !entries)) return D3M_ERR_INVALID;
+    if (!long_rows_ok(chunks, num_chunks, long_rows, long_chunk_ptr, num_long_rows, partials)) return D3M_ERR_INVALID;
+    if (num_chunks > 0 && !entries) return D3M_ERR_INVALID;
     const int n_pixels = image_height * image_width;
     hipStream_t st = (hipStream_t)stream;
     if (num_chunks > 0)
@@ -2149,12 +2157,9 @@ D3M_EXPORT int d3m_vertex_color_textures_backward(const float* grad_textures, co
                                                   int num_long_rows, int long_row, float* partials, float* grad_colors,
                                                   int batch_size, int num_vertices, int num_tri, d3m_stream_t stream) {
     if (!grad_textures || !adj_offsets || !adj_items || !grad_colors) return D3M_ERR_INVALID;
-    if (batch_size <= 0 || batch_size > 65535 || num_vertices <= 0 || num_tri <= 0 || long_row < 0 || num_chunks < 0 ||
-        num_long_rows < 0)
-        return D3M_ERR_INVALID;
+    if (batch_size <= 0 || batch_size > 65535 || num_vertices <= 0 || num_tri <= 0 || long_row < 0) return D3M_ERR_INVALID;
     if ((long)num_tri * 3 > 0x7FFFFFFF) return D3M_ERR_INVALID;        // items are int32
-    if (num_long_rows > 0 && (!long_rows || !long_chunk_ptr || num_chunks == 0)) return D3M_ERR_INVALID;
-    if (num_chunks > 0 && (!chunks || !partials)) return D3M_ERR_INVALID;
+    if (!long_rows_ok(chunks, num_chunks, long_rows, long_chunk_ptr, num_long_rows, partials)) return D3M_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (num_chunks > 0)
         LAUNCH("k_vertex_color_adjoint_chunks", k_vertex_color_adjoint_chunks, dim3(num_chunks, batch_size),
@@ -2198,10 +2203,9 @@ D3M_EXPORT int d3m_mesh_regularizer(const float* vertices, int batch_size, const
     const bool lap = w_laplacian > 0.f, edge = w_edge > 0.f && t.num_edges > 0, nc = w_normal > 0.f && t.num_wings > 0;
     if ((lap || edge) && (!t.nbr_offsets || (t.num_edges > 0 && !t.nbr_items))) return D3M_ERR_INVALID;
     if (nc && (!t.wings || !t.wing_offsets || !t.wing_items || ((uintptr_t)t.wings & 15))) return D3M_ERR_INVALID;
-    if (t.num_nbr_long_rows > 0 && (!t.nbr_long_rows || !t.nbr_long_chunk_ptr || t.num_nbr_chunks == 0)) return D3M_ERR_INVALID;
-    if (t.num_wing_long_rows > 0 && (!t.wing_long_rows || !t.wing_long_chunk_ptr || t.num_wing_chunks == 0)) return D3M_ERR_INVALID;
-    if ((t.num_nbr_chunks > 0 && (!t.nbr_chunks || t.num_nbr_long_rows == 0)) ||
-        (t.num_wing_chunks > 0 && (!t.wing_chunks || t.num_wing_long_rows == 0)))
+    // (the chunk sums of both CSRs go to scratch)
+    if (!long_rows_ok(t.nbr_chunks, t.num_nbr_chunks, t.nbr_long_rows, t.nbr_long_chunk_ptr, t.num_nbr_long_rows, scratch) ||
+        !long_rows_ok(t.wing_chunks, t.num_wing_chunks, t.wing_long_rows, t.wing_long_chunk_ptr, t.num_wing_long_rows, scratch))
         return D3M_ERR_INVALID;
     MeshRegArgs a;
     a.t = t;

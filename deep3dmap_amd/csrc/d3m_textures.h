@@ -3,6 +3,7 @@
 // Both are element-wise and HBM-bound (one texel / one atlas pixel per lane, outputs written coalesced).
 #pragma once
 #include "d3m_launch.h"
+#include "d3m_row_gather.h"
 
 enum { D3M_WRAP_REPEAT = 0, D3M_WRAP_MIRRORED_REPEAT = 1, D3M_WRAP_CLAMP_TO_EDGE = 2, D3M_WRAP_CLAMP_TO_BORDER = 3 };
 
@@ -172,41 +173,32 @@ __global__ void __launch_bounds__(256) k_uv_texture_taps(const float* __restrict
 
 // The adjoint as a gather over the transpose (CSR, one row per pixel: row_ptr [H*W+1], entries [nnz] of (texel, weight
 // bits) in ascending texel order): grad_image[b, p, k] = sum over the row of w * grad_textures[b, texel, k], in row order.
-// Rows longer than long_row entries (pixel (0,0) gets one per face) are cut into chunks [start, end) of the entry array;
-// k_uv_adjoint_chunks reduces each chunk in a fixed order into partials [B, n_chunks, 3], and k_uv_adjoint_rows adds a
-// long row's chunk sums in chunk order.  No float atomics: the result is the same bits on every run.
-constexpr int UV_ADJ_BLOCK = 256;
+// Rows longer than long_row entries (pixel (0,0) gets one per face) go through the chunks of d3m_row_gather.h, which states
+// the order: k_uv_adjoint_chunks reduces each chunk into partials [B, n_chunks, 3], and k_uv_adjoint_rows adds a long row's
+// chunk sums.  No float atomics: the result is the same bits on every run.
+constexpr int UV_ADJ_BLOCK = d3m::RG_BLOCK;
+
+// one entry's term onto acc: w * g[texel], the product rounded before the sum
+__device__ __forceinline__ void uv_add_entry(const int2* __restrict__ entries, const float* __restrict__ g, int e,
+                                             float (&acc)[3]) {
+    const int2 en = entries[e];
+    const float w = __int_as_float(en.y);
+    const float* gt = g + (long)en.x * 3;
+#pragma unroll
+    for (int k = 0; k < 3; k++) acc[k] += w * gt[k];
+}
 
 __global__ void __launch_bounds__(UV_ADJ_BLOCK) k_uv_adjoint_chunks(const int2* __restrict__ entries,
                                                                     const int2* __restrict__ chunks, int n_chunks,
                                                                     const float* __restrict__ grad_textures,
                                                                     long n_texels, float* __restrict__ partials) {
     const int c = blockIdx.x, b = blockIdx.y;
-    const int2 range = chunks[c];
     const float* g = grad_textures + (long)b * n_texels * 3;
-    float acc[3] = {0, 0, 0};
-    for (int e = range.x + (int)threadIdx.x; e < range.y; e += UV_ADJ_BLOCK) {
-        const int2 en = entries[e];
-        const float w = __int_as_float(en.y);
-        const float* gt = g + (long)en.x * 3;
-#pragma unroll
-        for (int k = 0; k < 3; k++) acc[k] += w * gt[k];
-    }
-    // fixed-order reduction: a butterfly inside each wave, then the waves' sums in wave order
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-        for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
-    __shared__ float wave_sum[UV_ADJ_BLOCK / 64][3];
-    const int wave = threadIdx.x / 64;
-    if ((threadIdx.x & 63) == 0) {
-        wave_sum[wave][0] = acc[0]; wave_sum[wave][1] = acc[1]; wave_sum[wave][2] = acc[2];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float s = 0;
-#pragma unroll
-        for (int w = 0; w < UV_ADJ_BLOCK / 64; w++) s += wave_sum[w][threadIdx.x];
-        partials[((long)b * n_chunks + c) * 3 + threadIdx.x] = s;
+    float sum[3];
+    d3m::rg_chunk_sum(chunks[c], sum, [&](int e, float (&acc)[3]) { uv_add_entry(entries, g, e, acc); });
+    if (threadIdx.x == 0) {
+        float* out = partials + ((long)b * n_chunks + c) * 3;
+        out[0] = sum[0]; out[1] = sum[1]; out[2] = sum[2];
     }
 }
 
@@ -220,6 +212,7 @@ __global__ void __launch_bounds__(256) k_uv_adjoint_rows(const int32_t* __restri
                                                          int long_row, const float* __restrict__ partials,
                                                          int n_chunks, const float* __restrict__ grad_textures,
                                                          long n_texels, float* __restrict__ grad_image, int n_pixels) {
+    const d3m::LongRows longs = {nullptr, long_rows, long_chunk_ptr, n_chunks, n_long, long_row};
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     const int sub = (int)(t % LPR);
     const int p = (int)min(t / LPR, (long)n_pixels);          // (lanes past the last row walk an empty row: no early exit
@@ -227,28 +220,11 @@ __global__ void __launch_bounds__(256) k_uv_adjoint_rows(const int32_t* __restri
     const bool valid = p < n_pixels;
     const int start = valid ? row_ptr[p] : 0, end = valid ? row_ptr[p + 1] : 0;
     float acc[3] = {0, 0, 0};
-    if (end - start > long_row && n_long > 0) {
-        if (sub == 0) {
-            int lo = 0, hi = n_long - 1;                       // long_rows is ascending and holds p
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (long_rows[mid] < p) lo = mid + 1; else hi = mid;
-            }
-            const float* part = partials + (long)b * n_chunks * 3;
-            for (int c = long_chunk_ptr[lo]; c < long_chunk_ptr[lo + 1]; c++) {
-#pragma unroll
-                for (int k = 0; k < 3; k++) acc[k] += part[(long)c * 3 + k];
-            }
-        }
+    if (d3m::rg_is_long(longs, end - start)) {
+        if (sub == 0) d3m::rg_add_chunk_sums(longs, d3m::rg_find_long(longs, p), partials + (long)b * n_chunks * 3, acc);
     } else {
         const float* g = grad_textures + (long)b * n_texels * 3;
-        for (int e = start + sub; e < end; e += LPR) {
-            const int2 en = entries[e];
-            const float w = __int_as_float(en.y);
-            const float* gt = g + (long)en.x * 3;
-#pragma unroll
-            for (int k = 0; k < 3; k++) acc[k] += w * gt[k];
-        }
+        for (int e = start + sub; e < end; e += LPR) uv_add_entry(entries, g, e, acc);
     }
 #pragma unroll
     for (int k = 0; k < 3; k++)

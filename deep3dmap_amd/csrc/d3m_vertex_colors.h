@@ -5,6 +5,7 @@
 // trilinear sample is the barycentric mix of the corner colours: the existing sampler renders smooth colour from it.
 #pragma once
 #include "d3m_aux.h"
+#include "d3m_row_gather.h"
 
 namespace d3m {
 
@@ -32,9 +33,9 @@ __global__ void __launch_bounds__(256) k_vertex_color_textures(const float* __re
 // 3 f + c in ascending order per vertex) --------------------------------------------------------------------------------
 // An item's term for channel k is t = sum over idx ascending of TFI_CUBE[idx][c] * grad_textures[b, f, idx, k], from 0.
 // A row of up to long_row items is ONE lane per (vertex, channel) adding its terms in item order.  A longer row (a fan
-// apex, a pole) is cut into chunks [start, end) of the item array: k_vertex_color_adjoint_chunks reduces each chunk in a
-// fixed order into partials [B, n_chunks, 3], and the row's lanes add its chunk sums in chunk order.  No float atomics.
-constexpr int VC_ADJ_BLOCK = 256;
+// apex, a pole) goes through the chunks of d3m_row_gather.h, which states the order: k_vertex_color_adjoint_chunks reduces
+// each chunk into partials [B, n_chunks, 3], and the row's lanes add its chunk sums.  No float atomics.
+constexpr int VC_ADJ_BLOCK = RG_BLOCK;
 
 __device__ __forceinline__ float vc_item_term(const float* __restrict__ g, int item, int k) {
     const int f = item / 3, c = item - 3 * f;
@@ -51,29 +52,16 @@ __global__ void __launch_bounds__(VC_ADJ_BLOCK) k_vertex_color_adjoint_chunks(co
                                                                               const float* __restrict__ grad_textures,
                                                                               long n_faces, float* __restrict__ partials) {
     const int ch = blockIdx.x, b = blockIdx.y;
-    const int2 range = chunks[ch];
     const float* g = grad_textures + (size_t)b * n_faces * 24;
-    float acc[3] = {0, 0, 0};
-    for (int e = range.x + (int)threadIdx.x; e < range.y; e += VC_ADJ_BLOCK) {
+    float sum[3];
+    rg_chunk_sum(chunks[ch], sum, [&](int e, float (&acc)[3]) {
         const int item = adj_items[e];
 #pragma unroll
         for (int k = 0; k < 3; k++) acc[k] += vc_item_term(g, item, k);
-    }
-    // fixed-order reduction: a butterfly inside each wave, then the waves' sums in wave order
-#pragma unroll
-    for (int k = 0; k < 3; k++)
-        for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
-    __shared__ float wave_sum[VC_ADJ_BLOCK / 64][3];
-    const int wave = threadIdx.x / 64;
-    if ((threadIdx.x & 63) == 0) {
-        wave_sum[wave][0] = acc[0]; wave_sum[wave][1] = acc[1]; wave_sum[wave][2] = acc[2];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float s = 0;
-#pragma unroll
-        for (int w = 0; w < VC_ADJ_BLOCK / 64; w++) s += wave_sum[w][threadIdx.x];
-        partials[((size_t)b * n_chunks + ch) * 3 + threadIdx.x] = s;
+    });
+    if (threadIdx.x == 0) {
+        float* out = partials + ((size_t)b * n_chunks + ch) * 3;
+        out[0] = sum[0]; out[1] = sum[1]; out[2] = sum[2];
     }
 }
 
@@ -87,25 +75,20 @@ __global__ void __launch_bounds__(256) k_vertex_color_adjoint_rows(const int32_t
                                                                    const float* __restrict__ partials, int n_chunks,
                                                                    const float* __restrict__ grad_textures,
                                                                    long n_faces, float* __restrict__ grad_colors, int V) {
+    const LongRows longs = {nullptr, long_rows, long_chunk_ptr, n_chunks, n_long, long_row};
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const int b = blockIdx.y;
     if (i >= (long)V * 3) return;
     const int v = (int)(i / 3), k = (int)(i - (long)v * 3);
     const int start = adj_offsets[v], end = adj_offsets[v + 1];
-    float acc = 0.0f;
-    if (end - start > long_row && n_long > 0) {
-        int lo = 0, hi = n_long - 1;                           // long_rows is ascending and holds v
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (long_rows[mid] < v) lo = mid + 1; else hi = mid;
-        }
-        const float* part = partials + (size_t)b * n_chunks * 3;
-        for (int c = long_chunk_ptr[lo]; c < long_chunk_ptr[lo + 1]; c++) acc += part[(size_t)c * 3 + k];
+    float acc[1] = {0.0f};
+    if (rg_is_long(longs, end - start)) {
+        rg_add_chunk_sums<1, 3>(longs, rg_find_long(longs, v), partials + (size_t)b * n_chunks * 3 + k, acc);
     } else {
         const float* g = grad_textures + (size_t)b * n_faces * 24;
-        for (int e = start; e < end; e++) acc += vc_item_term(g, adj_items[e], k);
+        for (int e = start; e < end; e++) acc[0] += vc_item_term(g, adj_items[e], k);
     }
-    grad_colors[(size_t)b * V * 3 + i] = acc;
+    grad_colors[(size_t)b * V * 3 + i] = acc[0];
 }
 
 }  // namespace d3m

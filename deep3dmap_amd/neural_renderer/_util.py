@@ -3,6 +3,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from .row_gather import csr_offsets
 
 _const_cache = {}
 
@@ -55,8 +56,7 @@ def vertex_adjacency(tri, num_vertices):
     if hit is None:
         flat = tri.reshape(-1).long()
         items = torch.argsort(flat, stable=True).to(torch.int32).contiguous()
-        offsets = torch.zeros(int(num_vertices) + 1, dtype=torch.int32, device=tri.device)
-        offsets[1:] = torch.cumsum(torch.bincount(flat, minlength=int(num_vertices)), 0).to(torch.int32)
+        offsets = csr_offsets(flat, int(num_vertices))[0].to(torch.int32)
         if len(_adjacency_cache) >= 16:
             _adjacency_cache.clear()
         hit = _adjacency_cache[key] = (offsets.contiguous(), items, tri)       # (the tensor itself: its address stays taken)

@@ -8,7 +8,7 @@ fit, value and gradient in one autograd node (`mesh_regularizer`, `MeshRegulariz
 A wing record (a, b, c, d) is an edge a < b with the third vertices of two of its faces; the sign of n1 makes a flat pair
 give cos = 1 whatever the faces' winding.  d3m_mesh_regularizer evaluates all three as gathers over the topology of the faces
 -- no float atomics, the same bits on every run.  The topology (unique edges as a neighbour CSR, the wing records, the wing
-CSR, chunk tables of the rows above LONG_ROW items) is built once per (faces tensor, version, V) with torch operators and kept
+CSR, the chunk tables of the rows above LONG_ROW items: row_gather.py) is built once per (faces tensor, version, V) with torch operators and kept
 in a bounded LRU cache of its own, like vertex_colors' adjacency."""
 import ctypes
 from collections import namedtuple
@@ -17,8 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .uv_textures import TransposeCache
-from .vertex_colors import CACHE_SIZE, CHUNK, LONG_ROW, _checked_faces, _faces_key, long_row_chunks
+from .row_gather import LONG_ROW, BuiltCache, checked_faces as _checked_faces, csr_offsets, long_row_chunks, tensor_key
 
 MAX_FACES_PER_EDGE = 16     # an edge of n faces gives n (n - 1) / 2 wing records
 
@@ -27,27 +26,15 @@ MeshTopology = namedtuple("MeshTopology", "edges nbr_offsets nbr_items wings win
 MeshTopology.__doc__ = """The faces of one mesh as d3m_mesh_regularizer reads them (all i32): edges [E,2] (a < b, sorted),
 the neighbour CSR nbr_offsets [V+1] / nbr_items [2E] (a vertex's distinct neighbours, ascending), wings [P,4] = (a, b, c, d)
 ordered by (edge, i, j), the wing CSR wing_offsets [V+1] / wing_items [4P] (item = 4 p + role, ascending per vertex), the
-chunk tables of either CSR's long rows (vertex_colors.long_row_chunks), and `c`: the d3m_mesh_topology that points at them."""
+chunk tables of either CSR's long rows (row_gather.long_row_chunks), and `c`: the d3m_mesh_topology that points at them."""
 
 
-class TopologyCache(TransposeCache):
-    """uv_textures.TransposeCache for mesh topologies: a bounded LRU whose entries also hold the caller's faces tensor;
-    handed out inside a stream capture an entry is registered with rasterize_ops._captured_refs, and a build inside a
-    capture raises."""
+class TopologyCache(BuiltCache):
+    """row_gather.BuiltCache for mesh topologies: an entry also holds the caller's faces tensor."""
     what = "mesh_regularizer: the faces' topology"
-
-    def __init__(self, size=CACHE_SIZE):
-        super().__init__(size)
 
 
 _cache = TopologyCache()
-
-
-def _csr(rows, num_rows):
-    counts = torch.bincount(rows, minlength=num_rows)
-    offsets = torch.zeros(num_rows + 1, dtype=torch.int64, device=rows.device)
-    offsets[1:] = torch.cumsum(counts, 0)
-    return offsets, counts
 
 
 def build_topology(faces, num_vertices):
@@ -71,7 +58,7 @@ def build_topology(faces, num_vertices):
     # neighbour CSR: both directions of every edge, sorted by (vertex, neighbour)
     directed = torch.sort(torch.cat([keys, eb * V + ea]))[0]
     nbr_rows, nbr_items = torch.div(directed, V, rounding_mode="floor"), directed % V
-    nbr_offsets, nbr_counts = _csr(nbr_rows, V)
+    nbr_offsets, nbr_counts = csr_offsets(nbr_rows, V)
     # wings: the sides of the faces that repeat no index, sorted by (edge, face)
     proper = (tri[:, 0] != tri[:, 1]) & (tri[:, 1] != tri[:, 2]) & (tri[:, 2] != tri[:, 0])
     keep = proper[:, None].expand(F, 3).reshape(-1)
@@ -93,7 +80,7 @@ def build_topology(faces, num_vertices):
     e_of = side_edge[i_side]
     wings = torch.stack([ea[e_of], eb[e_of], side_third[i_side], side_third[j_side]], 1).reshape(-1, 4)
     wing_items = torch.argsort(wings.reshape(-1), stable=True)   # item = 4 p + role; stable: ascending per vertex
-    wing_offsets, wing_counts = _csr(wings.reshape(-1), V)
+    wing_offsets, wing_counts = csr_offsets(wings.reshape(-1), V)
     nbr_tables = long_row_chunks(nbr_offsets, nbr_counts)
     wing_tables = long_row_chunks(wing_offsets, wing_counts)
     tensors = [torch.stack([ea, eb], 1).to(**i32).contiguous(), nbr_offsets.to(**i32), nbr_items.to(**i32).contiguous(),
@@ -109,7 +96,7 @@ def mesh_topology(faces, num_vertices, cache=None):
     at its current version, outside any stream capture); `cache`: the TopologyCache to keep it in (default: the module's)."""
     faces = _checked_faces(faces)
     cache = _cache if cache is None else cache
-    return cache.get(_faces_key(faces, num_vertices), lambda: build_topology(faces, num_vertices), holders=(faces,))
+    return cache.get(tensor_key(faces) + (int(num_vertices),), lambda: build_topology(faces, num_vertices), holders=(faces,))
 
 
 def _checked_weights(laplacian, edge, edge_target, normal):

@@ -5,23 +5,19 @@ The map image -> cubes is d3m_load_textures's sampling (obj_io.load_textures_fro
 Its adjoint is the transpose of that map, walked as a gather: a CSR with one row per image pixel whose entries are
 (texel, weight) in ascending texel order (d3m_uv_texture_taps + a stable sort by pixel, built once per layout and cached),
 reduced by d3m_uv_texture_adjoint in a fixed order -- no float atomics, the same bits on every run.  Texel 0 of every face
-samples pixel (0,0) with weight 1, so that row holds one entry per face: rows longer than LONG_ROW entries are cut into
-chunks of CHUNK entries, each reduced by a workgroup, and the chunk sums are added in chunk order.
+samples pixel (0,0) with weight 1, so that row holds one entry per face: rows longer than LONG_ROW entries go through the
+chunked reduction that row_gather.py describes.
 
 The layout (faces_uv, face mask, texture size, image size, wrapping, filter) is a constant: a gradient with respect to
 faces_uv raises NotImplementedError."""
-from collections import OrderedDict, namedtuple
+from collections import namedtuple
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _lib
-from . import obj_io, rasterize_ops
-
-LONG_ROW = 64           # rows with more entries go through the chunked reduction
-CHUNK = 1024            # entries per chunk (one workgroup of 256 lanes)
-CACHE_SIZE = 8          # layouts kept (least recently used goes)
+from . import obj_io
+from .row_gather import CACHE_SIZE, CHUNK, LONG_ROW, BuiltCache, csr_offsets, long_row_chunks, tensor_key  # noqa: F401 (the constants stay importable from here)
 
 Transpose = namedtuple("Transpose", "row_ptr entries chunks long_rows long_chunk_ptr lanes_per_row num_texels height width")
 Transpose.__doc__ = """The transpose of one layout's sampling map: row_ptr [H*W+1] i32, entries [nnz,2] i32 (texel, weight
@@ -41,53 +37,16 @@ def _wrapping_code(texture_wrapping):
 
 
 # ---- the transpose's cache --------------------------------------------------------------------------------------------
-class TransposeCache:
-    """Bounded LRU cache of transposes.  An entry also holds the caller's faces_uv and mask tensors: the key names them by
-    address and version, and holding them keeps those addresses taken.  A transpose handed out inside a stream capture is
-    registered with rasterize_ops._captured_refs, so the captured step that replays it keeps it alive after eviction
-    (graph.CapturedStep.capture claims it).  A build inside a capture raises: the warm-up step builds it."""
-
-    what = "textures_from_image: the uv layout's transpose"         # (names the payload in the capture error)
-
-    def __init__(self, size=CACHE_SIZE):
-        self.size = int(size)
-        self._items = OrderedDict()
-
-    def get(self, key, build, holders=()):
-        hit = self._items.get(key)
-        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-        if hit is None:
-            if capturing:
-                raise RuntimeError(f"{self.what} is not built yet and cannot be built "
-                                   "inside a stream capture (it synchronises); run the step once eagerly first "
-                                   "(graph.CapturedStep.capture's warm-up steps do)")
-            hit = (build(), tuple(holders))
-            self._items[key] = hit
-            while len(self._items) > self.size:
-                self._items.popitem(last=False)
-        else:
-            self._items.move_to_end(key)
-        if capturing:
-            rasterize_ops._captured_refs[id(hit[0])] = hit[0]
-        return hit[0]
-
-    def clear(self):
-        self._items.clear()
-
-    def __len__(self):
-        return len(self._items)
-
-    def __contains__(self, key):
-        return key in self._items
+class TransposeCache(BuiltCache):
+    """row_gather.BuiltCache for transposes: an entry also holds the caller's faces_uv and mask tensors."""
+    what = "textures_from_image: the uv layout's transpose"
 
 
 _cache = TransposeCache()
 
 
 def _layout_key(faces_uv, mask, texture_size, height, width, wrapping, use_bilinear):
-    def ident(t):
-        return None if t is None else (t.data_ptr(), t._version, tuple(t.shape), t.dtype, str(t.device))
-    return (ident(faces_uv), ident(mask), int(texture_size), int(height), int(width), int(wrapping), bool(use_bilinear))
+    return (tensor_key(faces_uv), tensor_key(mask), int(texture_size), int(height), int(width), int(wrapping), bool(use_bilinear))
 
 
 def build_transpose(faces_uv, mask32, texture_size, height, width, wrapping, use_bilinear):
@@ -104,30 +63,20 @@ def build_transpose(faces_uv, mask32, texture_size, height, width, wrapping, use
         _lib.ptr(pixel), _lib.ptr(weight), _lib.stream_ptr()), "d3m_uv_texture_taps")
     # stable: a pixel's entries keep ascending entry order = ascending (texel, tap); dropped entries (pixel H*W) sort last
     keys, order = torch.sort(pixel, stable=True)
-    counts = torch.bincount(keys.long(), minlength=n_pix + 1)[:n_pix]
-    row_ptr = torch.zeros(n_pix + 1, dtype=torch.int64, device=dev)
-    row_ptr[1:] = torch.cumsum(counts, 0)
+    row_ptr, counts = csr_offsets(keys.long(), n_pix + 1)
+    row_ptr, counts = row_ptr[:-1], counts[:-1]                 # (without the row of the dropped entries)
     nnz = int(row_ptr[-1])
     order = order[:nnz]
     entries = torch.stack([torch.div(order, taps, rounding_mode="floor").to(torch.int32),
                            weight[order].view(torch.int32)], 1).contiguous()
     # the long rows and their chunks (few: pixel (0,0) and whatever a layout piles up)
-    long_rows = torch.nonzero(counts > LONG_ROW).flatten()
-    starts = row_ptr[long_rows].cpu().numpy()
-    ends = row_ptr[long_rows + 1].cpu().numpy()
-    n_ch = (ends - starts + CHUNK - 1) // CHUNK
-    long_chunk_ptr = np.zeros(len(long_rows) + 1, np.int64)
-    long_chunk_ptr[1:] = np.cumsum(n_ch)
-    chunk_start = np.repeat(starts, n_ch) + CHUNK * (np.arange(int(long_chunk_ptr[-1])) - np.repeat(long_chunk_ptr[:-1], n_ch))
-    chunks = np.stack([chunk_start, np.minimum(chunk_start + CHUNK, np.repeat(ends, n_ch))], 1).astype(np.int32)
+    chunks, long_rows, long_chunk_ptr = long_row_chunks(row_ptr, counts)
     # a row's walk is a chain of dependent loads: split the typical row over a few lanes (fixed per layout)
     mean = nnz / max(1, int((counts > 0).sum()))
     lanes = 1
     while lanes < 16 and lanes * 4 < mean:
         lanes *= 2
-    return Transpose(row_ptr.to(torch.int32), entries, torch.from_numpy(chunks.reshape(-1, 2)).to(dev),
-                     long_rows.to(torch.int32).contiguous(), torch.from_numpy(long_chunk_ptr.astype(np.int32)).to(dev),
-                     lanes, n_texels, height, width)
+    return Transpose(row_ptr.to(torch.int32), entries, chunks, long_rows, long_chunk_ptr, lanes, n_texels, height, width)
 
 
 def uv_transpose(faces_uv, texture_size, height, width, texture_wrapping='REPEAT', use_bilinear=True, faces_mask=None):

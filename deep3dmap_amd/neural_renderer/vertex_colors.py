@@ -9,21 +9,17 @@ Gouraud-like colour through the sampler they have.
 The adjoint is a gather over the CSR adjacency of the faces (a vertex's items 3 f + c in ascending order: what
 d3m_vertex_gather walks), reduced by d3m_vertex_color_textures_backward in a fixed order -- no float atomics, the same bits
 on every run.  A hub vertex (a fan apex, a pole) must not make one lane walk thousands of items: rows longer than LONG_ROW
-items are cut into chunks of CHUNK items, each reduced by a workgroup, and the chunk sums are added in chunk order.  The
-adjacency is built once per (faces tensor, version, V) with torch operators -- where the indices are checked against V --
-and kept in a bounded LRU cache of its own."""
+items go through the chunked reduction that row_gather.py describes.  The adjacency is built once per (faces tensor,
+version, V) with torch operators -- where the indices are checked against V -- and kept in a bounded LRU cache of its own."""
 from collections import namedtuple
 
-import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _lib
-from .uv_textures import TransposeCache
-
-LONG_ROW = 64           # rows with more items go through the chunked reduction
-CHUNK = 1024            # items per chunk (one workgroup of 256 lanes)
-CACHE_SIZE = 8          # adjacencies kept (least recently used goes)
+# (the constants and long_row_chunks stay importable from here)
+from .row_gather import (CACHE_SIZE, CHUNK, LONG_ROW, BuiltCache, checked_faces as _checked_faces, csr_offsets,  # noqa: F401
+                         long_row_chunks, tensor_key)
 
 Adjacency = namedtuple("Adjacency", "offsets items tri chunks long_rows long_chunk_ptr num_vertices num_faces")
 Adjacency.__doc__ = """The faces of one mesh as the kernels read them: tri [F,3] i32, the CSR offsets [V+1] i32 and items [3F]
@@ -31,53 +27,29 @@ i32 (item = 3 f + c, ascending per vertex), chunks [C,2] i32 item ranges of the 
 long_chunk_ptr [L+1] i32."""
 
 
-class AdjacencyCache(TransposeCache):
-    """uv_textures.TransposeCache for adjacencies: a bounded LRU whose entries also hold the caller's faces tensor (the key
-    names it by address and version); handed out inside a stream capture an entry is registered with
-    rasterize_ops._captured_refs, and a build inside a capture raises."""
+class AdjacencyCache(BuiltCache):
+    """row_gather.BuiltCache for adjacencies: an entry also holds the caller's faces tensor."""
     what = "textures_from_vertex_colors: the faces' adjacency"
-
-    def __init__(self, size=CACHE_SIZE):
-        super().__init__(size)
 
 
 _cache = AdjacencyCache()
 
 
 def _faces_key(faces, num_vertices):
-    return (faces.data_ptr(), faces._version, tuple(faces.shape), faces.dtype, str(faces.device), int(num_vertices))
-
-
-def long_row_chunks(offsets, counts):
-    """(chunks [C,2] i32, long_rows [L] i32, long_chunk_ptr [L+1] i32) of a CSR (offsets [R+1] i64, counts [R]): the rows of
-    more than LONG_ROW items (few: hubs), ascending, each cut into item ranges [start, end) of CHUNK items in row order."""
-    dev = offsets.device
-    long_rows = torch.nonzero(counts > LONG_ROW).flatten()
-    starts = offsets[long_rows].cpu().numpy()
-    ends = offsets[long_rows + 1].cpu().numpy()
-    n_ch = (ends - starts + CHUNK - 1) // CHUNK
-    long_chunk_ptr = np.zeros(len(starts) + 1, np.int64)
-    long_chunk_ptr[1:] = np.cumsum(n_ch)
-    chunk_start = np.repeat(starts, n_ch) + CHUNK * (np.arange(int(long_chunk_ptr[-1])) - np.repeat(long_chunk_ptr[:-1], n_ch))
-    chunks = np.stack([chunk_start, np.minimum(chunk_start + CHUNK, np.repeat(ends, n_ch))], 1).astype(np.int32)
-    return (torch.from_numpy(chunks.reshape(-1, 2)).to(dev), long_rows.to(torch.int32).contiguous(),
-            torch.from_numpy(long_chunk_ptr.astype(np.int32)).to(dev))
+    return tensor_key(faces) + (int(num_vertices),)
 
 
 def build_adjacency(faces, num_vertices):
     """The Adjacency of faces [F,3] (int32 or int64, any device) over num_vertices vertices.  Raises ValueError for an
     index outside [0, num_vertices).  Synchronises (the range check, the long rows): never inside a capture."""
     V = int(num_vertices)
-    dev = faces.device
     flat = faces.reshape(-1).long()
     lo, hi = int(flat.min()), int(flat.max())
     if lo < 0 or hi >= V:
         raise ValueError(f"faces: vertex indices must be in [0, {V}) (found {lo if lo < 0 else hi})")
     # stable: a vertex's items keep ascending order
     items = torch.argsort(flat, stable=True).to(torch.int32).contiguous()
-    counts = torch.bincount(flat, minlength=V)
-    offsets = torch.zeros(V + 1, dtype=torch.int64, device=dev)
-    offsets[1:] = torch.cumsum(counts, 0)
+    offsets, counts = csr_offsets(flat, V)
     chunks, long_rows, long_chunk_ptr = long_row_chunks(offsets, counts)
     return Adjacency(offsets.to(torch.int32), items, faces.reshape(-1, 3).to(torch.int32).contiguous(),
                      chunks, long_rows, long_chunk_ptr, V, int(flat.numel() // 3))
@@ -122,14 +94,6 @@ class _VertexColorTextures(torch.autograd.Function):
     def backward(ctx, grad_out):
         grad_colors = vertex_color_adjoint(ctx.adjacency, grad_out)
         return (grad_colors if ctx.batched else grad_colors[0]), None, None
-
-
-def _checked_faces(faces):
-    if not torch.is_tensor(faces) or faces.dtype not in (torch.int32, torch.int64):
-        raise ValueError("faces must be an int32 or int64 tensor")
-    if not ((faces.dim() == 2 or (faces.dim() == 3 and faces.shape[0] == 1)) and faces.shape[-1] == 3 and faces.shape[-2] >= 1):
-        raise ValueError("faces must be [num_faces, 3] or [1, num_faces, 3]")
-    return faces
 
 
 def textures_from_vertex_colors(colors, faces, cache=None):

@@ -173,6 +173,40 @@ def test_dot_product_identity(bilinear):
         assert abs(lhs - rhs) <= 1e-6 * abs(lhs), lanes
 
 
+@pytest.fixture(scope="module")
+def hot_pixel_layout():
+    """2100 random faces on a 29 x 37 image, ts = 2, bilinear, REPEAT, no mask: texel 0 of every face samples pixel (0,0), a
+    row of three chunks.  The transpose, a cube gradient for two images and the per-entry terms float32(weight) * g[texel]
+    (one rounding: what the kernels add), computed once."""
+    from deep3dmap_amd.neural_renderer.uv_textures import uv_transpose
+    rng = np.random.default_rng(21)
+    F, H, W, ts, B = 2100, 29, 37, 2, 2
+    uv = _dev(_random_layout(rng, F))
+    T = uv_transpose(uv, ts, H, W, "REPEAT", True)
+    g = rng.standard_normal((B, F * ts ** 3, 3)).astype(np.float32)
+    entries = T.entries.cpu().numpy()
+    weight = np.ascontiguousarray(entries[:, 1]).view(np.float32)
+    terms = weight[:, None, None] * g[:, entries[:, 0], :].transpose(1, 0, 2)          # [nnz, B, 3]
+    return dict(T=T, uv=uv, g=g, terms=terms.reshape(-1, B * 3), B=B, H=H, W=W)
+
+
+@pytest.mark.parametrize("lanes", [1, 2, 4, 8, 16])
+def test_adjoint_has_the_bits_of_the_shared_order(hot_pixel_layout, lanes):
+    """grad_image bit for bit against the numpy replay of the order csrc/d3m_row_gather.h states (tests/
+    row_gather_replay.py), for every walk of the short rows and the three chunks of pixel (0,0)."""
+    from deep3dmap_amd.neural_renderer import uv_textures
+    from row_gather_replay import replay_gather
+    c = hot_pixel_layout
+    T, B, H, W = c["T"], c["B"], c["H"], c["W"]
+    row_ptr = T.row_ptr.cpu().numpy()
+    assert int(row_ptr[1] - row_ptr[0]) > 2 * uv_textures.CHUNK and int(T.long_chunk_ptr[1]) >= 3
+    got = uv_textures.uv_texture_adjoint(T._replace(lanes_per_row=lanes), _dev(c["g"]).reshape(B, -1))
+    want = replay_gather(c["terms"], row_ptr, T.chunks.cpu().numpy(), T.long_rows.cpu().numpy(),
+                         T.long_chunk_ptr.cpu().numpy(), uv_textures.LONG_ROW, lanes_per_row=lanes)
+    want = torch.from_numpy(np.ascontiguousarray(want.reshape(H, W, B, 3).transpose(2, 0, 1, 3)))
+    assert torch.equal(_bits(got).cpu(), _bits(want))
+
+
 # ---- 4. determinism ----------------------------------------------------------------------------------------------------
 def test_image_gradient_is_bit_identical_eager_and_replayed():
     from deep3dmap_amd.graph import CapturedStep

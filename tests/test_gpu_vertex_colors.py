@@ -101,6 +101,34 @@ def test_irregular_mesh_forward_and_adjoint(irregular, batch, dtype):
     assert torch.equal(_bits(unused), torch.zeros_like(_bits(unused)))
 
 
+def test_adjoint_has_the_bits_of_the_shared_order(irregular):
+    """grad_colors bit for bit against the numpy replay of the order csrc/d3m_row_gather.h states (tests/
+    row_gather_replay.py): the rows of LONG_ROW items (the short path), LONG_ROW + 1 (one chunk) and 2 CHUNK + 1 (three
+    chunks, the last of one item) are where a moved addition shows.  An item's term is t = 0; t += C[idx][c] g[f, idx, k]
+    for idx ascending, in float32 (the products are exact)."""
+    from deep3dmap_amd.core.renderer_utils import _CUBE
+    from deep3dmap_amd.neural_renderer import vertex_colors as vc
+    from row_gather_replay import replay_gather
+    c = irregular
+    V, B = c["V"], 3
+    A = vc.vertex_adjacency(c["faces"].cuda(), V)
+    got = vc.vertex_color_adjoint(A, c["g"].cuda())
+    counts = (A.offsets[1:] - A.offsets[:-1]).cpu()
+    assert {int(counts[h]) for h in c["notes"]["hubs"]} == {vc.LONG_ROW, vc.LONG_ROW + 1, 2 * vc.CHUNK + 1}
+    assert A.long_rows.shape[0] == 2 and A.chunks.shape[0] == 4
+    items = A.items.cpu().numpy()
+    f, corner = items // 3, items % 3
+    C = np.array(_CUBE, np.float32)
+    g = c["g"].numpy().reshape(B, -1, 8, 3)
+    t = np.zeros((items.shape[0], B, 3), np.float32)
+    for idx in range(8):
+        t = t + C[idx, corner][:, None, None] * g[:, f, idx, :].transpose(1, 0, 2)
+    want = replay_gather(t.reshape(-1, B * 3), A.offsets.cpu().numpy(), A.chunks.cpu().numpy(), A.long_rows.cpu().numpy(),
+                         A.long_chunk_ptr.cpu().numpy(), vc.LONG_ROW)
+    want = torch.from_numpy(np.ascontiguousarray(want.reshape(V, B, 3).transpose(1, 0, 2)))
+    assert torch.equal(_bits(got).cpu(), _bits(want))
+
+
 # ---- 3. through the renderer --------------------------------------------------------------------------------------------
 def test_colour_gradient_through_a_render():
     from deep3dmap_amd import _lib, neural_renderer as nr, synthetic
