@@ -1,45 +1,34 @@
 """Mirror of deep3dmap/core/all3dmm/bfm_tools.py: `param2points_bfm`, the face vertices of Basel-face-model coefficients
 (models/frameworks/imgs2mesh.py:78 calls it right before Pt3dRenderer.sample), on nr.morphable_vertices."""
-from collections import OrderedDict
-
 import torch
 
+from ..neural_renderer.built_cache import BuiltCache, tensor_key
 from ..neural_renderer.morphable import morphable_vertices
 
 N_SHAPE, N_EXP, N_POSE = 199, 29, 7     # the columns of preds: identity | expression | pose
 CACHE_SIZE = 4
 
-_bases = OrderedDict()      # (w, w_exp) by address and version -> (w, w_exp, their concatenation): built once per pair
-_scales = OrderedDict()     # (sigma, sigma_exp) likewise -> (sigma, sigma_exp, sigma | 1 / (1000 sigma_exp))
+
+class _BasisCache(BuiltCache):
+    what = "param2points_bfm: the basis w | w_exp"
 
 
-def _key(t):
-    return (t.data_ptr(), t._version, tuple(t.shape), str(t.device))
+class _ScaleCache(BuiltCache):
+    what = "param2points_bfm: the scale sigma | 1 / (1000 sigma_exp)"
 
 
-def _once_per_pair(cache, a, b, what, make):
-    key = (_key(a), _key(b))
-    hit = cache.get(key)
-    if hit is None:
-        if a.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"param2points_bfm: {what} is built on the first call with these tensors, which must run "
-                               "outside a stream capture")
-        hit = (a, b, make())        # (holds the pair: the key names it by address)
-        cache[key] = hit
-        while len(cache) > CACHE_SIZE:
-            cache.popitem(last=False)
-    else:
-        cache.move_to_end(key)
-    return hit[2]
+# (w, w_exp) / (sigma, sigma_exp) by address and version -> what the node reads, built once per pair; an entry holds the pair
+_bases, _scales = _BasisCache(CACHE_SIZE), _ScaleCache(CACHE_SIZE)
 
 
 def _basis(w, w_exp):
-    return _once_per_pair(_bases, w, w_exp, "the basis w | w_exp", lambda: torch.cat([w, w_exp], 1).contiguous())
+    return _bases.get((tensor_key(w), tensor_key(w_exp)), lambda: torch.cat([w, w_exp], 1).contiguous(), holders=(w, w_exp))
 
 
 def _scale(sigma, sigma_exp):
-    return _once_per_pair(_scales, sigma, sigma_exp, "the scale sigma | 1 / (1000 sigma_exp)",
-                          lambda: torch.cat([sigma.reshape(-1), 1.0 / (1000.0 * sigma_exp.reshape(-1))]).contiguous())
+    return _scales.get((tensor_key(sigma), tensor_key(sigma_exp)),
+                       lambda: torch.cat([sigma.reshape(-1), 1.0 / (1000.0 * sigma_exp.reshape(-1))]).contiguous(),
+                       holders=(sigma, sigma_exp))
 
 
 def param2points_bfm(shape_param, exp_param, other_param, preds):
@@ -50,9 +39,9 @@ def param2points_bfm(shape_param, exp_param, other_param, preds):
         face_shape = w (preds[:, :199] sigma) + w_exp (preds[:, 199:228] / (1000 sigma_exp)) + mu_shape
 
     as ONE morphable_vertices node: basis w | w_exp and scale sigma | 1 / (1000 sigma_exp), each built once per pair of
-    tensors (their address and version) and kept, mean mu_shape.  The gradient reaches preds only: a model tensor that
-    requires grad raises NotImplementedError, as the node does.  The reference
-    hard-codes reshape(-1, 53215, 3); this uses V = w.shape[0] // 3, the same number for the Basel model."""
+    tensors (their address and version) and kept in a BuiltCache (a captured step keeps what it reads), mean mu_shape.
+    The gradient reaches preds only: a model tensor that requires grad raises NotImplementedError, as the node does.  The
+    reference hard-codes reshape(-1, 53215, 3); this uses V = w.shape[0] // 3, the same number for the Basel model."""
     w, w_exp = shape_param['w'], exp_param['w_exp']
     sigma, mu_shape, sigma_exp = shape_param['sigma'], shape_param['mu_shape'], other_param['sigma_exp']
     if w.dim() != 2 or w_exp.dim() != 2 or w.shape[0] != w_exp.shape[0]:

@@ -4,7 +4,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from ._util import deterministic, f32c, vertex_adjacency
+from ._util import deterministic, f32c
+from .row_gather import vertex_adjacency
 
 
 class _GatherFaces(torch.autograd.Function):
@@ -33,10 +34,10 @@ class _GatherFaces(torch.autograd.Function):
         if deterministic() and tri.shape[0] == 1:
             # d3m_set_deterministic: the same sums gathered per vertex in a fixed order (CSR adjacency of the index tensor)
             # instead of scattered with float atomics in arrival order
-            off, items = vertex_adjacency(tri, V)
+            adj = vertex_adjacency(tri, V)
             gv = torch.empty(B, V, 3, dtype=torch.float32, device=g.device)
-            _lib.check(_lib.lib().d3m_vertex_gather(_lib.ptr(g), None, _lib.ptr(off), _lib.ptr(items), _lib.ptr(gv), B, V, Ft,
-                                                    int(fill_back), None, _lib.stream_ptr()), "d3m_vertex_gather")
+            _lib.check(_lib.lib().d3m_vertex_gather(_lib.ptr(g), None, _lib.ptr(adj.offsets), _lib.ptr(adj.items), _lib.ptr(gv),
+                                                    B, V, Ft, int(fill_back), None, _lib.stream_ptr()), "d3m_vertex_gather")
             return gv, None, None
         gv = torch.zeros(B, V, 3, dtype=torch.float32, device=g.device)
         rc = _lib.lib().d3m_scatter_face_grads(_lib.ptr(g), _lib.ptr(tri), tri.shape[0], _lib.ptr(gv), B, V, Ft,

@@ -30,7 +30,7 @@ chunk tables of either CSR's long rows (row_gather.long_row_chunks), and `c`: th
 
 
 class TopologyCache(BuiltCache):
-    """row_gather.BuiltCache for mesh topologies: an entry also holds the caller's faces tensor."""
+    """BuiltCache for mesh topologies: an entry also holds the caller's faces tensor."""
     what = "mesh_regularizer: the faces' topology"
 
 

@@ -12,15 +12,17 @@ VERTICES_PER_CHUNK * p + lane, then every VERTICES_PER_CHUNK * parts further, in
 wave are added as a butterfly, the four waves in wave order; a second launch adds a set's partials in ascending p, then the
 landmark terms in ascending l, and applies the Euler adjoint, FINISH_SETS sets per workgroup.  The landmark gradients reach
 grad_vertices in ascending l (with shared vertices: summed over the sets in ascending order first), so repeated indices are
-neither a race nor an order left open.  Nothing is cached but the range check of a landmark tensor, and nothing synchronises
-after it: the node can be captured once its landmark tensor has been seen."""
-from collections import OrderedDict, namedtuple
+neither a race nor an order left open.  The one thing cached is a landmark tensor's range-checked int32 form, in a
+built_cache.BuiltCache (so a captured step keeps the form it reads), and nothing synchronises after that check: the node can
+be captured once its landmark tensor has been seen."""
+from collections import namedtuple
 
 import torch
 import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
+from .built_cache import BuiltCache, tensor_key
 
 # the constants of csrc/d3m_pose.h that fix the summation tree
 VERTICES_PER_CHUNK = 256        # lanes of a workgroup, one vertex each per stride (PS_BLOCK)
@@ -33,7 +35,13 @@ CACHE_SIZE = 8
 
 PosedPoints = namedtuple("PosedPoints", ["posed", "uv", "landmarks"])
 
-_checked_landmarks = OrderedDict()      # (index tensor by address and version, V) -> (the tensor, its int32 form)
+
+class LandmarkCache(BuiltCache):
+    """BuiltCache of range-checked landmark tensors: the payload is the int32 form the kernels read, the holder the tensor."""
+    what = "pose_vertices: the landmark tensor's range check (its int32 form)"
+
+
+_checked_landmarks = LandmarkCache(CACHE_SIZE)
 
 
 def num_parts(num_vertices):
@@ -104,23 +112,12 @@ def _landmark_vector(landmarks, what="landmarks"):
 def _landmarks_in_range(landmarks, num_vertices):
     """The int32 form of a landmark tensor whose entries lie in [0, V): looked at once per (tensor, V), by address and
     version, and the only step of the node that reads device memory on the host."""
-    key = (landmarks.data_ptr(), landmarks._version, landmarks.numel(), str(landmarks.dtype), str(landmarks.device),
-           int(num_vertices))
-    hit = _checked_landmarks.get(key)
-    if hit is None:
-        if landmarks.is_cuda and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("pose_vertices: a landmark tensor is range-checked on the first call with it, which must run "
-                               "outside a stream capture")
+    def check():
         lo, hi = int(landmarks.min()), int(landmarks.max())
         if lo < 0 or hi >= num_vertices:
             raise ValueError(f"landmarks must lie in [0, {num_vertices}) (found {lo} to {hi})")
-        hit = (landmarks, landmarks.detach().to(torch.int32).contiguous())      # (holds the tensor: the key names it by address)
-        _checked_landmarks[key] = hit
-        while len(_checked_landmarks) > CACHE_SIZE:
-            _checked_landmarks.popitem(last=False)
-    else:
-        _checked_landmarks.move_to_end(key)
-    return hit[1]
+        return landmarks.detach().to(torch.int32).contiguous()
+    return _checked_landmarks.get(tensor_key(landmarks) + (int(num_vertices),), check, holders=(landmarks,))
 
 
 def _positive_or_none(value, name):

@@ -12,7 +12,8 @@ import torch.nn as nn
 
 from .. import _lib
 from . import rasterize_ops as ops
-from ._util import const_tensor, deterministic as _deterministic, f32c, vertex_adjacency
+from ._util import const_tensor, deterministic as _deterministic, f32c
+from .row_gather import vertex_adjacency
 
 DEFAULT_IMAGE_SIZE = 256
 DEFAULT_ANTI_ALIASING = True
@@ -544,6 +545,7 @@ class _LitState:
     need_lp: tuple = (False,) * 5           # which of them want a gradient (autograd inputs of the node)
     need_mesh: bool = False                 # the mesh (vertices or screen vertices) wants a gradient
     need_cp: tuple = (False,) * 6           # which of the camera's parameters want one (cameras.camera_inputs order)
+    adjacency: Any = None                   # det with a gradient for the mesh: the index tensor's row_gather.Adjacency
 
 
 # _backward_buffers: the vertex accumulators, the texture / light gradients of batch B and where each view group's gathered
@@ -745,11 +747,12 @@ class _RasterizeLit(torch.autograd.Function):
                        for lo, hi in groups]
         cur = torch.cuda.current_stream()
         det = need_grad and _deterministic()
+        adjacency = None
         if det:
             _RasterizeLit._deterministic_supported(G, tri, vertices, ts, 0.0 if _host_zero(idr) else 1.0,
                                                    ctx.needs_input_grad[1], light_per_view)
-            if need_geom:
-                vertex_adjacency(tri, V)            # (built here, outside any capture of the backward pass)
+            if need_geom:       # (both of backward's gathers: need_vert implies it)
+                adjacency = vertex_adjacency(tri, V)
         # (LitFitManual: every kernel on the caller's stream -- the step is cut BETWEEN kernels of one stream)
         manual = isinstance(ctx, _ManualContext)
         serial = G == 1 and (det or manual or _serial_branches(B, Ft, S))
@@ -788,7 +791,7 @@ class _RasterizeLit(torch.autograd.Function):
                        # (whether the registered objective brought its normaliser or the node took sum(mask):
                        #  multiview_fit_loss only rides on the node's result when it is asked for the same one)
                        hint_mask_sum_given=hinted and mask_sum_given, dlight=dlight, need_lp=need_lp,
-                       need_mesh=need_mesh, need_cp=need_cp)
+                       need_mesh=need_mesh, need_cp=need_cp, adjacency=adjacency)
         # THE STEP'S FIRST LAUNCH (d3m_lit_front): the camera transform (with its look_at basis), the per-face light and
         # every clear the operators below would otherwise each launch for themselves -- the forward workspace's counters (or
         # z-buffer), the plan's, the objective's arrival tickets, the lines' extents -- and, for a caller that runs backward
@@ -1085,19 +1088,18 @@ class _RasterizeLit(torch.autograd.Function):
                                            vertex_target=None if det else target, visibility=vis[k], unscaled=unscaled,
                                            edge_plan=m["edge_plan"][k])
                     if det:     # K4's and K6's per-face arrays -> the screen-space gradient, per vertex in a fixed order
-                        adj_off, adj_items = vertex_adjacency(tri, V)
-                        _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k4), _lib.ptr(det_k6), _lib.ptr(adj_off), _lib.ptr(adj_items),
-                                                       _lib.ptr(grad_sv), B, V, Ft, int(fill_back), _lib.ptr(vis[k]),
-                                                       _lib.stream_ptr()), "d3m_vertex_gather")
+                        _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k4), _lib.ptr(det_k6), _lib.ptr(st.adjacency.offsets),
+                                                       _lib.ptr(st.adjacency.items), _lib.ptr(grad_sv), B, V, Ft,
+                                                       int(fill_back), _lib.ptr(vis[k]), _lib.stream_ptr()),
+                                   "d3m_vertex_gather")
         if G > 1:
             yield "textures"
         def light_to_vertices(grad_light):
             # the light gradient -> world-space vertices through the face normals
             if det:     # the views' gradients summed in view order (torch's reduction), the adjoint gathered per vertex
                 total = det_gl.sum(0)           # (one shared mesh, one light: _deterministic_supported)
-                adj_off, adj_items = vertex_adjacency(tri, V)
-                head = (_lib.ptr(vertices), _lib.ptr(tri), _lib.ptr(adj_off), _lib.ptr(adj_items), _lib.ptr(total),
-                        _lib.ptr(grad_vertices))
+                head = (_lib.ptr(vertices), _lib.ptr(tri), _lib.ptr(st.adjacency.offsets), _lib.ptr(st.adjacency.items),
+                        _lib.ptr(total), _lib.ptr(grad_vertices))
                 if dlight is None:
                     _lib.check(L.d3m_face_light_backward_gather(*head, *by_value, V, Ft, int(fill_back), _lib.stream_ptr()),
                                "d3m_face_light_backward_gather")
@@ -1214,7 +1216,7 @@ class _RasterizeLit(torch.autograd.Function):
 # the camera (+ what its structs point into), the pass's maps and backward's accumulator, zeroed by forward (pre; one use)
 _MeshModesState = dataclasses.make_dataclass("_MeshModesState", (
     "aa eps fill_back ra rd det camera keep faces face_index_map weight_map depth_map alpha_map visibility plan pre need_mesh "
-    "need_cp").split(),
+    "need_cp adjacency").split(),
     eq=False)
 
 
@@ -1302,12 +1304,12 @@ class _RasterizeMeshModes(torch.autograd.Function):
                 _lib.check(L.d3m_edge_plan(_lib.ptr(faces), _lib.ptr(fi), _lib.ptr(vis), _lib.ptr(plan), plan.numel(), B, Fp, S,
                                            flags_plan, _lib.stream_ptr()), "d3m_edge_plan")
         det = bool(need_grad) and _deterministic()
-        if det and (return_alpha != return_depth) and tri.shape[0] == 1:
-            vertex_adjacency(tri, V)            # (the deterministic backward pass's CSR adjacency: built outside any capture of it)
+        # (the deterministic backward pass's CSR adjacency: one shared topology, silhouettes alone or depth alone)
+        adjacency = vertex_adjacency(tri, V) if (det and (return_alpha != return_depth) and tri.shape[0] == 1) else None
         ctx.state = _MeshModesState(aa=bool(anti_aliasing), eps=float(eps), fill_back=bool(fill_back), ra=bool(return_alpha), rd=bool(return_depth), det=det,
                                     camera=camera, keep=(cam_keep, basis_keep), faces=faces, face_index_map=fi,
                                     weight_map=wm, depth_map=dm, alpha_map=alpha_map, visibility=vis, plan=plan, pre=pre,
-                                    need_mesh=bool(ctx.needs_input_grad[0]), need_cp=need_cp)
+                                    need_mesh=bool(ctx.needs_input_grad[0]), need_cp=need_cp, adjacency=adjacency)
         ctx.save_for_backward(vertices, tri)
         empty = torch.tensor([])
         return (alpha if return_alpha else empty, depth if return_depth else empty)
@@ -1345,9 +1347,9 @@ class _RasterizeMeshModes(torch.autograd.Function):
                 _lib.zero_raw([_lib.tensor_range(det_k4)])
                 ops.backward_pixel_map(faces, fi, None, alpha_map, None, None, det_k4, S, eps, False, True,
                                        visibility=vis, unscaled=unscaled, edge_plan=plan)
-                adj_off, adj_items = vertex_adjacency(tri, V)
-                _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k4), None, _lib.ptr(adj_off), _lib.ptr(adj_items), _lib.ptr(grad_sv),
-                                               B, V, Ft, int(fill_back), _lib.ptr(vis), _lib.stream_ptr()), "d3m_vertex_gather")
+                _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k4), None, _lib.ptr(st.adjacency.offsets),
+                                               _lib.ptr(st.adjacency.items), _lib.ptr(grad_sv), B, V, Ft, int(fill_back),
+                                               _lib.ptr(vis), _lib.stream_ptr()), "d3m_vertex_gather")
             else:
                 ops.backward_pixel_map(faces, fi, None, alpha_map, None, None, None, S, eps, False, True, vertex_target=target,
                                        visibility=vis, unscaled=unscaled, edge_plan=plan)
@@ -1375,9 +1377,9 @@ class _RasterizeMeshModes(torch.autograd.Function):
             det_k6 = torch.empty(B, Fp, 3, 3, dtype=torch.float32, device=dev)
             _lib.zero_raw([_lib.tensor_range(det_k6)])
             ops.backward_depth_map(faces, dm, fi, const_tensor((0.0,), dev), wm, g_depth_map, det_k6, S)
-            adj_off, adj_items = vertex_adjacency(tri, V)
-            _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k6), None, _lib.ptr(adj_off), _lib.ptr(adj_items), _lib.ptr(grad_sv),
-                                           B, V, Ft, int(fill_back), _lib.ptr(vis), _lib.stream_ptr()), "d3m_vertex_gather")
+            _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k6), None, _lib.ptr(st.adjacency.offsets),
+                                           _lib.ptr(st.adjacency.items), _lib.ptr(grad_sv), B, V, Ft, int(fill_back),
+                                           _lib.ptr(vis), _lib.stream_ptr()), "d3m_vertex_gather")
         elif rd and not ra:
             if aa:
                 _lib.check(L.d3m_output_epilogue_backward(None, None, _lib.ptr(f32c(g_depth)), None, None, _lib.ptr(g_depth_map),

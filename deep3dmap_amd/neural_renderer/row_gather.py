@@ -1,20 +1,21 @@
 """The host side of the long-row CSR gather that the fixed-order adjoints share (csrc/d3m_row_gather.h states the format and
 the order of the sums once): uv_textures (the transpose of a layout), vertex_colors (the adjacency of the faces) and
-mesh_regularizers (the neighbour and the wing CSR) build their CSRs, their long-row tables and their caches with this.
+mesh_regularizers (the neighbour and the wing CSR) build their CSRs, their long-row tables and their caches with this.  The
+adjacency of the faces itself lives here too: vertex_colors and the deterministic mode's per-vertex gathers (rasterize.py,
+mesh_ops.py) walk the same one.
 
 A row of up to LONG_ROW items is summed by its own lane(s) in item order.  A longer row (a hub) must not make one lane walk
 thousands of items: it is cut into chunks of CHUNK items, each reduced by a workgroup in a fixed order, and the chunk sums are
 added in chunk order -- no float atomics, the same bits on every run."""
-from collections import OrderedDict
+from collections import namedtuple
 
 import numpy as np
 import torch
 
-from . import rasterize_ops
+from .built_cache import CACHE_SIZE, BuiltCache, tensor_key  # noqa: F401 (they stay importable from here)
 
 LONG_ROW = 64           # rows with more items go through the chunked reduction
 CHUNK = 1024            # items per chunk (one workgroup of 256 lanes)
-CACHE_SIZE = 8          # built structures kept per cache (least recently used goes)
 
 
 def csr_offsets(rows, num_rows):
@@ -42,12 +43,6 @@ def long_row_chunks(offsets, counts):
             torch.from_numpy(long_chunk_ptr.astype(np.int32)).to(dev))
 
 
-def tensor_key(t):
-    """What names a tensor in a cache key: its address, version, shape, dtype and device (None for None).  An entry that
-    holds the tensor keeps the address taken."""
-    return None if t is None else (t.data_ptr(), t._version, tuple(t.shape), t.dtype, str(t.device))
-
-
 def checked_faces(faces):
     if not torch.is_tensor(faces) or faces.dtype not in (torch.int32, torch.int64):
         raise ValueError("faces must be an int32 or int64 tensor")
@@ -56,41 +51,42 @@ def checked_faces(faces):
     return faces
 
 
-class BuiltCache:
-    """Bounded LRU cache of structures built from the caller's tensors.  An entry also holds those tensors (`holders`): the
-    key names them by address and version, and holding them keeps those addresses taken.  An entry handed out inside a
-    stream capture is registered with rasterize_ops._captured_refs, so the captured step that replays it keeps it alive
-    after eviction (graph.CapturedStep.capture claims it).  A build inside a capture raises: the warm-up step builds it."""
+Adjacency = namedtuple("Adjacency", "offsets items tri chunks long_rows long_chunk_ptr num_vertices num_faces")
+Adjacency.__doc__ = """The faces of one mesh as the kernels read them: tri [F,3] i32, the CSR offsets [V+1] i32 and items [3F]
+i32 (item = 3 f + c, ascending per vertex: what d3m_vertex_gather walks), chunks [C,2] i32 item ranges of the long rows,
+long_rows [L] i32 (ascending) and long_chunk_ptr [L+1] i32."""
 
-    what = "the cached structure"           # (names the payload in the capture error; a subclass says what it keeps)
 
-    def __init__(self, size=CACHE_SIZE):
-        self.size = int(size)
-        self._items = OrderedDict()
+class AdjacencyCache(BuiltCache):
+    """BuiltCache for adjacencies: an entry also holds the caller's faces tensor."""
+    what = "the faces' adjacency (textures_from_vertex_colors, the deterministic mode's per-vertex gathers)"
 
-    def get(self, key, build, holders=()):
-        hit = self._items.get(key)
-        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-        if hit is None:
-            if capturing:
-                raise RuntimeError(f"{self.what} is not built yet and cannot be built "
-                                   "inside a stream capture (it synchronises); run the step once eagerly first "
-                                   "(graph.CapturedStep.capture's warm-up steps do)")
-            hit = (build(), tuple(holders))
-            self._items[key] = hit
-            while len(self._items) > self.size:
-                self._items.popitem(last=False)
-        else:
-            self._items.move_to_end(key)
-        if capturing:
-            rasterize_ops._captured_refs[id(hit[0])] = hit[0]
-        return hit[0]
 
-    def clear(self):
-        self._items.clear()
+_cache = AdjacencyCache()
 
-    def __len__(self):
-        return len(self._items)
 
-    def __contains__(self, key):
-        return key in self._items
+def _faces_key(faces, num_vertices):
+    return tensor_key(faces) + (int(num_vertices),)
+
+
+def build_adjacency(faces, num_vertices):
+    """The Adjacency of faces [F,3] or [1,F,3] (int32 or int64, any device) over num_vertices vertices.  Raises ValueError
+    for an index outside [0, num_vertices).  Synchronises (the range check, the long rows): never inside a capture."""
+    V = int(num_vertices)
+    flat = faces.reshape(-1).long()
+    lo, hi = int(flat.min()), int(flat.max())
+    if lo < 0 or hi >= V:
+        raise ValueError(f"faces: vertex indices must be in [0, {V}) (found {lo if lo < 0 else hi})")
+    # stable: a vertex's items keep ascending order
+    items = torch.argsort(flat, stable=True).to(torch.int32).contiguous()
+    offsets, counts = csr_offsets(flat, V)
+    chunks, long_rows, long_chunk_ptr = long_row_chunks(offsets, counts)
+    return Adjacency(offsets.to(torch.int32), items, faces.reshape(-1, 3).to(torch.int32).contiguous(),
+                     chunks, long_rows, long_chunk_ptr, V, int(flat.numel() // 3))
+
+
+def vertex_adjacency(faces, num_vertices, cache=None):
+    """The cached Adjacency of a faces tensor (built on the first call with this tensor at its current version, outside
+    any stream capture); `cache`: the AdjacencyCache to keep it in (default: the module's)."""
+    cache = _cache if cache is None else cache
+    return cache.get(_faces_key(faces, num_vertices), lambda: build_adjacency(faces, num_vertices), holders=(faces,))

@@ -38,7 +38,7 @@ def _wrapping_code(texture_wrapping):
 
 # ---- the transpose's cache --------------------------------------------------------------------------------------------
 class TransposeCache(BuiltCache):
-    """row_gather.BuiltCache for transposes: an entry also holds the caller's faces_uv and mask tensors."""
+    """BuiltCache for transposes: an entry also holds the caller's faces_uv and mask tensors."""
     what = "textures_from_image: the uv layout's transpose"
 
 

@@ -10,55 +10,16 @@ The adjoint is a gather over the CSR adjacency of the faces (a vertex's items 3 
 d3m_vertex_gather walks), reduced by d3m_vertex_color_textures_backward in a fixed order -- no float atomics, the same bits
 on every run.  A hub vertex (a fan apex, a pole) must not make one lane walk thousands of items: rows longer than LONG_ROW
 items go through the chunked reduction that row_gather.py describes.  The adjacency is built once per (faces tensor,
-version, V) with torch operators -- where the indices are checked against V -- and kept in a bounded LRU cache of its own."""
-from collections import namedtuple
-
+version, V) with torch operators -- where the indices are checked against V -- and kept in row_gather's bounded LRU cache,
+the one the deterministic mode's per-vertex gathers read theirs from."""
 import torch
 import torch.nn as nn
 
 from .. import _lib
-# (the constants and long_row_chunks stay importable from here)
-from .row_gather import (CACHE_SIZE, CHUNK, LONG_ROW, BuiltCache, checked_faces as _checked_faces, csr_offsets,  # noqa: F401
-                         long_row_chunks, tensor_key)
-
-Adjacency = namedtuple("Adjacency", "offsets items tri chunks long_rows long_chunk_ptr num_vertices num_faces")
-Adjacency.__doc__ = """The faces of one mesh as the kernels read them: tri [F,3] i32, the CSR offsets [V+1] i32 and items [3F]
-i32 (item = 3 f + c, ascending per vertex), chunks [C,2] i32 item ranges of the long rows, long_rows [L] i32 (ascending) and
-long_chunk_ptr [L+1] i32."""
-
-
-class AdjacencyCache(BuiltCache):
-    """row_gather.BuiltCache for adjacencies: an entry also holds the caller's faces tensor."""
-    what = "textures_from_vertex_colors: the faces' adjacency"
-
-
-_cache = AdjacencyCache()
-
-
-def _faces_key(faces, num_vertices):
-    return tensor_key(faces) + (int(num_vertices),)
-
-
-def build_adjacency(faces, num_vertices):
-    """The Adjacency of faces [F,3] (int32 or int64, any device) over num_vertices vertices.  Raises ValueError for an
-    index outside [0, num_vertices).  Synchronises (the range check, the long rows): never inside a capture."""
-    V = int(num_vertices)
-    flat = faces.reshape(-1).long()
-    lo, hi = int(flat.min()), int(flat.max())
-    if lo < 0 or hi >= V:
-        raise ValueError(f"faces: vertex indices must be in [0, {V}) (found {lo if lo < 0 else hi})")
-    # stable: a vertex's items keep ascending order
-    items = torch.argsort(flat, stable=True).to(torch.int32).contiguous()
-    offsets, counts = csr_offsets(flat, V)
-    chunks, long_rows, long_chunk_ptr = long_row_chunks(offsets, counts)
-    return Adjacency(offsets.to(torch.int32), items, faces.reshape(-1, 3).to(torch.int32).contiguous(),
-                     chunks, long_rows, long_chunk_ptr, V, int(flat.numel() // 3))
-
-
-def vertex_adjacency(faces, num_vertices, cache=None):
-    """The cached Adjacency of a faces tensor (built on the first call with this tensor at its current version)."""
-    cache = _cache if cache is None else cache
-    return cache.get(_faces_key(faces, num_vertices), lambda: build_adjacency(faces, num_vertices), holders=(faces,))
+# (the adjacency, its cache and the constants stay importable from here)
+from .row_gather import (CACHE_SIZE, CHUNK, LONG_ROW, Adjacency, AdjacencyCache, BuiltCache, _cache, _faces_key,  # noqa: F401
+                         build_adjacency, checked_faces as _checked_faces, csr_offsets, long_row_chunks, tensor_key,
+                         vertex_adjacency)
 
 
 def vertex_color_adjoint(adjacency, grad_textures):

@@ -1,0 +1,276 @@
+"""The cache of structures built from a caller's tensors (neural_renderer/built_cache.py), host side, once for every cache
+the package has: the uv transpose, the faces' adjacency (as textures_from_vertex_colors reaches it and as the deterministic
+mode's per-vertex gathers do: one function, one cache), the mesh topology, pose_vertices' range-checked landmarks and
+param2points_bfm's basis and scale.  Bounded LRU at its default size, a hit builds nothing, eviction lets go of payload and
+holders, the key follows version, shape and V, and under a (monkey-patched) stream capture a hit is registered for the
+capturing step while a miss raises and names its structure.  Plus the adjacency itself against a from-scratch restatement."""
+import gc
+import weakref
+
+import numpy as np
+import pytest
+import torch
+
+from deep3dmap_amd import synthetic
+from deep3dmap_amd.core import bfm_tools
+from deep3dmap_amd.neural_renderer import (built_cache, mesh_regularizers as mr, pose, rasterize_ops, row_gather as rg,
+                                           uv_textures as uvt, vertex_colors as vc)
+
+
+class _Payload:
+    pass
+
+
+def _faces(*shape_prefix, dtype=torch.int64):
+    return torch.tensor([[0, 1, 2], [2, 1, 3]], dtype=dtype).reshape(*shape_prefix, 2, 3)
+
+
+class _Case:
+    """One cache: its class, the module-level instance, its default size, the words its capture error must carry, and (where
+    the structure can be built on CPU tensors) `use(cache, tensors, V)` -> the payload through the package's own function,
+    `tensors()` -> fresh caller's tensors, `read(payload)` -> the tensor the kernels read."""
+
+    def __init__(self, name, cls, module, attr, size, names, tensors=None, use=None, read=None, takes_v=False):
+        self.name, self.cls, self.module, self.attr, self.size, self.names = name, cls, module, attr, size, names
+        self.tensors, self.use, self.read, self.takes_v = tensors, use, read, takes_v
+
+    @property
+    def instance(self):
+        return getattr(self.module, self.attr)
+
+
+def _through_module_cache(module, attr, call):
+    """`use` of a function that reads its cache from the module: the cache under test stands in for the module's."""
+    def use(cache, tensors, V):
+        old = getattr(module, attr)
+        setattr(module, attr, cache)
+        try:
+            return call(tensors, V)
+        finally:
+            setattr(module, attr, old)
+    return use
+
+
+CASES = [
+    _Case("transpose", uvt.TransposeCache, uvt, "_cache", built_cache.CACHE_SIZE, "transpose.*capture"),
+    _Case("adjacency", vc.AdjacencyCache, vc, "_cache", built_cache.CACHE_SIZE, "adjacency.*capture",
+          tensors=lambda: (_faces(),), use=lambda cache, t, V: vc.vertex_adjacency(t[0], V, cache=cache),
+          read=lambda A: A.offsets, takes_v=True),
+    # ... as rasterize.py and mesh_ops.py reach it in the deterministic mode: the int32 index tensor [1,F,3] of a render node
+    _Case("deterministic_adjacency", rg.AdjacencyCache, rg, "_cache", built_cache.CACHE_SIZE, "adjacency.*capture",
+          tensors=lambda: (_faces(1, dtype=torch.int32),), use=lambda cache, t, V: rg.vertex_adjacency(t[0], V, cache=cache),
+          read=lambda A: A.items, takes_v=True),
+    _Case("topology", mr.TopologyCache, mr, "_cache", built_cache.CACHE_SIZE, "topology.*capture",
+          tensors=lambda: (_faces(),), use=lambda cache, t, V: mr.mesh_topology(t[0], V, cache=cache),
+          read=lambda T: T.nbr_offsets, takes_v=True),
+    _Case("landmarks", pose.LandmarkCache, pose, "_checked_landmarks", 8, "landmark.*capture",
+          tensors=lambda: (torch.tensor([0, 3, 3, 1]),),            # int64: the int32 form is the cache's alone
+          use=_through_module_cache(pose, "_checked_landmarks", lambda t, V: pose._landmarks_in_range(t[0], V)),
+          read=lambda lm: lm, takes_v=True),
+    _Case("basis", bfm_tools._BasisCache, bfm_tools, "_bases", 4, "basis.*capture",
+          tensors=lambda: (torch.rand(12, 5), torch.rand(12, 3)),
+          use=_through_module_cache(bfm_tools, "_bases", lambda t, V: bfm_tools._basis(*t)), read=lambda b: b),
+    _Case("scale", bfm_tools._ScaleCache, bfm_tools, "_scales", 4, "scale.*capture",
+          tensors=lambda: (torch.rand(5) + 1, torch.rand(3) + 1),
+          use=_through_module_cache(bfm_tools, "_scales", lambda t, V: bfm_tools._scale(*t)), read=lambda s: s),
+]
+BUILDERS = [c for c in CASES if c.use is not None]
+_id = lambda c: c.name
+
+
+def test_one_implementation_and_one_adjacency():
+    assert rg.BuiltCache is built_cache.BuiltCache and rg.tensor_key is built_cache.tensor_key
+    assert vc.CACHE_SIZE == uvt.CACHE_SIZE == rg.CACHE_SIZE == built_cache.CACHE_SIZE == 8
+    assert pose.CACHE_SIZE == 8 and bfm_tools.CACHE_SIZE == 4
+    assert all(issubclass(c.cls, built_cache.BuiltCache) for c in CASES)
+    # the adjacency is one function over one cache, wherever it is imported from; every other structure has its own cache
+    assert vc.vertex_adjacency is rg.vertex_adjacency and vc.build_adjacency is rg.build_adjacency
+    assert vc.AdjacencyCache is rg.AdjacencyCache and vc.Adjacency is rg.Adjacency and vc._cache is rg._cache
+    instances = {id(c.instance) for c in CASES}
+    assert len(instances) == len(CASES) - 1 and mr._cache is not vc._cache
+
+
+@pytest.mark.parametrize("case", CASES, ids=_id)
+def test_cache_is_bounded_lru(case):
+    assert case.cls().size == built_cache.CACHE_SIZE and case.instance.size == case.size
+    assert isinstance(case.instance, case.cls)
+    cache = case.cls(size=3)
+    builds = []
+
+    def builder(k):
+        def build():
+            builds.append(k)
+            return _Payload()
+        return build
+    first = cache.get("a", builder("a"))
+    for k in "bc":
+        cache.get(k, builder(k))
+    assert cache.get("a", builder("a")) is first            # a hit: no build, and "a" is now the most recent
+    cache.get("d", builder("d"))                            # evicts the least recently used: "b", not "a"
+    assert "a" in cache and "b" not in cache and "c" in cache and "d" in cache and len(cache) == 3
+    assert builds == ["a", "b", "c", "d"]
+    cache.get("b", builder("b"))
+    assert builds[-1] == "b" and "c" not in cache
+
+
+@pytest.mark.parametrize("case", BUILDERS, ids=_id)
+def test_eviction_drops_payload_and_holders(case):
+    cache = case.cls(size=3)
+    tensors = case.tensors()
+    held = [weakref.ref(t) for t in tensors]
+    payload = weakref.ref(case.read(case.use(cache, tensors, 4)))
+    assert len(cache) == 1
+    if case.takes_v:
+        assert vc._faces_key(tensors[0], 4) in cache
+    del tensors
+    gc.collect()
+    assert all(h() is not None for h in held) and payload() is not None    # the cache holds the tensors its key names
+    for k in "xyz":
+        cache.get(k, _Payload)
+    gc.collect()
+    assert len(cache) == 3 and all(h() is None for h in held) and payload() is None
+
+
+@pytest.mark.parametrize("case", BUILDERS, ids=_id)
+def test_cache_key(case):
+    cache = case.cls(size=8)
+    tensors = case.tensors()
+    first = case.use(cache, tensors, 4)
+    assert case.use(cache, tensors, 4) is first and len(cache) == 1
+    if case.takes_v:
+        assert case.use(cache, tensors, 5) is not first                 # another V: another structure
+    n = len(cache)
+    tensors[0].add_(0)                                                  # an in-place write: a new version
+    second = case.use(cache, tensors, 4)
+    assert second is not first and len(cache) == n + 1
+    # the same address and version under another shape: another structure
+    views = tuple(t[:, :1] if t.dim() == 3 else t[:t.shape[0] // 2] for t in tensors)
+    assert all(v.data_ptr() == t.data_ptr() and v._version == t._version for v, t in zip(views, tensors))
+    assert case.use(cache, views, 4) is not second and len(cache) == n + 2
+    assert built_cache.tensor_key(None) is None
+
+
+def test_cache_key_of_each_structure():
+    """... and what each structure's key and content showed where its cache was first tested."""
+    faces = _faces()
+    cache = vc.AdjacencyCache(size=2)
+    A = vc.vertex_adjacency(faces, 4, cache=cache)
+    faces[1, 2] = 0
+    B = vc.vertex_adjacency(faces, 4, cache=cache)
+    assert B is not A and B.offsets.tolist() == [0, 2, 4, 6, 6]
+    cache = mr.TopologyCache(size=2)
+    U = mr.mesh_topology(faces, 4, cache=cache)
+    assert U.edges.tolist() == [[0, 1], [0, 2], [1, 2]] and U.num_wings == 3
+    one = mr.mesh_topology(faces[None].int(), 4, cache=cache)            # [1,F,3], int32
+    assert one is not U and torch.equal(one.wings, U.wings)
+    uv = torch.rand(4, 3, 2)
+    mask = torch.ones(4, dtype=torch.bool)
+    k = uvt._layout_key(uv, mask, 4, 8, 8, 0, True)
+    assert uvt._layout_key(uv, mask, 4, 8, 8, 0, True) == k
+    assert uvt._layout_key(uv, None, 4, 8, 8, 0, True) != k
+    assert uvt._layout_key(uv, mask, 2, 8, 8, 0, True) != k
+    assert uvt._layout_key(uv, mask, 4, 8, 8, 0, False) != k
+    uv.add_(0)                                              # an in-place write is a new layout
+    assert uvt._layout_key(uv, mask, 4, 8, 8, 0, True) != k
+
+
+@pytest.mark.parametrize("case", CASES, ids=_id)
+def test_captured_step_keeps_its_structure_after_eviction(case, monkeypatch):
+    """Under a capture the cache registers what it hands out with rasterize_ops._captured_refs, which the capturing
+    CapturedStep takes (graph.CapturedStep.capture -> take_captured_refs); a build inside a capture raises and names the
+    structure that was missing."""
+    rasterize_ops.take_captured_refs()
+    cache = case.cls(size=2)
+    payload = _Payload()
+    alive = weakref.ref(payload)
+    cache.get("mesh", lambda: payload)                      # the warm-up step builds it
+    del payload
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    cache.get("mesh", lambda: pytest.fail("a hit must not build"))
+    with pytest.raises(RuntimeError, match=case.names):
+        cache.get("other", _Payload)
+    assert "other" not in cache
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
+    step_refs = rasterize_ops.take_captured_refs()          # what CapturedStep.capture keeps as _scratch_refs
+    for k in "xyz":
+        cache.get(k, _Payload)
+    assert "mesh" not in cache
+    gc.collect()
+    assert alive() is not None and alive() in step_refs
+    del step_refs
+    gc.collect()
+    assert alive() is None
+
+
+@pytest.mark.parametrize("case", BUILDERS, ids=_id)
+def test_the_package_functions_register_and_refuse_under_a_capture(case, monkeypatch):
+    """The same through the functions the nodes call, on CPU tensors: what the kernels read is what the step keeps."""
+    rasterize_ops.take_captured_refs()
+    cache = case.cls(size=2)
+    tensors = case.tensors()
+    built = case.use(cache, tensors, 4)
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    assert case.use(cache, tensors, 4) is built
+    with pytest.raises(RuntimeError, match=case.names):
+        case.use(cache, case.tensors(), 4)
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
+    refs = rasterize_ops.take_captured_refs()
+    assert len(refs) == 1 and refs[0] is built and len(cache) == 1
+
+
+def test_range_and_shape_checks_stay_in_front_of_the_caches():
+    with pytest.raises(ValueError, match=r"landmarks must lie in \[0, 3\)"):
+        pose._landmarks_in_range(torch.tensor([0, 3]), 3)
+    with pytest.raises(ValueError, match="landmarks must lie"):
+        pose._landmarks_in_range(torch.tensor([-1, 2]), 3)
+    lm = torch.tensor([0, 2, 2])
+    got = pose._landmarks_in_range(lm, 3)
+    assert got.dtype == torch.int32 and got.is_contiguous() and got.tolist() == [0, 2, 2]
+    assert pose._landmarks_in_range(lm, 3) is got
+    with pytest.raises(ValueError, match="indices"):
+        rg.vertex_adjacency(_faces(1, dtype=torch.int32), 3)            # (what failed inside bincount / cumsum before)
+    with pytest.raises(ValueError, match="indices"):
+        rg.vertex_adjacency(-_faces(1, dtype=torch.int32), 4)
+    w, w_exp, sigma, sigma_exp = torch.rand(12, 5), torch.rand(12, 3), torch.rand(5) + 1, torch.rand(3) + 1
+    basis, scale = bfm_tools._basis(w, w_exp), bfm_tools._scale(sigma, sigma_exp)
+    assert basis.is_contiguous() and torch.equal(basis, torch.cat([w, w_exp], 1)) and bfm_tools._basis(w, w_exp) is basis
+    assert torch.equal(scale, torch.cat([sigma, 1.0 / (1000.0 * sigma_exp)])) and bfm_tools._scale(sigma, sigma_exp) is scale
+    with pytest.raises(ValueError, match="same rows"):
+        bfm_tools.param2points_bfm({"w": w, "sigma": sigma, "mu_shape": torch.rand(12, 1)}, {"w_exp": torch.rand(9, 3)},
+                                   {"sigma_exp": sigma_exp}, torch.rand(2, 15))
+
+
+# ---- the adjacency against a from-scratch restatement ----------------------------------------------------------------------
+def _fan(num_faces):
+    """num_faces triangles around vertex 0: one hub row of num_faces items (beyond LONG_ROW: one chunk)."""
+    rim = np.arange(1, num_faces + 1)
+    return np.stack([np.zeros(num_faces, np.int64), rim, np.roll(rim, -1)], 1).astype(np.int32), num_faces + 1
+
+
+def _meshes():
+    out = {f"grid_mesh({n})": (synthetic.grid_mesh(n)[1], n * n) for n in (2, 9)}
+    out["fan(200)"] = _fan(200)
+    return out
+
+
+@pytest.mark.parametrize("name", list(_meshes()))
+def test_vertex_adjacency_equals_a_restatement(name):
+    """offsets [V+1] / items [3F] (item = 3 f + c, a vertex's items ascending) of the [1,F,3] int32 index tensor the render
+    nodes hand over, against numpy's bincount and stable argsort."""
+    tri_np, V = _meshes()[name]
+    tri = torch.from_numpy(np.ascontiguousarray(tri_np)).to(torch.int32)[None]
+    A = rg.vertex_adjacency(tri, V, cache=rg.AdjacencyCache(1))
+    flat = tri_np.reshape(-1).astype(np.int64)
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(flat, minlength=V))]).astype(np.int32)
+    items = np.argsort(flat, kind="stable").astype(np.int32)
+    assert A.offsets.dtype == torch.int32 and A.items.dtype == torch.int32
+    assert A.offsets.is_contiguous() and A.items.is_contiguous()
+    assert torch.equal(A.offsets, torch.from_numpy(offsets)) and torch.equal(A.items, torch.from_numpy(items))
+    assert (A.num_vertices, A.num_faces) == (V, tri_np.shape[0]) and torch.equal(A.tri, tri[0])
+    for v in (0, V // 2, V - 1):                            # item = 3 f + c names the corners that hold v, ascending
+        row = items[offsets[v]:offsets[v + 1]]
+        assert np.all(flat[row] == v) and np.all(np.diff(row) > 0)
+    n_long = int((np.diff(offsets) > rg.LONG_ROW).sum())
+    assert A.long_rows.numel() == n_long == (1 if name == "fan(200)" else 0) and A.chunks.shape[0] == n_long

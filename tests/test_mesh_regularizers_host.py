@@ -1,11 +1,9 @@
 """Mesh shape regularisers (neural_renderer/mesh_regularizers.py), host side: a plain-torch restatement of the three terms
 over edges and wing records this file builds with Python loops (tests/test_gpu_mesh_regularizers.py runs it in float64 as
 the reference and in float32 as the yardstick of the tolerance), known answers, the topology builder against the loop-built
-one, the topology cache, argument errors, and the entry points' D3M_ERR_INVALID."""
+one, argument errors, and the entry points' D3M_ERR_INVALID (the topology's cache: tests/test_built_cache_host.py)."""
 import ctypes
-import gc
 import math
-import weakref
 
 import numpy as np
 import pytest
@@ -287,81 +285,7 @@ def test_topology_errors_and_small_cases():
         build_topology(book, 19)
 
 
-# ---- 3. the cache ---------------------------------------------------------------------------------------------------------
-class _Payload:
-    pass
-
-
-def test_topology_cache_is_bounded_lru_and_drops_its_references():
-    from deep3dmap_amd.neural_renderer import mesh_regularizers as mr, vertex_colors as vc
-    cache = mr.TopologyCache(size=3)
-    assert mr.TopologyCache().size == vc.CACHE_SIZE and mr._cache.size == vc.CACHE_SIZE and mr._cache is not vc._cache
-    builds = []
-
-    def builder(k):
-        def build():
-            builds.append(k)
-            return _Payload()
-        return build
-    first = cache.get("a", builder("a"))
-    for k in "bc":
-        cache.get(k, builder(k))
-    assert cache.get("a", builder("a")) is first
-    cache.get("d", builder("d"))
-    assert "a" in cache and "b" not in cache and "c" in cache and "d" in cache and len(cache) == 3
-    assert builds == ["a", "b", "c", "d"]
-    faces = torch.tensor([[0, 1, 2]])
-    held = weakref.ref(faces)
-    payload = weakref.ref(mr.mesh_topology(faces, 3, cache=cache).nbr_offsets)
-    key = vc._faces_key(faces, 3)
-    assert key in cache
-    del faces
-    gc.collect()
-    assert held() is not None
-    for k in "xyz":
-        cache.get(k, builder(k))
-    gc.collect()
-    assert key not in cache and held() is None and payload() is None
-
-
-def test_topology_cache_key():
-    from deep3dmap_amd.neural_renderer import mesh_regularizers as mr
-    faces = torch.tensor([[0, 1, 2], [2, 1, 3]])
-    cache = mr.TopologyCache(size=2)
-    T = mr.mesh_topology(faces, 4, cache=cache)
-    assert mr.mesh_topology(faces, 4, cache=cache) is T
-    assert mr.mesh_topology(faces, 5, cache=cache) is not T
-    faces[1, 2] = 0                                                      # an in-place write: a new version
-    U = mr.mesh_topology(faces, 4, cache=cache)
-    assert U is not T and U.edges.tolist() == [[0, 1], [0, 2], [1, 2]] and U.num_wings == 3
-    one = mr.mesh_topology(faces[None].int(), 4, cache=cache)            # [1,F,3], int32
-    assert torch.equal(one.wings, U.wings)
-
-
-def test_captured_step_keeps_its_topology_after_eviction(monkeypatch):
-    from deep3dmap_amd.neural_renderer import rasterize_ops
-    from deep3dmap_amd.neural_renderer.mesh_regularizers import TopologyCache
-    rasterize_ops.take_captured_refs()
-    cache = TopologyCache(size=2)
-    payload = _Payload()
-    alive = weakref.ref(payload)
-    cache.get("mesh", lambda: payload)
-    del payload
-    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
-    cache.get("mesh", lambda: pytest.fail("a hit must not build"))
-    with pytest.raises(RuntimeError, match="topology.*capture"):
-        cache.get("other", _Payload)
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-    step_refs = rasterize_ops.take_captured_refs()
-    for k in "xyz":
-        cache.get(k, _Payload)
-    assert "mesh" not in cache
-    gc.collect()
-    assert alive() is not None and alive() in step_refs
-    del step_refs
-    gc.collect()
-    assert alive() is None
+# (3. the cache: tests/test_built_cache_host.py, once for every cache of the package)
 
 
 # ---- 4. argument errors (none needs a device) -----------------------------------------------------------------------------

@@ -1,9 +1,8 @@
 """Learnable uv images (neural_renderer/uv_textures.py), host side: a torch restatement of k_load_textures's sampling map
 (pinned bit for bit to the oracle on the golden vectors; tests/test_gpu_uv_textures.py uses it in float64 as the adjoint's
-reference), the hot-spot fact the adjoint is built around, argument errors, and the transpose cache."""
-import gc
+reference), the hot-spot fact the adjoint is built around, and argument errors (the transpose's cache:
+tests/test_built_cache_host.py)."""
 import os
-import weakref
 
 import numpy as np
 import pytest
@@ -220,68 +219,4 @@ def test_faces_uv_gradient_raises():
         textures_from_image(torch.rand(5, 6, 3), torch.rand(4, 3, 2, requires_grad=True))
 
 
-class _Payload:
-    pass
-
-
-def test_transpose_cache_is_bounded_lru():
-    from deep3dmap_amd.neural_renderer.uv_textures import TransposeCache
-    cache = TransposeCache(size=3)
-    builds = []
-
-    def builder(k):
-        def build():
-            builds.append(k)
-            return _Payload()
-        return build
-    first = cache.get("a", builder("a"))
-    for k in "bc":
-        cache.get(k, builder(k))
-    assert cache.get("a", builder("a")) is first           # a hit: no build, and "a" is now the most recent
-    cache.get("d", builder("d"))                           # evicts the least recently used: "b", not "a"
-    assert "a" in cache and "b" not in cache and "c" in cache and "d" in cache
-    assert len(cache) == 3
-    assert builds == ["a", "b", "c", "d"]
-    cache.get("b", builder("b"))
-    assert builds[-1] == "b" and "c" not in cache
-
-
-def test_transpose_cache_key_hits_for_the_same_layout():
-    from deep3dmap_amd.neural_renderer.uv_textures import _layout_key
-    uv = torch.rand(4, 3, 2)
-    mask = torch.ones(4, dtype=torch.bool)
-    k = _layout_key(uv, mask, 4, 8, 8, 0, True)
-    assert _layout_key(uv, mask, 4, 8, 8, 0, True) == k
-    assert _layout_key(uv, None, 4, 8, 8, 0, True) != k
-    assert _layout_key(uv, mask, 2, 8, 8, 0, True) != k
-    assert _layout_key(uv, mask, 4, 8, 8, 0, False) != k
-    uv.add_(0)                                              # an in-place write is a new layout
-    assert _layout_key(uv, mask, 4, 8, 8, 0, True) != k
-
-
-def test_captured_step_keeps_its_transpose_after_eviction(monkeypatch):
-    """Under a capture the cache registers what it hands out with rasterize_ops._captured_refs, which the capturing
-    CapturedStep takes (graph.CapturedStep.capture -> take_captured_refs); a build inside a capture raises."""
-    from deep3dmap_amd.neural_renderer import rasterize_ops
-    from deep3dmap_amd.neural_renderer.uv_textures import TransposeCache
-    rasterize_ops.take_captured_refs()
-    cache = TransposeCache(size=2)
-    payload = _Payload()
-    alive = weakref.ref(payload)
-    cache.get("layout", lambda: payload)                    # the warm-up step builds it
-    del payload
-    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
-    cache.get("layout", lambda: pytest.fail("a hit must not build"))
-    with pytest.raises(RuntimeError, match="capture"):
-        cache.get("other", _Payload)
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-    step_refs = rasterize_ops.take_captured_refs()          # what CapturedStep.capture keeps as _scratch_refs
-    for k in "xyz":
-        cache.get(k, _Payload)
-    assert "layout" not in cache
-    gc.collect()
-    assert alive() is not None and alive() in step_refs
-    del step_refs
-    gc.collect()
-    assert alive() is None
+# (the transpose cache: tests/test_built_cache_host.py, once for every cache of the package)

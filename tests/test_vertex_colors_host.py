@@ -1,9 +1,7 @@
 """Learnable per-vertex colours (neural_renderer/vertex_colors.py), host side: an element-wise torch restatement of the map
 colours -> cubes (pinned to this repo's vcolor_to_texture_cube and, bit for bit, to the grid mesh of get_textures_from_im;
 tests/test_gpu_vertex_colors.py uses it in float32 as the forward's reference and in float64 for the adjoint's), the CSR
-builder, argument errors, the adjacency cache, and VertexColors.from_textures."""
-import gc
-import weakref
+builder, argument errors, and VertexColors.from_textures (the adjacency's cache: tests/test_built_cache_host.py)."""
 
 import numpy as np
 import pytest
@@ -181,82 +179,7 @@ def test_argument_errors():
         nr.VertexColors.from_textures(torch.rand(2, 2, 2, 2, 3), faces, 5)
 
 
-# ---- 4. the cache -------------------------------------------------------------------------------------------------------
-class _Payload:
-    pass
-
-
-def test_adjacency_cache_is_bounded_lru_and_drops_its_references():
-    from deep3dmap_amd.neural_renderer import vertex_colors as vc
-    cache = vc.AdjacencyCache(size=3)
-    assert vc.AdjacencyCache().size == vc.CACHE_SIZE and vc._cache.size == vc.CACHE_SIZE
-    builds = []
-
-    def builder(k):
-        def build():
-            builds.append(k)
-            return _Payload()
-        return build
-    first = cache.get("a", builder("a"))
-    for k in "bc":
-        cache.get(k, builder(k))
-    assert cache.get("a", builder("a")) is first            # a hit: no build, and "a" is now the most recent
-    cache.get("d", builder("d"))                            # evicts the least recently used: "b", not "a"
-    assert "a" in cache and "b" not in cache and "c" in cache and "d" in cache and len(cache) == 3
-    assert builds == ["a", "b", "c", "d"]
-    # an evicted entry lets go of its payload and of the caller's tensor
-    faces = torch.tensor([[0, 1, 2]])
-    held = weakref.ref(faces)
-    payload = weakref.ref(vc.vertex_adjacency(faces, 3, cache=cache).offsets)
-    key = vc._faces_key(faces, 3)
-    assert key in cache
-    del faces
-    gc.collect()
-    assert held() is not None                               # the cache holds the tensor its key names
-    for k in "xyz":
-        cache.get(k, builder(k))
-    gc.collect()
-    assert key not in cache and held() is None and payload() is None
-
-
-def test_adjacency_cache_key():
-    from deep3dmap_amd.neural_renderer import vertex_colors as vc
-    faces = torch.tensor([[0, 1, 2], [2, 1, 3]])
-    cache = vc.AdjacencyCache(size=2)
-    A = vc.vertex_adjacency(faces, 4, cache=cache)
-    assert vc.vertex_adjacency(faces, 4, cache=cache) is A
-    assert vc.vertex_adjacency(faces, 5, cache=cache) is not A          # another V: another adjacency
-    faces[1, 2] = 0                                                      # an in-place write: a new version
-    B = vc.vertex_adjacency(faces, 4, cache=cache)
-    assert B is not A and B.offsets.tolist() == [0, 2, 4, 6, 6]
-
-
-def test_captured_step_keeps_its_adjacency_after_eviction(monkeypatch):
-    """Under a capture the cache registers what it hands out with rasterize_ops._captured_refs (graph.CapturedStep.capture
-    takes them); a build inside a capture raises and names the adjacency."""
-    from deep3dmap_amd.neural_renderer import rasterize_ops
-    from deep3dmap_amd.neural_renderer.vertex_colors import AdjacencyCache
-    rasterize_ops.take_captured_refs()
-    cache = AdjacencyCache(size=2)
-    payload = _Payload()
-    alive = weakref.ref(payload)
-    cache.get("mesh", lambda: payload)                      # the warm-up step builds it
-    del payload
-    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
-    cache.get("mesh", lambda: pytest.fail("a hit must not build"))
-    with pytest.raises(RuntimeError, match="adjacency.*capture"):
-        cache.get("other", _Payload)
-    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
-    step_refs = rasterize_ops.take_captured_refs()
-    for k in "xyz":
-        cache.get(k, _Payload)
-    assert "mesh" not in cache
-    gc.collect()
-    assert alive() is not None and alive() in step_refs
-    del step_refs
-    gc.collect()
-    assert alive() is None
+# (4. the cache: tests/test_built_cache_host.py, once for every cache of the package)
 
 
 # ---- 5. VertexColors.from_textures ----------------------------------------------------------------------------------------
