@@ -809,11 +809,20 @@ __global__ void __launch_bounds__(256) k_fit_loss_records(const float* __restric
 // Lanes per face in the gathered lit pass.  What is done once per face -- bounding box, inverse, the 24 + 9 DPP sums,
 // the stores -- is per-lane vector work shared by all the faces of a wave, so fewer lanes per face means fewer
 // instructions per face, at the price of more scan steps per lane (each a memory round trip).  Measured on the
-// headline step: 8 lanes 2.135 ms, 4 lanes 2.155 ms.
+// headline step: 8 lanes 2.135 ms, 4 lanes 2.155 ms; again with the owned-pixel scan (scan_owned_pixels, whose dense steps
+// leave the per-face work the larger share), three alternating runs each: 8 lanes 1.4591 / 1.4687 / 1.4879 ms, 4 lanes
+// 1.4631 / 1.4775 / 1.4734 -- the kernel by itself 170 against 164 us, the step no faster.  Eight stays.
 #ifndef D3M_LIT_LANES
 #define D3M_LIT_LANES 8
 #endif
 constexpr int LIT_LANES = D3M_LIT_LANES;
+// blocks of the gathered pass's launch over the visibility list (a fixed grid that strides over the list).  With the
+// owned-pixel scan, headline step: 2 048 blocks 1.4501 / 1.4563 / 1.4699 ms, 4 096 1.4544 / 1.4577 / 1.4690, 8 192
+// 1.4695 / 1.4613 / 1.4649 -- no difference beyond the spread.
+#ifndef D3M_LIT_LIST_BLOCKS
+#define D3M_LIT_LIST_BLOCKS 4096
+#endif
+constexpr unsigned LIT_LIST_BLOCKS = D3M_LIT_LIST_BLOCKS;
 constexpr int LIT_FACES_PER_BLOCK = 256 / LIT_LANES;
 __device__ __forceinline__ float lit_sum(float v) {       // over the LIT_LANES adjacent lanes of a face, in every one
     v += dpp_f32<0xB1>(v);      // quad_perm [1,0,3,2]
@@ -847,7 +856,8 @@ struct LitFaceArgs {
 
 // LANES adjacent lanes share a face: LIT_LANES (8) for ordinary meshes, a whole wave (64) for coarse ones, whose faces of
 // hundreds of pixels were ninety steps of dependent loads for each of eight lanes (722 triangles @512^2: 210 us of a 337 us
-// step).  The arithmetic per pixel and the order of a lane's sums are the same; the sum over the lanes is a tree either way.
+// step).  The arithmetic per pixel is the same; a lane takes the owned pixels of rank sub, sub + LANES, ... of each chunk of
+// the box (scan_owned_pixels), and the sum over the lanes is a tree either way.
 template <int LANES>
 __device__ __forceinline__ float lit_lanes_sum(float v) { return LANES == 64 ? wave_sum(v) : lit_sum(v); }
 template <int LANES>
@@ -913,37 +923,16 @@ __device__ __forceinline__ void lit_face_backward(const LitFaceArgs& a, long gi,
             dtmp[1] += -iy[l2] * rz[l2];
         }
     }
-    // what the epilogue needs, requested now: this lane's texel (sub) of the face's cube and the face's light
-    const int lrow = (lt.light_batch > 1 ? bn : 0) * Fp + fn;
-    const float li[3] = {lt.light[3 * (size_t)lrow], lt.light[3 * (size_t)lrow + 1], lt.light[3 * (size_t)lrow + 2]};
-    constexpr int TPL = LANES >= 8 ? 1 : 8 / LANES;       // texels per lane in the epilogue: sub, sub + LANES (lanes >= 8: none)
-    const float* tex_face = lt.textures + ((size_t)(lt.tex_batch > 1 ? bn : 0) * lt.F + fo) * 24;
-    int to[TPL];
-    float tx[TPL][3];
-#pragma unroll
-    for (int j = 0; j < TPL; j++) {
-        const int t = (sub + j * LANES) & 7;               // (lanes 8 .. 63 of a wave-wide face: unused copies)
-        to[j] = fn >= lt.F ? ((t & 1) << 2) | (t & 2) | ((t >> 2) & 1) : t;   // (a,b,c) -> (c,b,a) for ts = 2
-#pragma unroll
-        for (int c3 = 0; c3 < 3; c3++) tx[j][c3] = tex_face[to[j] * 3 + c3];
-    }
-    BoxCursorN<LANES> c(x0, x1, y0, sub);
-    for (int i = sub; i < area; i += LANES, c.advance()) {
-        const size_t p = base + (size_t)c.y * S + c.x;
-        // Everything the pixel could contribute is requested together with its owner (ONE round trip per step of
-        // the scan instead of two); a pixel of another face then computes on stand-in values with zero gradients
-        // (selected, never multiplied away: its own weights / depth belong to a different triangle).
-        const bool own = face_index_map[p] == fn;
-        const float lw0 = weight_map[3 * p], lw1 = weight_map[3 * p + 1], lw2 = weight_map[3 * p + 2];
-        const float lg0 = grad_rgb.get(p, 0) * s_rgb, lg1 = grad_rgb.get(p, 1) * s_rgb, lg2 = grad_rgb.get(p, 2) * s_rgb;
-        const float ld = depth_map[p], lgd = grad_depth_map ? grad_depth_map[p] * s_depth : 0.0f;
-        if (!__builtin_amdgcn_ballot_w64(own)) continue;                  // nobody in the wave owns its pixel
-        const float third = 1.0f / 3.0f;
-        const float weight[3] = {own ? lw0 : third, own ? lw1 : third, own ? lw2 : third};
-        const float g0 = own ? lg0 : 0.0f, g1 = own ? lg1 : 0.0f, g2 = own ? lg2 : 0.0f;
-        const float depth = own ? ld : 1.0f;
+    // The box is scanned for owner indices alone; weights, gradients and depth are requested, and the arithmetic runs, for
+    // the pixels the face owns and no others (scan_owned_pixels: a quarter of the box on the headline scene, dealt to the
+    // lanes by rank, so that a step of the dense loop has eight real pixels and not two).
+    scan_owned_pixels<LANES>(face_index_map + base, fn, S, x0, x1, y0, area, sub, [&](int x, int y) {
+        const size_t p = base + (size_t)y * S + x;
+        const float weight[3] = {weight_map[3 * p], weight_map[3 * p + 1], weight_map[3 * p + 2]};
+        const float g0 = grad_rgb.get(p, 0) * s_rgb, g1 = grad_rgb.get(p, 1) * s_rgb, g2 = grad_rgb.get(p, 2) * s_rgb;
+        const float depth = depth_map[p];
         if (grad_depth_map) {
-            const float g = own ? lgd : 0.0f, depth2 = depth * depth;
+            const float g = grad_depth_map[p] * s_depth, depth2 = depth * depth;
 #pragma unroll
             for (int k = 0; k < 3; k++) {
                 const float z_k = fc[3 * k + 2];
@@ -966,6 +955,21 @@ __device__ __forceinline__ void lit_face_backward(const LitFaceArgs& a, long gi,
             acc[isc * 3 + 1] += w * g1;
             acc[isc * 3 + 2] += w * g2;
         }
+    });
+    // what the epilogue needs: this lane's texel (sub) of the face's cube and the face's light (requested after the scan:
+    // held across it, their seven registers put the kernel over 128 and down to three waves per SIMD)
+    const int lrow = (lt.light_batch > 1 ? bn : 0) * Fp + fn;
+    const float li[3] = {lt.light[3 * (size_t)lrow], lt.light[3 * (size_t)lrow + 1], lt.light[3 * (size_t)lrow + 2]};
+    constexpr int TPL = LANES >= 8 ? 1 : 8 / LANES;       // texels per lane in the epilogue: sub, sub + LANES (lanes >= 8: none)
+    const float* tex_face = lt.textures + ((size_t)(lt.tex_batch > 1 ? bn : 0) * lt.F + fo) * 24;
+    int to[TPL];
+    float tx[TPL][3];
+#pragma unroll
+    for (int j = 0; j < TPL; j++) {
+        const int t = (sub + j * LANES) & 7;               // (lanes 8 .. 63 of a wave-wide face: unused copies)
+        to[j] = fn >= lt.F ? ((t & 1) << 2) | (t & 2) | ((t >> 2) & 1) : t;   // (a,b,c) -> (c,b,a) for ts = 2
+#pragma unroll
+        for (int c3 = 0; c3 < 3; c3++) tx[j][c3] = tex_face[to[j] * 3 + c3];
     }
 #pragma unroll
     for (int t = 0; t < 24; t++) acc[t] = lit_lanes_sum<LANES>(acc[t]);
@@ -1017,7 +1021,9 @@ __device__ __forceinline__ void lit_face_backward(const LitFaceArgs& a, long gi,
 // FM_LANES lanes per face.  Without a list every face of [B,F'] gets its lanes (hidden ones leave at once: ~95 % of
 // a fill_back mesh, i.e. mostly idle waves); with the compacted list of a d3m_visibility only faces that own a pixel
 // do, on a fixed grid that strides over the list.
-// (111 registers, 4 waves per SIMD; held to 5 or 6 waves it spills and loses: 0.26 / 0.34 ms against 0.22)
+// (126 registers, 4 waves per SIMD; held to 5 or 6 waves it spills and loses: 0.26 / 0.34 ms against 0.22.  The scan's
+// prefetched owner indices took it to 137 and three waves with the epilogue's texels and light requested before the scan,
+// as they were up to then: they are requested behind it.)
 template <int LANES = LIT_LANES>
 __global__ void __launch_bounds__(256) k_backward_textures_lit_faces(LitFaceArgs a) {
     static_assert(LANES == LIT_LANES || LANES == 64, "LIT_LANES lanes per face, or a wave");
@@ -1086,15 +1092,12 @@ __device__ __forceinline__ void lit_face_backward_any(const LitFaceArgs& a, long
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");          // (the zeroes before the first sums: one wave, in order)
     __builtin_amdgcn_wave_barrier();
     const size_t base = (size_t)bn * S * S;
-    BoxCursorN<LANES> c(x0, x1, y0, sub);
-    for (int i = sub; i < area; i += LANES, c.advance()) {
-        const size_t p = base + (size_t)c.y * S + c.x;
-        // (the pixel's maps are requested together with its owner: one round trip per step of the scan)
-        const bool own = a.face_index_map[p] == fn;
+    // (owner indices over the box, everything else for the owned pixels only, in the order of lit_face_backward)
+    scan_owned_pixels<LANES>(a.face_index_map + base, fn, S, x0, x1, y0, area, sub, [&](int x, int y) {
+        const size_t p = base + (size_t)y * S + x;
         const float lw[3] = {a.weight_map[3 * p], a.weight_map[3 * p + 1], a.weight_map[3 * p + 2]};
         const float lg[3] = {a.grad_rgb.get(p, 0) * s_rgb, a.grad_rgb.get(p, 1) * s_rgb, a.grad_rgb.get(p, 2) * s_rgb};
         const float ld = a.depth_map[p], lgd = a.grad_depth_map ? a.grad_depth_map[p] * s_depth : 0.0f;
-        if (!own) continue;
         if (a.grad_depth_map) {
             const float depth2 = ld * ld;
 #pragma unroll
@@ -1116,7 +1119,7 @@ __device__ __forceinline__ void lit_face_backward_any(const LitFaceArgs& a, long
 #pragma unroll
             for (int k = 0; k < 3; k++) atomicAdd(&acc_lds[isc * 3 + k], w * lg[k]);
         }
-    }
+    });
     if (a.grad_depth_map) {
 #pragma unroll
         for (int k = 0; k < 9; k++) dacc[k] = lit_lanes_sum<LANES>(dacc[k]);

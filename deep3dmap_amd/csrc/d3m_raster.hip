@@ -1676,7 +1676,7 @@ D3M_EXPORT int d3m_backward_textures_lit(const float* faces, const float* textur
         // (a coarse mesh -- more than 48 raster pixels per triangle -- gives a face a whole wave instead of eight lanes)
         const bool coarse = list && (double)S * S > 48.0 * (double)num_tri;
         const unsigned all_blocks = blocks_for(nf, coarse ? 4 : LIT_FACES_PER_BLOCK);
-        const dim3 g_faces(list ? (all_blocks > 4096 ? 4096 : (all_blocks + 7) / 8 * 8) : all_blocks);
+        const dim3 g_faces(list ? (all_blocks > LIT_LIST_BLOCKS ? LIT_LIST_BLOCKS : (all_blocks + 7) / 8 * 8) : all_blocks);
         if (coarse) LAUNCH("k_backward_textures_lit_faces", k_backward_textures_lit_faces<64>, g_faces, dim3(256), st, fa);
         else LAUNCH("k_backward_textures_lit_faces", k_backward_textures_lit_faces<>, g_faces, dim3(256), st, fa);
         // the texel and depth gradients of the faces the gathered pass marked LARGE (normally none: leaves at once) -- and, for
