@@ -51,7 +51,8 @@ class D3MMeshTopology(ctypes.Structure):
 class D3MFitTargets(ctypes.Structure):
     _fields_ = [("rgb_target", _P), ("depth_target", _P), ("alpha_target", _P), ("mask", _P), ("scratch", _P),
                 ("loss", _P), ("grad_rgb_map", _P), ("grad_alpha_map", _P), ("grad_depth_map", _P), ("grad_loss", _P),
-                ("mask_sum", _P), ("edge_grad", _P), ("edge_dot", _P), ("edge_nz_lo_inv", _P), ("edge_nz_hi1", _P), ("flags", _I)]
+                ("mask_sum", _P), ("edge_grad", _P), ("edge_dot", _P), ("edge_nz_lo_inv", _P), ("edge_nz_hi1", _P), ("flags", _I),
+                ("tile_void", _P)]
 
 
 class D3MG2SBlock(ctypes.Structure):
@@ -153,6 +154,10 @@ _SIGNATURES = {
     "d3m_render_fit_scratch_floats": (_SZ, [_I, _I]),
     "d3m_render_fit_scratch_clear_range": (_SZ, [_I, _I, ctypes.POINTER(_SZ)]),
     "d3m_fit_finish": (_I, [ctypes.POINTER(D3MFitTargets), _I, _I, _P]),
+    "d3m_render_fit_scratch_tile_void_offset": (_SZ, [_I, _I]),
+    "d3m_fit_target_summary": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
+    "d3m_set_fit_tile_form": (_I, [_I]),
+    "d3m_get_fit_tile_form": (_I, []),
     "d3m_fit_loss_records": (_I, [_P, _P, _P, _P, ctypes.POINTER(D3MFitTargets), _I, _I, _P]),
     "d3m_backward_textures_lit": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _SZ,
                                        _P, _P, _P, _I, _P]),

@@ -113,10 +113,33 @@ struct EdgeGradArgs {
         const int yo = img_aa ? (S - 1 - y) >> 1 : S - 1 - y, xo = img_aa ? x >> 1 : x;
         return ga_img[(view * img_s + yo) * img_s + xo] * (img_aa ? 0.25f : 1.0f);
     }
+    // VOID TILES (rgb + alpha records of the fused fit objective's pass, d3m_lit.h struct FitRecords; NULL = none).  The pass
+    // wrote neither records nor values for the pixels of a tile whose byte is 1 -- what is there is stale: such a pixel IS
+    // the constant the pass would have stored: value (0, background of the view), gradients 0, (T, owner) = (0, -1).  One
+    // byte per (view, tile of 1 << tile_shift pixels a side), tiles_x tiles per row, tiles_view per view.
+    const unsigned char* tile_void;
+    const float* void_bg;     // [B,4]: the background the pass read, per view
+    int tile_shift, tiles_x, tiles_view;
+    __device__ __forceinline__ bool void_at(size_t view, int axis, int d0, int d1) const {      // position d1 of line d0
+        if (!tile_void) return false;
+        const int y = axis ? d0 : d1, x = axis ? d1 : d0;
+        return tile_void[view * tiles_view + (size_t)(y >> tile_shift) * tiles_x + (x >> tile_shift)] != 0;
+    }
+    __device__ __forceinline__ bool void_pixel(size_t pi) const {       // pi = (b*S + y)*S + x (the walks from global memory)
+        if (!tile_void) return false;
+        const size_t plane = (size_t)S * S, b = pi / plane;
+        const int rem = (int)(pi - b * plane), y = rem / S;
+        return void_at(b, 1, y, rem - y * S);
+    }
+    __device__ __forceinline__ float4 void_value(size_t view) const {
+        return make_float4(0.0f, void_bg[4 * view], void_bg[4 * view + 1], void_bg[4 * view + 2]);
+    }
     __device__ __forceinline__ float4 rec_grad(size_t pi) const {
+        if (void_pixel(pi)) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return direct() ? make_float4(direct_ga(pi), 0.0f, 0.0f, 0.0f) : grad[pi];
     }
     __device__ __forceinline__ float2 rec_dot(size_t pi) const {
+        if (void_pixel(pi)) return make_float2(0.0f, __int_as_float(-1));
         if (!direct()) return dot[pi];
         return make_float2(alpha_map[pi] * direct_ga(pi), __int_as_float(fi_direct[pi]));
     }
@@ -327,6 +350,11 @@ __device__ __forceinline__ void visit_pixel_div(float diff, int d1, float d1_cro
 __device__ __forceinline__ SegRef load_ref(const EdgeGradArgs& a, int axis, size_t view_base, int d0, int d1) {
     const size_t idx = view_base + (axis ? (size_t)d0 * a.S + d1 : (size_t)d1 * a.S + d0);
     SegRef r = {0, 0, 0, 0};
+    if (a.void_pixel(idx)) {                                  // (see EdgeGradArgs::tile_void: the maps are stale there)
+        const float4 v = a.void_value(idx / ((size_t)a.S * a.S));
+        r.r = v.y; r.g = v.z; r.b = v.w;
+        return r;
+    }
     if (a.use_alpha) r.alpha = a.alpha_map[idx];
     if (a.use_rgb) { r.r = a.rgb_map[3 * idx + 0]; r.g = a.rgb_map[3 * idx + 1]; r.b = a.rgb_map[3 * idx + 2]; }
     return r;
@@ -1144,18 +1172,28 @@ __global__ void __launch_bounds__(WAVES * 64, 8) k_edge_lines(EdgeGradArgs a, Ed
     float4* s_grd = (float4*)(s_df + is + (is & 1));           // [is] gradients (alpha, r, g, b)
     float4* s_val = s_grd + is;                                // [is] values (alpha, r, g, b), then the PAD tail
     const float go_sign = a.go_sign();
+    // (rgb + alpha: a pixel of a VOID TILE is staged as its constant, with no load but the tile's byte -- one byte serves
+    //  a whole tile row of a row line: EdgeGradArgs::tile_void)
+    constexpr bool VOID_TILES = USE_RGB && USE_ALPHA;
     for (int p = (int)threadIdx.x; p < is; p += EG_LINE_THREADS) {
         const size_t pi = a.pixel(axis, view_base, d0, p);
         float4 v = make_float4(0, 0, 0, 0);
-        if (USE_ALPHA) v.x = a.alpha_map[pi];
-        if (USE_RGB) { v.y = a.rgb_map[3 * pi]; v.z = a.rgb_map[3 * pi + 1]; v.w = a.rgb_map[3 * pi + 2]; }
+        if (VOID_TILES && a.void_at(bn, axis, d0, p)) {
+            v = a.void_value(bn);
+        } else {
+            if (USE_ALPHA) v.x = a.alpha_map[pi];
+            if (USE_RGB) { v.y = a.rgb_map[3 * pi]; v.z = a.rgb_map[3 * pi + 1]; v.w = a.rgb_map[3 * pi + 2]; }
+        }
         s_val[p] = v;
     }
     for (int p = p_lo + (int)threadIdx.x; p <= p_hi; p += EG_LINE_THREADS) {
         const size_t pi = a.pixel(axis, view_base, d0, p);
         float4 g;
         float2 d;
-        if (!USE_RGB && a.direct()) {
+        if (VOID_TILES && a.void_at(bn, axis, d0, p)) {
+            g = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            d = make_float2(0.0f, __int_as_float(-1));
+        } else if (!USE_RGB && a.direct()) {
             const float ga = a.direct_ga_at(bn, axis, d0, p, pi);
             g = make_float4(ga, 0.0f, 0.0f, 0.0f);
             d = make_float2(a.alpha_map[pi] * ga, __int_as_float(a.fi_direct[pi]));
@@ -2058,6 +2096,10 @@ struct EdgeRecords {
     const int* nz_lo_inv;
     const int* nz_hi1;
     const float* go;       // the factor they still lack (device scalar; NULL = 1)
+    // the fused fit objective's void tiles (EdgeGradArgs::tile_void): flags, the views' backgrounds, tile edge (16 | 32)
+    const unsigned char* tile_void = nullptr;
+    const float* void_bg = nullptr;
+    int tile = 0;
     // alpha only, no records at all (EdgeGradArgs "DIRECT"): the OUTPUT image's alpha gradient [B,s,s], s = S or S/2 (aa)
     const float* ga_img = nullptr;
     int img_aa = 0;
@@ -2111,9 +2153,16 @@ int run_edge_grad(FS fs, PixelMaps m, float* grad_faces, VertexTarget vt, const 
     // runs; the output image's gradient has no packed form)
     const bool direct = !rec.grad && !m.use_rgb && m.use_alpha && !gs.totals &&
                         (rec.ga_img || d3m_env_int("D3M_EG_DIRECT", 1) != 0);
+    a.tile_void = nullptr; a.void_bg = nullptr; a.tile_shift = 0; a.tiles_x = a.tiles_view = 0;
     if (rec.grad) {
         a.grad = rec.grad; a.dot = rec.dot; a.go = rec.go;
         a.nz_lo_inv = rec.nz_lo_inv; a.nz_hi1 = rec.nz_hi1;
+        if (rec.tile_void) {
+            if (!(m.use_rgb && m.use_alpha) || !rec.void_bg || (rec.tile != 16 && rec.tile != 32)) return 1;   // D3M_ERR_INVALID
+            a.tile_void = rec.tile_void; a.void_bg = rec.void_bg;
+            a.tile_shift = rec.tile == 32 ? 5 : 4;
+            a.tiles_x = (S + rec.tile - 1) / rec.tile; a.tiles_view = a.tiles_x * a.tiles_x;
+        }
     } else if (direct) {
         a.grad = nullptr; a.dot = nullptr; a.go = nullptr; a.nz_lo_inv = a.nz_hi1 = nullptr;
         if (rec.ga_img) { a.ga_img = rec.ga_img; a.img_aa = rec.img_aa; a.img_s = rec.img_aa ? S / 2 : S; }

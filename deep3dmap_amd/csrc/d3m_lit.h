@@ -511,7 +511,34 @@ struct FitRecords {
     int* nz_hi1;           // [B,2,S] zeroed: last such pixel + 1
     const float* mask_sum; // [1]
     float* g_depth;        // [B,S,S] sign(depth - target) * mask (the depth gradient stays a map: k_backward_textures_lit)
+    // VOID TILES (k_render_lit_fit_records only; all NULL = every tile does all of its work).  target_void: one byte per
+    // (view, 16 x 16 tile of the OUTPUT image), 1 = the targets ask nothing of the tile (k_fit_target_summary).  A tile of
+    // the pass whose targets are void and which no face covers stores its zero partial sums and its byte of tile_void
+    // [B, tiles_y, tiles_x] (written by EVERY tile in EVERY launch, 0 or 1) and nothing else; the line walk stages such a
+    // tile's pixels as constants (EdgeGradArgs::tile_void), the background among them: void_bg [B,4], as this launch read it.
+    const unsigned char* target_void = nullptr;
+    unsigned char* tile_void = nullptr;
+    float* void_bg = nullptr;
 };
+
+// One byte per (view, 16 x 16 tile of the OUTPUT image, row 0 = top): 1 iff at every pixel of the tile inside the image
+// alpha_t == 0, mask == 0, and rgb_t and depth_t are finite -- the pixels where the fit objective's terms and gradients
+// do not depend on the targets at all (a term is |image - target| * mask: 0 * finite).  Targets are constants of a fit:
+// built once per set of targets, not per step.
+__global__ void __launch_bounds__(256) k_fit_target_summary(const float* __restrict__ rgb_t, const float* __restrict__ depth_t,
+                                                           const float* __restrict__ alpha_t, const float* __restrict__ mask,
+                                                           unsigned char* __restrict__ target_void, int B, int S) {
+    const int b = blockIdx.z, xo = blockIdx.x * 16 + (threadIdx.x & 15), yo = blockIdx.y * 16 + (threadIdx.x >> 4);
+    bool live = false;
+    if (xo < S && yo < S) {
+        const size_t o = ((size_t)b * S + yo) * S + xo;
+        live = !(alpha_t[o] == 0.0f) || !(mask[o] == 0.0f) || !isfinite(depth_t[o]);
+#pragma unroll
+        for (int k = 0; k < 3; k++) live = live || !isfinite(rgb_t[(((size_t)b * 3 + k) * S + yo) * S + xo]);
+    }
+    const int any = __syncthreads_or(live ? 1 : 0);
+    if (threadIdx.x == 0) target_void[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = any ? 0 : 1;
+}
 
 // (4 waves per SIMD: the compiler wants 134 registers, six more than four waves allow; held to 128 the pass -- bound by its
 //  memory round trips, i.e. by how many of them are in flight -- takes 0.198 instead of 0.233 ms alone; 5 waves spill: 0.35)
@@ -543,6 +570,49 @@ __global__ void __launch_bounds__(256, D3M_FIT_MINWAVES) k_render_lit_fit_record
     const float inv_pixels = 1.0f / (float)((long)S * S), inv_3den = 1.0f / (3.0f * *rec.mask_sum);
     float t_rgb = 0, t_d = 0, t_m = 0, t_sse = 0;
     auto sgn = [](float x) { return x > 0 ? 1.0f : (x < 0 ? -1.0f : 0.0f); };
+    // VOID TILES (struct FitRecords).  t_void (uniform): the targets ask nothing of this tile -- every 16 x 16 tile of the
+    // output image it touches is flagged (the row flip yo = S - 1 - yi is applied HERE: off a multiple of 16 an internal
+    // tile straddles one more row of output tiles), and the launch's own constants are finite (a void pixel's terms are
+    // constant * 0).  Such a tile issues no target loads: tg = 0 gives the same terms and gradients up to the sign of a zero.
+    bool t_void = false;
+    if (rec.target_void) {
+        const int n16 = (S + 15) >> 4, xe = min(x0 + TILE, S) - 1, yo_lo = S - min(y0 + TILE, S), yo_hi = S - 1 - y0;
+        t_void = isfinite(bg[0]) && isfinite(bg[1]) && isfinite(bg[2]) && isfinite(inv_3den);
+        for (int j = yo_lo >> 4; j <= yo_hi >> 4; j++)
+            for (int i = x0 >> 4; i <= xe >> 4; i++) t_void = t_void && rec.target_void[((size_t)b * n16 + j) * n16 + i] != 0;
+        if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 3) rec.void_bg[4 * b + threadIdx.x] = bg[threadIdx.x];
+        const size_t tile = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        bool covered = false;
+        if (t_void) {                                         // (uniform: the barrier of the OR is the workgroup's)
+            for (int r = ty; r < TILE; r += ROWS)
+                if (y0 + r < S && x0 + tx < S) covered = covered || face_index_map[((size_t)b * S + y0 + r) * S + x0 + tx] >= 0;
+            covered = __syncthreads_or(covered ? 1 : 0) != 0;
+        }
+        // VOID: no target, no coverage.  Every pixel is the background with alpha 0, every term and gradient is zero: the
+        // tile says so in one byte, stores the zero partial sums the objective's finish adds in its fixed order, and leaves
+        // rgb_blended, alpha_map, the records, the depth gradient and the extents alone (their readers: the line walk, which
+        // stages the constants by the byte; the gathered texture / depth pass, k_lit_large_faces and the per-pixel texture
+        // and depth passes, which read them at pixels a face owns; the plan reads face_index_map, the tile pass's).
+        if (threadIdx.x == 0) rec.tile_void[tile] = (t_void && !covered) ? 1 : 0;
+        if (t_void && !covered) {
+            if (threadIdx.x == 0) reinterpret_cast<float4*>(fit.partials)[tile] = make_float4(0, 0, 0, 0);
+            if (rgb_out || alpha_out || depth_out) {          // the images are written everywhere
+                for (int r = ty; r < TILE; r += ROWS) {
+                    const int yi = y0 + r, xi = x0 + tx;
+                    if (yi >= S || xi >= S) continue;
+                    const int yo = S - 1 - yi;
+                    const size_t o = ((size_t)b * S + yo) * S + xi;
+                    if (rgb_out) {
+#pragma unroll
+                        for (int k = 0; k < 3; k++) rgb_out[(((size_t)b * 3 + k) * S + yo) * S + xi] = bg[k];
+                    }
+                    if (alpha_out) alpha_out[o] = 0.0f;
+                    if (depth_out) depth_out[o] = depth_map[((size_t)b * S + yi) * S + xi];   // (the tile pass's far value)
+                }
+            }
+            return;
+        }
+    }
     for (int r = ty; r < TILE; r += ROWS) {
         const int yi = y0 + r, xi = x0 + tx;                  // internal pixel; row 0 = bottom (rasterize.py:311-317)
         bool nz = false;
@@ -550,10 +620,12 @@ __global__ void __launch_bounds__(256, D3M_FIT_MINWAVES) k_render_lit_fit_record
             const int yo = S - 1 - yi;                        // output row
             const size_t p = ((size_t)b * S + yi) * S + xi, o = ((size_t)b * S + yo) * S + xi;
             // the objective's targets are requested first: they then arrive under the dependent loads of the sampling
-            float tg[6];
+            float tg[6] = {0, 0, 0, 0, 0, 0};
+            if (!t_void) {
 #pragma unroll
-            for (int k = 0; k < 3; k++) tg[k] = fit.rgb_t[(((size_t)b * 3 + k) * S + yo) * S + xi];
-            tg[3] = fit.depth_t[o]; tg[4] = fit.alpha_t[o]; tg[5] = fit.mask[o];
+                for (int k = 0; k < 3; k++) tg[k] = fit.rgb_t[(((size_t)b * 3 + k) * S + yo) * S + xi];
+                tg[3] = fit.depth_t[o]; tg[4] = fit.alpha_t[o]; tg[5] = fit.mask[o];
+            }
             const int fi = face_index_map[p];
             const float depth = depth_map[p];
             float v[3] = {bg[0], bg[1], bg[2]};

@@ -526,6 +526,9 @@ static GradScale to_grad_scale(const d3m_fit_targets* unscaled, int image_size) 
                      unscaled->edge_grad ? 1 : 0, unscaled->mask_sum};
 }
 
+// (the fused fit objective's void tiles, if its pass flagged any: defined with the objective's scratch below)
+static void fit_void_records(const d3m_fit_targets* unscaled, int B, int S, EdgeRecords& rec);
+
 D3M_EXPORT size_t d3m_backward_pixel_map_workspace_bytes(int batch_size, int num_faces, int image_size) {
     return edge_grad_workspace_bytes(batch_size, num_faces, image_size);
 }
@@ -562,6 +565,7 @@ D3M_EXPORT int d3m_backward_pixel_map(const float* faces, const int32_t* face_in
     if (records)
         rec = EdgeRecords{(const float4*)unscaled->edge_grad, (const float2*)unscaled->edge_dot, unscaled->edge_nz_lo_inv,
                           unscaled->edge_nz_hi1, unscaled->grad_loss};
+    if (records) fit_void_records(unscaled, batch_size, image_size, rec);
     if (of_image) {
         rec.ga_img = unscaled->grad_alpha_map;
         rec.img_aa = (unscaled->flags & D3M_FIT_POOLED) ? 1 : 0;
@@ -1391,7 +1395,7 @@ D3M_EXPORT int d3m_forward_texture_sampling_lit(const float* faces, const float*
 // (k_render_lit_fit_records) -- more of them than pixels / 256 when the image is smaller than a tile; a group (the unit of
 // the objective's two-level finish, d3m_lit.h fit_finish_groups) is a view's tiles, or 256 consecutive workgroups.
 struct FitScratch {
-    size_t off_partials, off_group_sums, off_tickets, ticket_words, floats;
+    size_t off_partials, off_group_sums, off_tickets, ticket_words, off_void_bg, off_tile_void, floats;
 };
 // Tile edge of the records form of the objective's pass (k_render_lit_fit_records<TILE>, k_fit_loss_records<TILE>): 16 -- one
 // pixel per thread, four times the workgroups -- while the batch has at most FIT_TILE16_MAX_PIXELS pixels (a pass of a
@@ -1401,8 +1405,20 @@ struct FitScratch {
 // Measured (round 6, same box, committed tree | this): one view of the 53 k mesh @256 0.108 -> 0.102 ms (the pass itself
 // 24.4 -> 11 us), 8 views of the headline mesh 0.467 -> 0.458; 4 views 0.270 -> 0.273 (the pass is off that step's critical
 // chain); 32 views keep the 32 x 32 tiles (one atomic per column and tile instead of four).
+// d3m_set_fit_tile_form (A/B runs and tests): -1 = by the launch's size, 0 = always 16, 1 = always 32.
 static const long FIT_TILE16_MAX_PIXELS = 4l << 20;
-static int fit_tile(int B, int S) { return (long)B * S * S <= FIT_TILE16_MAX_PIXELS ? 16 : 32; }
+static std::atomic<int> g_fit_tile_form{-1};
+D3M_EXPORT int d3m_set_fit_tile_form(int form) {
+    if (form < -1 || form > 1) return D3M_ERR_INVALID;
+    g_fit_tile_form.store(form);
+    return D3M_OK;
+}
+D3M_EXPORT int d3m_get_fit_tile_form(void) { return g_fit_tile_form.load(); }
+static int fit_tile(int B, int S) {
+    const int form = g_fit_tile_form.load();
+    if (form >= 0) return form ? 32 : 16;
+    return (long)B * S * S <= FIT_TILE16_MAX_PIXELS ? 16 : 32;
+}
 static FitScratch fit_scratch_layout(int B, int S) {
     const size_t per_pixels = blocks_for((long)B * S * S, 256);
     const size_t tiles32 = (size_t)B * ((S + 31) / 32) * ((S + 31) / 32), tiles16 = (size_t)B * ((S + 15) / 16) * ((S + 15) / 16);
@@ -1414,12 +1430,33 @@ static FitScratch fit_scratch_layout(int B, int S) {
     L.off_group_sums = 8 + 4 * P;
     L.off_tickets = L.off_group_sums + 4 * G;
     L.ticket_words = 4;
-    L.floats = L.off_tickets + L.ticket_words;
+    // the void tiles of the records form (d3m_fit_targets.tile_void): the views' backgrounds [B,4] | one byte per tile
+    L.off_void_bg = L.off_tickets + L.ticket_words;
+    L.off_tile_void = L.off_void_bg + 4 * (size_t)B;
+    L.floats = L.off_tile_void + (tiles + 3) / 4;
     return L;
+}
+// whether a records-form pass with this struct flags void tiles (forward) / its walk reads the flags (backward): the same rule
+static bool fit_void_tiles(const d3m_fit_targets* fit) {
+    return fit && fit->tile_void && fit->edge_grad && fit->scratch && !(fit->flags & D3M_FIT_POOLED);
+}
+// the pass that wrote these records skipped its void tiles: so must the walk that reads them
+static void fit_void_records(const d3m_fit_targets* unscaled, int B, int S, EdgeRecords& rec) {
+    if (!fit_void_tiles(unscaled)) return;
+    const FitScratch L = fit_scratch_layout(B, S);
+    rec.tile_void = (const unsigned char*)(unscaled->scratch + L.off_tile_void);
+    rec.void_bg = unscaled->scratch + L.off_void_bg;
+    rec.tile = fit_tile(B, S);
 }
 D3M_EXPORT size_t d3m_render_fit_scratch_floats(int batch_size, int image_size) {
     if (batch_size <= 0 || image_size <= 0) return 0;
     return fit_scratch_layout(batch_size, image_size).floats;
+}
+// where the records form's void-tile flags lie in that scratch (d3m_fit_targets.tile_void; tests read them back): the offset
+// in floats of one byte per tile of the launch, [B, tiles_y, tiles_x], tiles of the edge the launch took (d3m_set_fit_tile_form)
+D3M_EXPORT size_t d3m_render_fit_scratch_tile_void_offset(int batch_size, int image_size) {
+    if (batch_size <= 0 || image_size <= 0) return 0;
+    return fit_scratch_layout(batch_size, image_size).off_tile_void;
 }
 // the part of that scratch which must be ZERO when a pass with a fused objective starts (the finish's ticket): cleared by the
 // pass's entry point itself unless the caller did (fit->flags & D3M_PRECLEARED)
@@ -1495,6 +1532,12 @@ D3M_EXPORT int d3m_render_lit_epilogue(const float* faces, const float* textures
         const dim3 tiles16((image_size + 15) / 16, (image_size + 15) / 16, batch_size);
         FitRecords rec{(float4*)fit->edge_grad, (float2*)fit->edge_dot, fit->edge_nz_lo_inv, fit->edge_nz_hi1, fit->mask_sum,
                        fit->grad_depth_map};
+        if (fit_void_tiles(fit)) {                   // (never the pooled form: fit_void_tiles)
+            const FitScratch L = fit_scratch_layout(batch_size, image_size);
+            rec.target_void = fit->tile_void;
+            rec.void_bg = fit->scratch + L.off_void_bg;
+            rec.tile_void = (unsigned char*)(fit->scratch + L.off_tile_void);
+        }
         if (anti_aliasing)
             LAUNCH("k_render_lit_fit_records", k_render_lit_fit_records_pooled, tiles, dim3(256), st, faces, lt,
                    face_index_map, weight_map, depth_map, background, background_batch, rgb_blended, alpha_map, rgb_out,
@@ -1546,6 +1589,7 @@ D3M_EXPORT int d3m_fit_loss_records(const float* rgb, const float* depth, const 
     FitTargets ft;
     if (int rc = to_fit_targets(fit, ft)) return rc;
     if (fit->flags & (D3M_FIT_FINISH_DEFERRED | D3M_FIT_POOLED)) return D3M_ERR_INVALID;      // (finished images: no pooling here)
+    if (fit->tile_void) return D3M_ERR_INVALID;      // (this pass writes every record: a walk told otherwise would read stale flags)
     hipStream_t st = (hipStream_t)stream;
     if (int rc = clear_fit_tickets(fit, batch_size, image_size, st)) return rc;
     FitRecords rec{(float4*)fit->edge_grad, (float2*)fit->edge_dot, fit->edge_nz_lo_inv, fit->edge_nz_hi1, fit->mask_sum,
@@ -1558,6 +1602,19 @@ D3M_EXPORT int d3m_fit_loss_records(const float* rgb, const float* depth, const 
                dim3(256), st, rgb, depth, alpha, face_index_map, batch_size, image_size, ft, rec);
     const FitFin fin = fit_fin_of_tiles(fit, batch_size, image_size);
     LAUNCH("k_fit_finish", k_fit_finish, dim3(fin.n_groups), dim3(256), st, fin);
+    return check_launch();
+}
+
+// The targets' summary for d3m_fit_targets.tile_void: one byte per (view, 16 x 16 tile of the output image), see
+// k_fit_target_summary.  tile_void: batch_size * ceil(image_size / 16)^2 bytes.
+D3M_EXPORT int d3m_fit_target_summary(const float* rgb_target, const float* depth_target, const float* alpha_target,
+                                      const float* mask, unsigned char* tile_void, int batch_size, int image_size,
+                                      d3m_stream_t stream) {
+    if (!rgb_target || !depth_target || !alpha_target || !mask || !tile_void || batch_size <= 0 || image_size <= 0)
+        return D3M_ERR_INVALID;
+    const int n16 = (image_size + 15) / 16;
+    LAUNCH("k_fit_target_summary", k_fit_target_summary, dim3(n16, n16, batch_size), dim3(256), (hipStream_t)stream,
+           rgb_target, depth_target, alpha_target, mask, tile_void, batch_size, image_size);
     return check_launch();
 }
 

@@ -13,6 +13,7 @@ import torch.nn as nn
 from .. import _lib
 from . import rasterize_ops as ops
 from ._util import const_tensor, deterministic as _deterministic, f32c
+from .built_cache import BuiltCache, tensor_key
 from .row_gather import vertex_adjacency
 
 DEFAULT_IMAGE_SIZE = 256
@@ -388,6 +389,7 @@ class _FitState(NamedTuple):
     mask_sum: Optional[torch.Tensor]        # [1]: the photometric normaliser (None: sum(mask), no gradient wanted)
     pooled: bool                            # an objective on the 2x2-pooled images (anti-aliasing)
     records: Optional[_Records]
+    tile_void: Optional[torch.Tensor] = None    # [B,n16,n16] uint8: the targets' void tiles (target_void_summary) or None
 
     def struct(self, k, lo, hi, grad_loss=None, flags=0):
         """d3m_fit_targets of view group k (views lo..hi): forward's `fit` (grad_loss None) / backward's `unscaled`."""
@@ -398,7 +400,61 @@ class _FitState(NamedTuple):
             rgb_target=_lib.ptr(self.rgb_t[lo:hi]), depth_target=_lib.ptr(self.depth_t[lo:hi]),
             alpha_target=_lib.ptr(self.alpha_t[lo:hi]), mask=_lib.ptr(self.mask[lo:hi]), scratch=_lib.ptr(self.scratch[k]),
             loss=_lib.ptr(self.loss[k:k + 1]), grad_loss=_lib.ptr(grad_loss), mask_sum=_lib.ptr(self.mask_sum), **rec,
-            flags=int(flags))
+            flags=int(flags), tile_void=_lib.ptr(None if self.tile_void is None else self.tile_void[lo:hi]))
+
+
+class _TargetVoidCache(BuiltCache):
+    what = "the fit targets' void-tile summary"
+
+
+# Two sets of targets at most: an entry holds its four target tensors (at the headline's size about 200 MB) to keep their
+# addresses taken, and a caller whose targets are new tensors every step (a tracker; targets f32c has to copy) should pin no
+# more than that.  Such a caller also pays the summary's kernel every step (61 us at the headline's size, more than void
+# tiles save there): D3M_FIT_VOID_TILES=0 is for it.
+_target_void_cache = _TargetVoidCache(size=2)
+
+
+def fit_void_tiles_enabled():
+    """D3M_FIT_VOID_TILES=0 keeps d3m_fit_targets.tile_void NULL: the fused objective's pass does all of its work in every
+    tile (A/B runs and the parity tests)."""
+    return os.environ.get("D3M_FIT_VOID_TILES", "1") != "0"
+
+
+def _build_target_void(rgb_t, depth_t, alpha_t, mask):
+    B, S = mask.shape[0], mask.shape[-1]
+    n16 = (S + 15) // 16
+    out = torch.empty(B, n16, n16, dtype=torch.uint8, device=mask.device)
+    _lib.check(_lib.lib().d3m_fit_target_summary(_lib.ptr(rgb_t), _lib.ptr(depth_t), _lib.ptr(alpha_t), _lib.ptr(mask),
+                                                 _lib.ptr(out), B, S, _lib.stream_ptr()), "d3m_fit_target_summary")
+    return out
+
+
+def target_void_summary(rgb_t, depth_t, alpha_t, mask, build=_build_target_void, capturing=None):
+    """One byte per (view, 16 x 16 tile of the output image): 1 where the targets ask nothing of the fit objective (alpha
+    target 0, mask 0, finite rgb / depth targets at every pixel of the tile) -- d3m_fit_targets.tile_void.  The targets of a
+    fit are constants (MultiViewFit.set_targets_from, Renderer.fit_targets), so the summary is built ONCE per set of target
+    tensors -- keyed by their addresses and versions -- on the first eager step, and never inside a stream capture: a
+    capture that finds none takes the pass without void tiles (None), it does not raise.  None as well under
+    D3M_FIT_VOID_TILES=0.
+    Like _vec3_host, the key only sees writes that bump a tensor's `_version`: after a write that does not (through
+    `.data`, a raw pointer, another library), call invalidate_target_void_summaries().
+    A CAPTURED step replays with the summary it was captured with -- no check can run at replay: after ANY write to the
+    targets of a captured step (a `copy_` into persistent target buffers included) the step must be captured again, or such a
+    caller runs under D3M_FIT_VOID_TILES=0.  Without the summary the kernels read the targets at replay and need neither."""
+    if not fit_void_tiles_enabled():
+        return None
+    targets = (rgb_t, depth_t, alpha_t, mask)
+    key = tuple(tensor_key(t) for t in targets)
+    if capturing is None:
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+    if capturing and key not in _target_void_cache:
+        return None
+    return _target_void_cache.get(key, lambda: build(*targets), holders=targets)
+
+
+def invalidate_target_void_summaries():
+    """Forget every cached summary of fit targets (target_void_summary): the next eager step rebuilds its own."""
+    _target_void_cache.clear()
 
 
 def _front_clears(clears):
@@ -779,7 +835,15 @@ class _RasterizeLit(torch.autograd.Function):
                                     .view(B, 2, S) for j in range(2))
                 own_extents = extents is None
                 records = _pixel_records(B, S, dev, grad_depth=True, extents=extents)
-            fit_state = _FitState(rgb_t, depth_t, alpha_t, mask, scratch, loss_g, mask_sum, bool(anti_aliasing), records)
+            # VOID TILES: where neither the targets nor the mesh ask anything of a tile, the pass does no memory work there
+            # (d3m_fit_targets.tile_void).  Records form without anti-aliasing only; not for a REGISTERED objective, whose
+            # backward pass may turn out to be the images' after all and then reads rgb_map / alpha_map at every pixel
+            # (d3m_output_epilogue_backward_records).  Backward hands the library the same struct, so both passes agree.
+            tile_void = None
+            if records is not None and not anti_aliasing and not hinted:
+                tile_void = target_void_summary(rgb_t, depth_t, alpha_t, mask)
+            fit_state = _FitState(rgb_t, depth_t, alpha_t, mask, scratch, loss_g, mask_sum, bool(anti_aliasing), records,
+                                  tile_void)
         st = _LitState(S=S, eps=float(eps), aa=bool(anti_aliasing), ra=bool(return_alpha), rd=bool(return_depth),
                        fill_back=bool(fill_back), light=(float(ia), float(idr), ca, cd, direction) if dlight is None else None,
                        Bl=Bl, groups=groups, need_grad=need_grad, need_geom=need_geom, need_tex=need_tex,

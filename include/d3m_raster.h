@@ -585,14 +585,37 @@ struct d3m_fit_targets {
                                   * handed this struct (same flag) as `unscaled`, completes it in a kernel it launches anyway --
                                   * for callers that run the backward pass right behind the forward pass: no finishing launch
                                   * D3M_FIT_POOLED: the records belong to an objective on the 2x2-pooled images (see above) */
+    /* VOID TILES (optional; NULL = exactly the behaviour without it).  The summary d3m_fit_target_summary made of THESE
+     * targets: one byte per (view, 16 x 16 tile of the output image), 1 = alpha_target == 0, mask == 0 and finite rgb /
+     * depth targets at every pixel of the tile.  Records form without anti-aliasing only (ignored otherwise): a tile of the
+     * pass whose targets are void and which no face covers stores its zero partial sums and one byte in `scratch`, reads
+     * face_index_map alone (and depth_map where depth_out is given: the tile's depth_out is copied from it) and writes
+     * neither rgb_blended, alpha_map, the records nor grad_depth_map there (rgb_out / alpha_out / depth_out, when given,
+     * are written everywhere).  The summary must describe the targets AS THE KERNEL READS THEM: targets rewritten in place
+     * need a new summary.  d3m_backward_pixel_map handed the SAME struct as `unscaled` (same
+     * tile_void, scratch, batch and image size; return_rgb and return_alpha) stages those tiles' pixels as the constants the
+     * pass would have stored; d3m_backward_textures_lit reads records only at pixels a face owns.  Nothing is carried from
+     * one launch to the next: every tile writes its byte in every launch.  d3m_fit_loss_records writes every record and
+     * refuses a struct with tile_void set. */
+    const unsigned char* tile_void;
 };
 #define D3M_FIT_FINISH_DEFERRED 2
 #define D3M_FIT_POOLED 4
 /* ... or, should the backward pass not come that way after all, by this call (the ticket must still be zero: one finish). */
+/* tile_void of a set of targets (see struct d3m_fit_targets): batch_size * ceil(image_size / 16)^2 bytes, written. */
+int d3m_fit_target_summary(const float* rgb_target, const float* depth_target, const float* alpha_target, const float* mask,
+                           unsigned char* tile_void, int batch_size, int image_size, d3m_stream_t stream);
+/* Tile edge of the records form of the objective's pass (A/B runs and tests): -1 = by the launch's size (16 up to 4 M
+ * pixels, 32 above), 0 = always 16, 1 = always 32.  Anything else: D3M_ERR_INVALID, no change.  The forward and the
+ * backward pass of a step must run under the same setting. */
+int d3m_set_fit_tile_form(int form);
+int d3m_get_fit_tile_form(void);
 int d3m_fit_finish(const d3m_fit_targets* fit, int batch_size, int image_size, d3m_stream_t stream);
-/* scratch: totals | partial sums | group sums | ticket. */
+/* scratch: totals | partial sums | group sums | ticket | void tiles: the views' backgrounds and one byte per tile. */
 size_t d3m_render_fit_scratch_floats(int batch_size, int image_size);
 size_t d3m_render_fit_scratch_clear_range(int batch_size, int image_size, size_t* offset_floats);   /* returns a count of floats */
+/* offset (in floats) of the void-tile flags a records-form pass with fit->tile_void leaves in the scratch: one byte per tile */
+size_t d3m_render_fit_scratch_tile_void_offset(int batch_size, int image_size);
 /* The same objective evaluated on FINISHED images -- rgb [B,3,S,S], depth / alpha [B,S,S], row 0 = top: what
  * d3m_render_lit_epilogue wrote as rgb_out / depth_out / alpha_out without anti-aliasing -- with its gradient left as the
  * edge gradient's per-pixel records, exactly as the fused pass leaves them (fit->edge_grad, edge_dot, edge_nz_* zeroed by
