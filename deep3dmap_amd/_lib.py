@@ -212,6 +212,10 @@ _SIGNATURES = {
     "d3m_pose_scratch_floats": (_SZ, [_I, _I]),
     "d3m_pose_tree_constants": (None, [ctypes.POINTER(_I)]),
     "d3m_pose_backward": (_I, [_P, _I, _P, _I, _F, _F, _F, _P, _I, _P, _P, _P, _P, _SZ, _P, _P, _I, _I, _P]),
+    "d3m_smooth_shade_forward": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _SZ, _P, _P, _P, _I, _I, _I, _P]),
+    "d3m_smooth_shade_scratch_floats": (_SZ, [_I, _I, _I, _I, _I]),
+    "d3m_smooth_shade_backward": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _SZ, _P, _P,
+                                       _P, _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -13,6 +13,7 @@
 #include "d3m_mesh_reg.h"
 #include "d3m_morphable.h"
 #include "d3m_pose.h"
+#include "d3m_smooth_shade.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -2415,6 +2416,105 @@ D3M_EXPORT int d3m_pose_backward(const float* vertices, int vertices_batch, cons
                vertices, vertices_batch, pose, pose_stride, translation_scale, angle_limit, landmarks, num_landmarks,
                grad_landmark_points, (const float*)scratch, parts, grad_vertices, grad_pose, batch_size, num_vertices,
                pose_blocks);
+    return check_launch();
+}
+
+// Smooth vertex normals and spherical-harmonic vertex shading (d3m_smooth_shade.h), and the fixed-order adjoint.
+static bool smooth_shade_sizes(int B, int vb, int cb, int sb, int V, int F, bool with_colors) {
+    if (B < 1 || B > 65535 || V < 1 || F < 1 || (long)F * 3 > 0x7FFFFFFF || (long)B * V * 3 >= 0x80000000L) return false;
+    if (vb != 1 && vb != B) return false;
+    if (!with_colors) return vb == B;
+    return (cb == 1 || cb == B) && (sb == 1 || sb == B);
+}
+
+D3M_EXPORT size_t d3m_smooth_shade_scratch_floats(int batch_size, int vertices_batch, int num_vertices, int num_tri,
+                                                  int num_chunks) {
+    if (!smooth_shade_sizes(batch_size, vertices_batch, 1, 1, num_vertices, num_tri, true) || num_chunks < 0) return 0;
+    const size_t vb = vertices_batch;
+    return vb * num_vertices * 3 + (size_t)batch_size * ss_parts(num_vertices) * SS_SUMS + vb * num_tri * 9 +
+           vb * num_chunks * 3;
+}
+
+D3M_EXPORT int d3m_smooth_shade_forward(const float* vertices, int vertices_batch, const float* colors, int colors_batch,
+                                        const float* sh, int sh_batch, const int32_t* tri, const int32_t* adj_offsets,
+                                        const int32_t* adj_items, const int32_t* chunks, int num_chunks,
+                                        const int32_t* long_rows, const int32_t* long_chunk_ptr, int num_long_rows,
+                                        int long_row, float* scratch, size_t scratch_floats, float* shaded, float* normals,
+                                        float* lengths, int batch_size, int num_vertices, int num_tri, d3m_stream_t stream) {
+    if (!vertices || !tri || !adj_offsets || !adj_items || !scratch || !normals || !lengths) return D3M_ERR_INVALID;
+    if (colors ? (!sh || !shaded) : shaded != nullptr) return D3M_ERR_INVALID;
+    if (!smooth_shade_sizes(batch_size, vertices_batch, colors_batch, sh_batch, num_vertices, num_tri, colors != nullptr) ||
+        long_row < 0)
+        return D3M_ERR_INVALID;
+    if (!long_rows_ok(chunks, num_chunks, long_rows, long_chunk_ptr, num_long_rows, scratch)) return D3M_ERR_INVALID;
+    const int vb = vertices_batch, V = num_vertices;
+    const long F = num_tri;
+    const size_t n_normals = (size_t)vb * F * 3;
+    if (scratch_floats < n_normals + (size_t)vb * num_chunks * 3) return D3M_ERR_INVALID;
+    if (misaligned4(vertices) || misaligned4(colors) || misaligned4(sh) || misaligned4(scratch) || misaligned4(shaded) ||
+        misaligned4(normals) || misaligned4(lengths))
+        return D3M_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    float* face_normals = scratch;
+    float* partials = scratch + n_normals;
+    const SmoothAdj adj = {adj_offsets, adj_items, {(const int2*)chunks, long_rows, long_chunk_ptr, num_chunks, num_long_rows, long_row}};
+    LAUNCH("k_smooth_shade_face_normals", k_smooth_shade_face_normals, dim3(blocks_for(F, SS_BLOCK), vb), dim3(SS_BLOCK), st,
+           vertices, tri, face_normals, V, F);
+    if (num_chunks > 0)
+        LAUNCH("k_smooth_shade_normal_chunks", k_smooth_shade_chunks<3>, dim3(num_chunks, vb), dim3(RG_BLOCK), st, adj_items,
+               (const int2*)chunks, num_chunks, (const float*)face_normals, F, partials);
+    LAUNCH("k_smooth_shade_vertices", k_smooth_shade_vertices, dim3(blocks_for((long)V, SS_BLOCK), vb), dim3(SS_BLOCK), st, adj,
+           (const float*)face_normals, (const float*)partials, colors, colors_batch, sh, sh_batch, shaded, normals, lengths,
+           batch_size, vb, V, F);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_smooth_shade_backward(const float* vertices, int vertices_batch, const float* colors, int colors_batch,
+                                         const float* sh, int sh_batch, const float* normals, const float* lengths,
+                                         const float* grad_shaded, const float* grad_normals, const int32_t* tri,
+                                         const int32_t* adj_offsets, const int32_t* adj_items, const int32_t* chunks,
+                                         int num_chunks, const int32_t* long_rows, const int32_t* long_chunk_ptr,
+                                         int num_long_rows, int long_row, float* scratch, size_t scratch_floats,
+                                         float* grad_vertices, float* grad_colors, float* grad_sh, int batch_size,
+                                         int num_vertices, int num_tri, d3m_stream_t stream) {
+    if (!vertices || !normals || !lengths || !tri || !adj_offsets || !adj_items || !scratch) return D3M_ERR_INVALID;
+    if (!grad_vertices && !grad_colors && !grad_sh) return D3M_ERR_INVALID;
+    if (colors ? !sh : (grad_shaded != nullptr)) return D3M_ERR_INVALID;
+    if (!grad_shaded && (grad_colors || grad_sh)) return D3M_ERR_INVALID;      // (zeros: the caller leaves them out)
+    if (!smooth_shade_sizes(batch_size, vertices_batch, colors_batch, sh_batch, num_vertices, num_tri, colors != nullptr) ||
+        long_row < 0)
+        return D3M_ERR_INVALID;
+    if (!long_rows_ok(chunks, num_chunks, long_rows, long_chunk_ptr, num_long_rows, scratch)) return D3M_ERR_INVALID;
+    if (scratch_floats < d3m_smooth_shade_scratch_floats(batch_size, vertices_batch, num_vertices, num_tri, num_chunks))
+        return D3M_ERR_INVALID;
+    if (misaligned4(vertices) || misaligned4(colors) || misaligned4(sh) || misaligned4(normals) || misaligned4(lengths) ||
+        misaligned4(grad_shaded) || misaligned4(grad_normals) || misaligned4(scratch) || misaligned4(grad_vertices) ||
+        misaligned4(grad_colors) || misaligned4(grad_sh))
+        return D3M_ERR_INVALID;
+    const int B = batch_size, vb = vertices_batch, V = num_vertices, parts = ss_parts(V);
+    const long F = num_tri;
+    hipStream_t st = (hipStream_t)stream;
+    float* g_s = scratch;
+    float* sh_partial = g_s + (size_t)vb * V * 3;
+    float* terms = sh_partial + (size_t)B * parts * SS_SUMS;
+    float* partials = terms + (size_t)vb * F * 9;
+    const SmoothAdj adj = {adj_offsets, adj_items, {(const int2*)chunks, long_rows, long_chunk_ptr, num_chunks, num_long_rows, long_row}};
+    const int walk_sets = B > 1 && (vb == 1 || (colors && colors_batch == 1)) ? 1 : 0;
+    LAUNCH("k_smooth_shade_backward_vertices", k_smooth_shade_backward_vertices, dim3(parts, walk_sets ? 1 : B),
+           dim3(SS_BLOCK), st, colors, colors_batch, sh, sh_batch, normals, lengths, vb, grad_shaded, grad_normals, grad_colors,
+           grad_vertices ? g_s : (float*)nullptr, grad_sh ? sh_partial : (float*)nullptr, B, V, walk_sets);
+    if (grad_sh)
+        LAUNCH("k_smooth_shade_backward_finish", k_smooth_shade_backward_finish, dim3(blocks_for((long)sh_batch * SS_SUMS, SS_BLOCK)),
+               dim3(SS_BLOCK), st, (const float*)sh_partial, parts, grad_sh, sh_batch, B);
+    if (grad_vertices) {
+        LAUNCH("k_smooth_shade_backward_faces", k_smooth_shade_backward_faces, dim3(blocks_for(F, SS_BLOCK), vb), dim3(SS_BLOCK),
+               st, vertices, tri, (const float*)g_s, terms, V, F);
+        if (num_chunks > 0)
+            LAUNCH("k_smooth_shade_term_chunks", k_smooth_shade_chunks<1>, dim3(num_chunks, vb), dim3(RG_BLOCK), st, adj_items,
+                   (const int2*)chunks, num_chunks, (const float*)terms, F * 3, partials);
+        LAUNCH("k_smooth_shade_backward_rows", k_smooth_shade_backward_rows, dim3(blocks_for((long)V * 3, SS_BLOCK), vb),
+               dim3(SS_BLOCK), st, adj, (const float*)terms, (const float*)partials, grad_vertices, V, F);
+    }
     return check_launch();
 }
 

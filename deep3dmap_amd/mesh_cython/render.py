@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from ..neural_renderer.smooth_shading import sh_basis
 
 _workspace = {}
 
@@ -70,6 +71,46 @@ def get_norm_direction(vertices, triangles):
                                              _lib.ptr(ws), ws.numel(), _lib.stream_ptr()), "d3m_mesh_get_norm_direction")
     _lib.check(L.d3m_mesh_normalize(_lib.ptr(norm), v.shape[1], _lib.stream_ptr()), "d3m_mesh_normalize")
     return _out(norm, np_in)
+
+
+def illumination_fit(image, vertices, texture, norm, vis_ind, lamb=10, max_iter=3):
+    """The part of fit_illumination after the normals, on float64 torch tensors of any one device: image [h, w, c], vertices
+    [3, nver], texture [c, nver], norm [3, nver] (unit normals), vis_ind [n] (integer).  Returns the appearance [c, nver]."""
+    if int(max_iter) < 1:
+        raise ValueError("max_iter must be at least 1")
+    h, w, c = image.shape
+    # the pixel under every vertex: clamped to the image, then rounded half to even as numpy rounds (on a copy)
+    px = vertices[0].clamp(0, w - 1).round().long()
+    py = vertices[1].clamp(0, h - 1).round().long()
+    pixel = image[py, px, :].T                                  # [c, nver]
+    harmonic = sh_basis(norm.T)                                 # [nver, 9]
+    vis = vis_ind.long()
+    n = vis.numel()
+    tex, seen = texture[:, vis], pixel[:, vis]                  # [c, n]
+    A = (tex[:, :, None] * harmonic[vis][None]).reshape(c * n, 9)
+    light = (tex * seen).sum(1) / (tex * tex).sum(1)            # per channel: the least-squares scale of albedo alone
+    left = A.T @ A + lamb * torch.eye(9, dtype=A.dtype, device=A.device)
+    for _ in range(int(max_iter)):
+        alpha = torch.linalg.inv(left) @ (A.T @ (seen / light[:, None]).reshape(c * n, 1))      # the ridge solve
+        lit = (A @ alpha).reshape(c, n)
+        light = (lit * seen).sum(1) / (lit * lit).sum(1)
+    appearance = torch.stack([((harmonic * texture[k][:, None]) @ (alpha * light[k]))[:, 0] for k in range(c)])
+    return appearance.clamp(0, 1)
+
+
+def fit_illumination(image, vertices, texture, triangles, vis_ind, lamb=10, max_iter=3):
+    """MP:31-122: fits a 9-term spherical-harmonic light (a ridge solve of weight `lamb`, alternated max_iter times with a
+    per-channel light scale) to the image pixels under the visible vertices `vis_ind`, and returns the albedo `texture`
+    [c, nver] lit by it at every vertex, clamped to [0, 1].  image [h, w, c], vertices [3, nver] in pixel coordinates.  The
+    normals are get_norm_direction's, the basis is nr.sh_basis.  The reference clamps the caller's vertices[:2] to the image
+    in place (through a numpy view); this function leaves `vertices` unchanged."""
+    img, np_in = _in(image, torch.float64)
+    v, _ = _in(vertices, torch.float64)
+    tex, _ = _in(texture, torch.float64)
+    t, _ = _in(triangles, torch.int32)
+    vis = torch.as_tensor(vis_ind).to(v.device)
+    norm = get_norm_direction(v, t)
+    return _out(illumination_fit(img, v, tex, norm, vis, lamb, max_iter), np_in)
 
 
 def render_colors(vertices, triangles, colors, h, w, c=3, isBG=False):

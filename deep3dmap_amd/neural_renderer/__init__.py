@@ -10,6 +10,7 @@ from .pose import PoseHead, PosedPoints, pose_vertices
 from .rasterize import (Rasterize, RasterizeFunction, rasterize, rasterize_depth, rasterize_rgbad,
                         rasterize_silhouettes)
 from .renderer import Renderer
+from .smooth_shading import SHLight, sh_basis, sh_vertex_colors, vertex_normals
 from .uv_textures import UVTextures, textures_from_image
 from .vertex_colors import VertexColors, textures_from_vertex_colors
 

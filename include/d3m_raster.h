@@ -971,6 +971,47 @@ int d3m_pose_backward(const float* vertices, int vertices_batch, const float* po
                       float angle_limit, float uv_size, const int32_t* landmarks, int num_landmarks, const float* grad_posed,
                       const float* grad_uv, const float* grad_landmark_points, float* scratch, size_t scratch_floats,
                       float* grad_vertices, float* grad_pose, int batch_size, int num_vertices, d3m_stream_t stream);
+/* Smooth per-vertex normals of an indexed mesh and a 9-term spherical-harmonic light on per-vertex albedo, with the adjoint
+ * (no float atomics, the same bits on every run; plain f32; csrc/d3m_smooth_shade.h states the order of every sum).
+ * vertices [vertices_batch, V, 3], colors [colors_batch, V, 3], sh [sh_batch, 3, 9]: each batch is 1 (shared by all sets) or
+ * batch_size.  tri [F, 3] i32 and the adjacency (adj_offsets [V+1], adj_items [3 F], the long-row tables) are those of
+ * d3m_vertex_color_textures_backward (every index in range: the caller checks).
+ *   N_f = (x1 - x0) x (x2 - x0);  s[b,v] = the sum of N_f over v's items in ascending order;  r = |s|;  n = s / max(r, 1e-6)
+ *   H(n) = (a0, a1 nx, a1 ny, a1 nz, a2 (2 nz^2 - nx^2 - ny^2), a3 ny nz, a3 nx nz, a3 nx ny, a4 (nx^2 - ny^2)) with
+ *   a0 = sqrt(1/4pi), a1 = sqrt(3/4pi), a2 = a1 / 2, a3 = 3 sqrt(5/12pi), a4 = a3 / 2
+ *   shaded[b,v,k] = colors[b,v,k] * sum_j sh[b,k,j] H_j(n[b,v])
+ * WRITES every element of normals [vertices_batch, V, 3] (a vertex of no face: 0), lengths [vertices_batch, V] (r) and shaded
+ * [batch_size, V, 3].  colors NULL: the normals only (shaded NULL, batch_size == vertices_batch; sh is not read).  At most
+ * three launches (k_smooth_shade_face_normals, k_smooth_shade_normal_chunks on a mesh with long rows, k_smooth_shade_vertices).
+ * scratch_floats >= d3m_smooth_shade_scratch_floats().
+ * D3M_ERR_INVALID, before any launch: NULL vertices / tri / adj_offsets / adj_items / scratch / normals / lengths, colors
+ * without sh or shaded, shaded without colors, batch_size outside [1, 65535], a batch that is neither 1 nor batch_size, a
+ * size <= 0, 3 F beyond int32, batch_size * V * 3 >= 2^31, long_row < 0, long rows without chunks, a scratch that is too
+ * small, a pointer that is not 4-byte aligned. */
+int d3m_smooth_shade_forward(const float* vertices, int vertices_batch, const float* colors, int colors_batch,
+                             const float* sh, int sh_batch, const int32_t* tri, const int32_t* adj_offsets,
+                             const int32_t* adj_items, const int32_t* chunks, int num_chunks, const int32_t* long_rows,
+                             const int32_t* long_chunk_ptr, int num_long_rows, int long_row, float* scratch,
+                             size_t scratch_floats, float* shaded, float* normals, float* lengths, int batch_size,
+                             int num_vertices, int num_tri, d3m_stream_t stream);
+/* Floats of scratch the two entry points need (0 for sizes they refuse): vertices_batch * (3 V + 9 F + 3 num_chunks) +
+ * batch_size * min(ceil(V / 256), 64) * 27. */
+size_t d3m_smooth_shade_scratch_floats(int batch_size, int vertices_batch, int num_vertices, int num_tri, int num_chunks);
+/* The adjoint of d3m_smooth_shade_forward, from its inputs and its outputs normals and lengths.  grad_shaded [batch_size, V,
+ * 3] and grad_normals [vertices_batch, V, 3] may each be NULL (zeros).  WRITES every element of grad_vertices
+ * [vertices_batch, V, 3], grad_colors [colors_batch, V, 3] and grad_sh [sh_batch, 3, 9]; each may be NULL (not computed), not
+ * all three; the gradient of a shared input is summed over the sets in ascending order.  grad_colors and grad_sh need
+ * grad_shaded.  At most five launches (k_smooth_shade_backward_vertices, k_smooth_shade_backward_finish for grad_sh, and for
+ * grad_vertices k_smooth_shade_backward_faces, k_smooth_shade_term_chunks on a mesh with long rows, k_smooth_shade_backward_rows).
+ * D3M_ERR_INVALID, before any launch: what d3m_smooth_shade_forward refuses of the inputs, NULL normals / lengths, all three
+ * outputs NULL, grad_colors or grad_sh without grad_shaded, grad_shaded without colors. */
+int d3m_smooth_shade_backward(const float* vertices, int vertices_batch, const float* colors, int colors_batch,
+                              const float* sh, int sh_batch, const float* normals, const float* lengths,
+                              const float* grad_shaded, const float* grad_normals, const int32_t* tri,
+                              const int32_t* adj_offsets, const int32_t* adj_items, const int32_t* chunks, int num_chunks,
+                              const int32_t* long_rows, const int32_t* long_chunk_ptr, int num_long_rows, int long_row,
+                              float* scratch, size_t scratch_floats, float* grad_vertices, float* grad_colors,
+                              float* grad_sh, int batch_size, int num_vertices, int num_tri, d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row

@@ -1,0 +1,439 @@
+"""Smooth shading on the device (neural_renderer/smooth_shading.py, csrc/d3m_smooth_shade.h): accuracy against the float64
+restatement of tests/smooth_shading_scenes.py within max(8 E32, 16 2^-24 max|ref|) per tensor (E32: the float32 CPU
+restatement's own deviation, computed here), needles through the fixed trees, bit identities (two runs, batched against
+unbatched, shared against expanded, eager against a captured step), the kernels that run, the chain into a render, and
+mesh_cython.fit_illumination against the reference's outputs."""
+import functools
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import smooth_shading_scenes as S
+from conftest import kernels_launched
+from test_smooth_shading_host import FIT_TOL, GOLDEN
+
+pytestmark = pytest.mark.gpu
+FORWARD = {"k_smooth_shade_face_normals", "k_smooth_shade_vertices"}
+BACKWARD = {"k_smooth_shade_backward_vertices", "k_smooth_shade_backward_finish", "k_smooth_shade_backward_faces",
+            "k_smooth_shade_backward_rows"}
+CHUNKS = {"k_smooth_shade_normal_chunks", "k_smooth_shade_term_chunks"}
+ULP = 2.0 ** -23
+
+
+def _nr():
+    from deep3dmap_amd import neural_renderer as nr
+    return nr
+
+
+def _ss():
+    from deep3dmap_amd.neural_renderer import smooth_shading as ss
+    return ss
+
+
+def _bits(t):
+    return t.detach().contiguous().view(torch.int32)
+
+
+def _same(a, b):
+    return a.shape == b.shape and bool(torch.equal(_bits(a), _bits(b)))
+
+
+def _dev(t):
+    return t.detach().float().cuda()
+
+
+@functools.lru_cache(maxsize=None)
+def _fan():
+    v, f, notes = S.fan_mesh()
+    return v, torch.from_numpy(f), notes
+
+
+@functools.lru_cache(maxsize=None)
+def _case(B):
+    """the inputs (float64, on the host) of the accuracy case with B sets, its float64 reference and its tolerances"""
+    v, faces, _ = _fan()
+    inputs = S.case_inputs(v, B, 5)
+    ref64 = {k: t.detach() for k, t in S.reference(inputs[0], faces, *inputs[1:]).items()}
+    ref32 = S.reference(inputs[0].float(), faces, *(t.float() for t in inputs[1:]))
+    return inputs, ref64, S.tolerances(ref64, ref32)
+
+
+def _run(x, faces, colors, sh, g, g_normals, cache=None):
+    """the node forward and backward on device tensors -> dict of the five checked tensors"""
+    nr = _nr()
+    leaves = [t.clone().requires_grad_(True) for t in (x, colors, sh)]
+    shaded, normals = nr.sh_vertex_colors(leaves[0], faces, leaves[1], leaves[2], cache=cache, return_normals=True)
+    loss = (shaded * g).sum() if g_normals is None else (shaded * g).sum() + (normals * g_normals).sum()
+    loss.backward()
+    return dict(normals=normals.detach(), shaded=shaded.detach(), g_x=leaves[0].grad, g_colors=leaves[1].grad,
+                g_sh=leaves[2].grad)
+
+
+@functools.lru_cache(maxsize=None)
+def _device_case(B):
+    """the accuracy case on the device: (device inputs, faces, results); B = 1 runs unbatched"""
+    inputs, _, _ = _case(B)
+    faces = _fan()[1].cuda()
+    d = [_dev(t if B > 1 else t[0]) for t in inputs]
+    return d, faces, _run(d[0], faces, *d[1:])
+
+
+# ---- 1. accuracy --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("B", [1, 3])
+def test_accuracy_on_the_fan_mesh(B):
+    _, ref64, tol = _case(B)
+    _, _, got = _device_case(B)
+    notes = _fan()[2]
+    V = ref64["normals"].shape[1]
+    report = []
+    for name, ref in ref64.items():
+        out = got[name].cpu().double()
+        assert tuple(out.shape) == (tuple(ref.shape) if B > 1 else tuple(ref.shape[1:])), name
+        err = float((out.reshape(ref.shape) - ref).abs().max())
+        bound, e32 = tol[name]
+        report.append((name, err, bound, err / e32 if e32 else math.inf))
+    print(f"B={B} V={V}: " + ", ".join(f"{n} err {e:.2e} bound {b:.2e} err/E32 {r:.2f}" for n, e, b, r in report))
+    for name, err, bound, _ in report:
+        assert err <= bound, (name, err, bound)
+    # the vertex of no face: exact zeros, forward and backward (its shaded colour is colors * sh[k,0] a0)
+    u = notes["unused"]
+    normals, g_x = got["normals"].reshape(-1, V, 3), got["g_x"].reshape(-1, V, 3)
+    assert bool((normals[:, u] == 0).all()) and bool((g_x[:, u] == 0).all())
+    lengths = normals.norm(dim=-1)
+    assert float((lengths[:, :u] - 1).abs().max()) < 1e-5
+
+
+def test_the_doubled_face_contributes_nothing():
+    (x, colors, sh, g, gn), faces, with_face = _device_case(1)
+    notes = _fan()[2]
+    a, b = notes["doubled"]
+    keep = torch.ones(faces.shape[0], dtype=torch.bool)
+    keep[notes["doubled_face"]] = False
+    without = _run(x, faces[keep.cuda()].contiguous(), colors, sh, g, gn)
+    # forward: its normal is exactly zero, and adding zero changes no bit
+    assert _same(with_face["normals"], without["normals"]) and _same(with_face["shaded"], without["shaded"])
+    assert _same(with_face["g_colors"], without["g_colors"]) and _same(with_face["g_sh"], without["g_sh"])
+    # backward: a's two terms are t and -t (they cancel up to the rounding of the row's sum), b's is zero
+    rest = torch.ones(x.shape[0], dtype=torch.bool)
+    rest[a] = False
+    assert _same(with_face["g_x"][rest.cuda()], without["g_x"][rest.cuda()])
+    bound = _case(1)[2]["g_x"][0]
+    assert float((with_face["g_x"][a] - without["g_x"][a]).abs().max()) <= bound
+
+
+def _raw(B, nan_fill):
+    """the C entry points called raw on the B-set case with every output (and the scratch) pre-filled"""
+    from deep3dmap_amd import _lib
+    ss = _ss()
+    d, faces, _ = _device_case(B)
+    x, colors, sh, g, gn = (ss._batch(t) for t in d)
+    A = ss.vertex_adjacency(faces, x.shape[1])
+    V, L = x.shape[1], _lib.lib()
+    new = lambda *shape: torch.full(shape, nan_fill, dtype=torch.float32, device="cuda")       # noqa: E731
+    n = int(L.d3m_smooth_shade_scratch_floats(B, B, V, A.num_faces, A.chunks.shape[0]))
+    out = dict(shaded=new(B, V, 3), normals=new(B, V, 3), lengths=new(B, V), g_x=new(B, V, 3), g_colors=new(B, V, 3),
+               g_sh=new(B, 3, 9))
+    scratch = new(n)
+    _lib.check(L.d3m_smooth_shade_forward(_lib.ptr(x), B, _lib.ptr(colors), B, _lib.ptr(sh), B, *ss._adjacency_args(A),
+                                          _lib.ptr(scratch), n, _lib.ptr(out["shaded"]), _lib.ptr(out["normals"]),
+                                          _lib.ptr(out["lengths"]), B, V, A.num_faces, _lib.stream_ptr()), "forward")
+    scratch2 = new(n)
+    _lib.check(L.d3m_smooth_shade_backward(_lib.ptr(x), B, _lib.ptr(colors), B, _lib.ptr(sh), B, _lib.ptr(out["normals"]),
+                                           _lib.ptr(out["lengths"]), _lib.ptr(g), _lib.ptr(gn), *ss._adjacency_args(A),
+                                           _lib.ptr(scratch2), n, _lib.ptr(out["g_x"]), _lib.ptr(out["g_colors"]),
+                                           _lib.ptr(out["g_sh"]), B, V, A.num_faces, _lib.stream_ptr()), "backward")
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("B", [1, 3])
+def test_every_output_element_is_written(B):
+    _, _, got = _device_case(B)
+    out = _raw(B, float("nan"))
+    for name, t in out.items():
+        assert not bool(torch.isnan(t).any()), name
+        if name != "lengths":
+            assert _same(t.reshape(got[name].shape), got[name]), name
+
+
+# ---- 2. needles through the fixed trees ------------------------------------------------------------------------------------
+def _needle_sh(x, faces, colors, sh, vertices):
+    """g non-zero at one vertex only: g_sh must be that vertex's single term gL_k H_j(n) to 4 ulp, never lost"""
+    ss = _ss()
+    V = x.shape[0]
+    A = ss.vertex_adjacency(faces, V)
+    xb, cb, sb = x[None].contiguous(), colors[None].contiguous(), sh[None].contiguous()
+    _, normals, lengths = ss.forward(xb, cb, sb, A)
+    H = S.basis(normals[0].cpu())                               # float32, the kernel's association
+    value = torch.tensor([0.75, -1.25, 0.5])
+    for v in vertices:
+        g = torch.zeros(1, V, 3)
+        g[0, v] = value
+        _, _, g_sh = ss.backward(xb, cb, sb, normals, lengths, A, g.cuda(), None, need_vertices=False, need_colors=False)
+        want = (value * colors[v].cpu())[:, None] * H[v][None, :]
+        got = g_sh[0].cpu()
+        assert float(want[:, 0].abs().min()) > 0, v
+        assert bool(((got - want).abs() <= 4 * ULP * want.abs()).all()), (v, got, want)
+
+
+def test_needles_through_the_sh_tree_on_the_fan_mesh():
+    (x, colors, sh, _, _), faces, _ = _device_case(1)
+    V = x.shape[0]
+    assert V > 256
+    _needle_sh(x, faces, colors, sh, [0, 63, 64, 255, 256, V - 1])
+
+
+def test_needles_through_the_sh_tree_beyond_the_cap_of_parts():
+    from deep3dmap_amd.neural_renderer.pose import MAX_PARTS, VERTICES_PER_CHUNK
+    v, f = S.grid_mesh(129)
+    V = v.shape[0]
+    assert V == 16641 > VERTICES_PER_CHUNK * MAX_PARTS == 16384          # the lanes stride
+    gen = torch.Generator().manual_seed(7)
+    colors = (0.2 + 0.7 * torch.rand(V, 3, generator=gen)).cuda()
+    sh = (torch.rand(3, 9, generator=gen) - 0.5).cuda()
+    _needle_sh(torch.from_numpy(v).float().cuda(), torch.from_numpy(f).cuda(), colors, sh, [0, 16383, 16384, 16640])
+
+
+def test_needles_on_the_smallest_meshes():
+    gen = torch.Generator().manual_seed(8)
+    # one vertex, one (degenerate) face: n = 0, only the constant term is lit
+    x1, f1 = torch.tensor([[0.3, -0.2, 0.9]]).cuda(), torch.tensor([[0, 0, 0]]).cuda()
+    _needle_sh(x1, f1, (0.2 + 0.7 * torch.rand(1, 3, generator=gen)).cuda(), (torch.rand(3, 9, generator=gen) - 0.5).cuda(), [0])
+    # one triangle: a needle at each vertex leaves the other two vertices' colour gradients zero
+    nr = _nr()
+    x3 = torch.tensor([[0.0, 0.0, 0.0], [1.0, 0.1, 0.0], [0.2, 0.9, 0.3]]).cuda()
+    f3 = torch.tensor([[0, 1, 2]]).cuda()
+    c3 = (0.2 + 0.7 * torch.rand(3, 3, generator=gen)).cuda()
+    s3 = (torch.rand(3, 9, generator=gen) - 0.5).cuda()
+    _needle_sh(x3, f3, c3, s3, [0, 1, 2])
+    for v in range(3):
+        c = c3.clone().requires_grad_(True)
+        g = torch.zeros(3, 3, device="cuda")
+        g[v] = 1.0
+        nr.sh_vertex_colors(x3, f3, c, s3).backward(g)
+        others = [i for i in range(3) if i != v]
+        assert bool((c.grad[others] == 0).all()) and bool((c.grad[v] != 0).all())
+
+
+def blade_mesh():
+    """Three hubs of LONG_ROW, LONG_ROW + 1 and 2 CHUNK + 1 blades: blade k of a hub is a triangle of the hub (at corner slot
+    k % 3) and two vertices of its own, so a gradient at one of those reaches exactly one item of the hub's row -- item k, the
+    hub's faces being listed in blade order."""
+    from deep3dmap_amd.neural_renderer.row_gather import CHUNK, LONG_ROW
+    verts, faces, hubs = [], [], {}
+    for i, count in enumerate((LONG_ROW, LONG_ROW + 1, 2 * CHUNK + 1)):
+        hub = len(verts)
+        verts.append([3.0 * i, 0.0, 0.5])
+        hubs[hub] = (count, len(faces))
+        for k in range(count):
+            a = 2 * math.pi * k / count
+            p = len(verts)
+            verts += [[3.0 * i + math.cos(a), math.sin(a), 0.01 * (k % 7)], [3.0 * i + math.cos(a + 0.4), math.sin(a + 0.4), 0.0]]
+            tri = [hub, p, p + 1]
+            faces.append(tri[-(k % 3):] + tri[:-(k % 3)] if k % 3 else tri)
+    return np.array(verts, np.float32), np.array(faces, np.int64), hubs
+
+
+def test_needles_through_the_hub_rows_of_the_vertex_gradient():
+    from deep3dmap_amd.neural_renderer.row_gather import CHUNK
+    ss = _ss()
+    v, f, hubs = blade_mesh()
+    V = v.shape[0]
+    x, faces = torch.from_numpy(v)[None].cuda(), torch.from_numpy(f).cuda()
+    A = ss.vertex_adjacency(faces, V)
+    assert A.long_rows.cpu().tolist() == sorted(h for h, (c, _) in hubs.items() if c > ss.LONG_ROW)
+    _, normals, lengths = ss.forward(x, None, None, A)
+    n, r = normals[0].cpu().numpy(), lengths[0].cpu().numpy()
+    e = np.array([0.5, -0.75, 1.25], np.float32)
+    for hub, (count, first_face) in hubs.items():
+        ks = sorted({0, 1, count - 2, count - 1} | ({255, 256, CHUNK - 1, CHUNK, 2 * CHUNK - 1} if count > 2 * CHUNK else set()))
+        for k in ks:
+            face = f[first_face + k]
+            slot = k % 3
+            assert face[slot] == hub
+            p = int(face[(slot + 1) % 3])                       # a vertex of this blade alone
+            g_n = torch.zeros(1, V, 3)
+            g_n[0, p] = torch.from_numpy(e)
+            g_x, _, _ = ss.backward(x, None, None, normals, lengths, A, None, g_n.cuda())
+            # the hub's single term, in float32 with the kernel's association
+            dot = (n[p, 0] * e[0] + n[p, 1] * e[1]) + n[p, 2] * e[2]
+            gN = (e - n[p] * dot) / r[p]
+            x0, x1, x2 = (v[face[c]] for c in range(3))
+            ea, eb = x1 - x0, x2 - x0
+            cross = lambda a, b: np.array([a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]],  # noqa: E731
+                                          np.float32)
+            t1, t2 = cross(eb, gN), cross(gN, ea)
+            want = (-(t1 + t2), t1, t2)[slot]
+            got = g_x[0, hub].cpu().numpy()
+            assert np.abs(want).max() > 1e-3 and np.abs(got - want).max() <= 4 * ULP * np.abs(want).max(), (hub, k, got, want)
+
+
+# ---- 3. bit identities ------------------------------------------------------------------------------------------------------
+def test_two_runs_batched_and_unbatched_and_vertex_normals_agree_bit_for_bit():
+    nr = _nr()
+    (x, colors, sh, g, gn), faces, first = _device_case(3)
+    again = _run(x, faces, colors, sh, g, gn)
+    for name in first:
+        assert _same(first[name], again[name]), name
+    for b in range(3):
+        one = _run(x[b], faces, colors[b], sh[b], g[b], gn[b])
+        for name in first:
+            assert _same(first[name][b], one[name]), (name, b)
+    assert _same(nr.vertex_normals(x, faces), first["normals"])
+    assert _same(nr.vertex_normals(x[1], faces), first["normals"][1])
+    # the normals' own gradient, without colours: the vertex gradient of a loss on the normals alone
+    leaf = x.clone().requires_grad_(True)
+    (nr.vertex_normals(leaf, faces) * gn).sum().backward()
+    lit = x.clone().requires_grad_(True)
+    (nr.sh_vertex_colors(lit, faces, colors, sh, return_normals=True)[1] * gn).sum().backward()
+    assert float(leaf.grad.abs().max()) > 0 and _same(leaf.grad, lit.grad)
+
+
+@pytest.mark.parametrize("shared", ["vertices", "colors", "sh", "vertices+colors", "colors+sh", "vertices+colors+sh"])
+def test_a_shared_input_gives_the_bits_of_the_same_input_expanded(shared):
+    B = 3
+    (x, colors, sh, g, _), faces, _ = _device_case(B)
+    tol = _case(B)[2]
+    names = shared.split("+")
+    pick = dict(vertices=x, colors=colors, sh=sh)
+    full = {k: (t[1:2].expand(B, *t.shape[1:]).contiguous() if k in names else t) for k, t in pick.items()}
+    part = {k: (t[1] if k in names else t) for k, t in pick.items()}
+    g_out = g if len(names) < 3 else g[1]                       # (all three shared: one set, outputs without B)
+    if len(names) == 3:
+        full = {k: t[1:2].contiguous() for k, t in pick.items()}
+    want = _run(full["vertices"], faces, full["colors"], full["sh"], g_out if len(names) < 3 else g[1:2], None)
+    got = _run(part["vertices"], faces, part["colors"], part["sh"], g_out, None)
+    if len(names) == 3:
+        assert got["shaded"].shape == tuple(x.shape[1:])
+        for name in got:
+            assert _same(got[name], want[name][0]), name
+        return
+    assert got["shaded"].shape == (B,) + tuple(x.shape[1:])
+    assert _same(got["shaded"], want["shaded"])
+    assert _same(got["normals"], want["normals"][1] if "vertices" in names else want["normals"])
+    for key, grad in (("vertices", "g_x"), ("colors", "g_colors"), ("sh", "g_sh")):
+        if key not in names:                                    # a per-set input: the expanded call's bits
+            assert _same(got[grad], want[grad]), grad
+            continue
+        # a shared input: the sum over the sets.  Each set's gradient holds the accuracy bound and B of them are added
+        # (the vertex gradient projects the summed normal gradient once: the same map, linear in it)
+        total = want[grad].double().sum(0)
+        bound = B * max(tol[grad][0], 16 * 2.0 ** -24 * float(total.abs().max()))
+        assert got[grad].shape == part[key].shape, grad
+        err = float((got[grad].double() - total).abs().max())
+        assert float(total.abs().max()) > 0 and err <= bound, (grad, err, bound)
+
+
+def test_a_captured_step_equals_its_eager_twin():
+    from deep3dmap_amd.graph import CapturedStep
+    nr = _nr()
+    (x, colors, sh, g, gn), faces, _ = _device_case(3)
+    light = nr.SHLight(3).cuda().requires_grad_(False)
+
+    def make():
+        return [t.clone().requires_grad_(True) for t in (x, colors, sh)]
+
+    def run(vx, vc, vs):
+        vx.grad = vc.grad = vs.grad = None
+        shaded, normals = light(vx, faces, vc, return_normals=True)
+        lit = nr.sh_vertex_colors(vx, faces, vc, vs, cache=light._adjacency)
+        # (gradients that depend on the inputs)
+        (((shaded + lit) ** 2 * g).sum() + (normals ** 2 * gn).sum()).backward()
+        return torch.cat([vx.grad.reshape(-1), vc.grad.reshape(-1), vs.grad.reshape(-1), lit.detach().reshape(-1)])
+
+    twin, live = make(), make()
+    first = run(*twin).clone()
+    assert float(first.abs().max()) > 0 and _same(run(*twin), first)
+    cs = CapturedStep(lambda: run(*live)).capture()
+    gen = torch.Generator().manual_seed(11)
+    for i in range(2):
+        deltas = [0.02 * (torch.rand(t.shape, generator=gen) - 0.5).cuda() for t in twin]
+        with torch.no_grad():
+            for t, u, d in zip(live, twin, deltas):
+                t.add_(d)
+                u.add_(d)
+        got = cs().clone()
+        torch.cuda.synchronize()
+        want = run(*twin)
+        assert not _same(want, first) and _same(got, want), i
+    cs.release()
+    assert len(light._adjacency) == 1
+
+
+# ---- 4. the kernels that run ------------------------------------------------------------------------------------------------
+def test_only_the_nodes_kernels_run_and_the_chunk_kernels_only_for_long_rows():
+    (x, colors, sh, g, gn), faces, _ = _device_case(3)           # (the adjacency is cached)
+    with kernels_launched() as k:
+        _run(x, faces, colors, sh, g, gn)
+    assert set(k.names) == FORWARD | BACKWARD | CHUNKS, k.names
+    assert all(k.times[name][0] == 1 for name in k.names), k.times
+    v, f = S.grid_mesh(20)
+    xg, fg = torch.from_numpy(v).float().cuda(), torch.from_numpy(f).cuda()
+    gen = torch.Generator().manual_seed(12)
+    cg, sg, gg = torch.rand(400, 3, generator=gen).cuda(), torch.rand(3, 9, generator=gen).cuda(), torch.rand(400, 3, generator=gen).cuda()
+    _run(xg, fg, cg, sg, gg, None)
+    with kernels_launched() as k:
+        _run(xg, fg, cg, sg, gg, None)
+    assert set(k.names) == FORWARD | BACKWARD, k.names
+    with kernels_launched() as k:                               # the normals alone: no finish launch
+        leaf = xg.clone().requires_grad_(True)
+        _nr().vertex_normals(leaf, fg).sum().backward()
+    assert set(k.names) == FORWARD | (BACKWARD - {"k_smooth_shade_backward_finish"}), k.names
+
+
+# ---- 5. the chain into a render ---------------------------------------------------------------------------------------------
+def test_smooth_lit_colours_through_a_render():
+    from deep3dmap_amd import _lib, neural_renderer as nr, synthetic
+    v_np, tri_np = synthetic.icosphere(1)
+    V = v_np.shape[0]
+    tri = torch.from_numpy(tri_np).cuda()
+    gen = torch.Generator().manual_seed(2)
+    x = torch.from_numpy(v_np).cuda().requires_grad_(True)
+    colors = (0.2 + 0.7 * torch.rand(V, 3, generator=gen)).cuda().requires_grad_(True)
+    sh = ((torch.rand(3, 9, generator=gen) - 0.5) + torch.tensor([2.0] + [0.0] * 8)).cuda().requires_grad_(True)
+    target = torch.rand(1, 3, 32, 32, generator=gen).cuda()
+    r = nr.Renderer(camera_mode="look_at", image_size=32, anti_aliasing=False, light_intensity_ambient=1.0,
+                    light_intensity_directional=0.0)
+    r.eye = [0.4, 0.7, -2.4]
+    runs = []
+    with _lib.deterministic():
+        for _ in range(2):
+            x.grad = colors.grad = sh.grad = None
+            shaded = nr.sh_vertex_colors(x, tri, colors, sh)
+            rgb = r.render(x[None], tri[None], nr.textures_from_vertex_colors(shaded, tri))[0]
+            ((rgb - target) ** 2).sum().backward()
+            runs.append([t.grad.clone() for t in (x, colors, sh)] + [rgb.detach().clone()])
+    for a, b, name in zip(runs[0], runs[1], ("g_x", "g_colors", "g_sh", "rgb")):
+        assert bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0 and _same(a, b), name
+    # SHLight's initial light leaves the colours as they are
+    light = nr.SHLight().cuda()
+    with torch.no_grad():
+        lit = light(x, tri, colors)
+    assert len(light._adjacency) == 1
+    assert float(((lit - colors.detach()).abs() / colors.detach().abs()).max()) <= 2.0 ** -22
+
+
+# ---- 6. fit_illumination ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted(S.FIT_SCENES))
+def test_fit_illumination_reproduces_the_reference(name):
+    from deep3dmap_amd.mesh_cython import fit_illumination, render as R
+    assert fit_illumination is R.fit_illumination
+    golden = np.load(GOLDEN)
+    s = S.fit_scene(name)
+    before = s["vertices"].copy()
+    args = [s[k] for k in ("image", "vertices", "texture", "triangles", "vis_ind")]
+    for key, kw in ((name, {}), (name + "/iter1_lamb2", dict(lamb=2, max_iter=1))):
+        got = R.fit_illumination(*args, **kw)
+        assert isinstance(got, np.ndarray) and got.dtype == np.float64 and got.shape == golden[key].shape
+        dev = float(np.abs(got - golden[key]).max())
+        tensors = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in args]
+        kept = tensors[1].clone()
+        on_device = R.fit_illumination(*tensors, **kw)
+        assert torch.is_tensor(on_device) and on_device.is_cuda and on_device.dtype == torch.float64
+        dev_t = float(np.abs(on_device.cpu().numpy() - golden[key]).max())
+        print(f"{key}: largest deviation {dev:.2e} (numpy inputs), {dev_t:.2e} (device tensors)")
+        assert dev <= 16 * FIT_TOL and dev_t <= 16 * FIT_TOL, (key, dev, dev_t)
+        assert torch.equal(kept, tensors[1])
+    assert np.array_equal(before, s["vertices"])                # the caller's vertices are unchanged
