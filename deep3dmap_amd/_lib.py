@@ -39,13 +39,15 @@ class D3MLight(ctypes.Structure):
                 ("direction", _P), ("ia_batch", _I), ("id_batch", _I), ("ca_batch", _I), ("cd_batch", _I), ("dir_batch", _I)]
 
 
+class D3MCsr(ctypes.Structure):
+    """d3m_csr (include/d3m_raster.h): a gathered CSR with its long-row tables (neural_renderer/row_gather.py builds it)."""
+    _fields_ = ([(n, _P) for n in ("offsets", "items", "chunks", "long_rows", "long_chunk_ptr")] +
+                [(n, _I) for n in ("num_rows", "num_chunks", "num_long_rows", "long_row")])
+
+
 class D3MMeshTopology(ctypes.Structure):
-    """d3m_mesh_topology (include/d3m_raster.h): the neighbour CSR, the wing records and the wing CSR of a faces tensor."""
-    _fields_ = ([(n, _P) for n in ("nbr_offsets", "nbr_items", "wings", "wing_offsets", "wing_items", "nbr_chunks",
-                                   "nbr_long_rows", "nbr_long_chunk_ptr", "wing_chunks", "wing_long_rows",
-                                   "wing_long_chunk_ptr")] +
-                [(n, _I) for n in ("num_vertices", "num_edges", "num_wings", "num_nbr_chunks", "num_nbr_long_rows",
-                                   "num_wing_chunks", "num_wing_long_rows", "long_row")])
+    """d3m_mesh_topology (include/d3m_raster.h): the neighbour CSR, the wing CSR and the wing records of a faces tensor."""
+    _fields_ = [("nbr", D3MCsr), ("wing", D3MCsr), ("wings", _P), ("num_edges", _I), ("num_wings", _I)]
 
 
 class D3MFitTargets(ctypes.Structure):
@@ -200,9 +202,9 @@ _SIGNATURES = {
     "d3m_create_texture_image": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
     "d3m_textures_from_image": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "d3m_uv_texture_taps": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "d3m_uv_texture_adjoint": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _L, _I, _I, _P]),
+    "d3m_uv_texture_adjoint": (_I, [ctypes.POINTER(D3MCsr), _I, _P, _P, _P, _I, _L, _I, _I, _P]),
     "d3m_vertex_color_textures": (_I, [_P, _I, _P, _P, _I, _I, _P]),
-    "d3m_vertex_color_textures_backward": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
+    "d3m_vertex_color_textures_backward": (_I, [_P, ctypes.POINTER(D3MCsr), _P, _P, _I, _I, _I, _P]),
     "d3m_mesh_regularizer_scratch_floats": (_SZ, [_I, ctypes.POINTER(D3MMeshTopology)]),
     "d3m_mesh_regularizer": (_I, [_P, _I, ctypes.POINTER(D3MMeshTopology), _F, _F, _F, _F, _P, _SZ, _P, _P, _P, _I, _P]),
     "d3m_morphable_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
@@ -212,10 +214,10 @@ _SIGNATURES = {
     "d3m_pose_scratch_floats": (_SZ, [_I, _I]),
     "d3m_pose_tree_constants": (None, [ctypes.POINTER(_I)]),
     "d3m_pose_backward": (_I, [_P, _I, _P, _I, _F, _F, _F, _P, _I, _P, _P, _P, _P, _SZ, _P, _P, _I, _I, _P]),
-    "d3m_smooth_shade_forward": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _SZ, _P, _P, _P, _I, _I, _I, _P]),
+    "d3m_smooth_shade_forward": (_I, [_P, _I, _P, _I, _P, _I, _P, ctypes.POINTER(D3MCsr), _P, _SZ, _P, _P, _P, _I, _I, _I, _P]),
     "d3m_smooth_shade_scratch_floats": (_SZ, [_I, _I, _I, _I, _I]),
-    "d3m_smooth_shade_backward": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _SZ, _P, _P,
-                                       _P, _I, _I, _I, _P]),
+    "d3m_smooth_shade_backward": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, ctypes.POINTER(D3MCsr), _P, _SZ, _P, _P, _P,
+                                       _I, _I, _I, _P]),
 }
 
 _lib = None

@@ -24,7 +24,9 @@ namespace d3m {
 constexpr int MR_BLOCK = RG_BLOCK;
 
 struct MeshRegArgs {
-    d3m_mesh_topology t;
+    CsrRows nbr, wing;          // the neighbour CSR and the wing CSR, V rows each
+    const int32_t* wings;       // [P, 4] (a, b, c, d), 16-byte aligned
+    int V;
     const float* x;             // [B, V, 3]
     float4* delta;              // [B, V] (delta, 1/deg); NULL without the Laplacian
     float* mean_partials;       // [B, num_nbr_chunks, 3]
@@ -46,16 +48,6 @@ __device__ __forceinline__ mr3 mr_load(const float* __restrict__ p, int v) {
 __device__ __forceinline__ mr3 mr_sub(mr3 a, mr3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ mr3 mr_cross(mr3 a, mr3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ float mr_dot(mr3 a, mr3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-// the long-row tables of the neighbour CSR and of the wing CSR
-__device__ __forceinline__ LongRows mr_nbr_longs(const d3m_mesh_topology& t) {
-    return {reinterpret_cast<const int2*>(t.nbr_chunks), t.nbr_long_rows, t.nbr_long_chunk_ptr, t.num_nbr_chunks,
-            t.num_nbr_long_rows, t.long_row};
-}
-__device__ __forceinline__ LongRows mr_wing_longs(const d3m_mesh_topology& t) {
-    return {reinterpret_cast<const int2*>(t.wing_chunks), t.wing_long_rows, t.wing_long_chunk_ptr, t.num_wing_chunks,
-            t.num_wing_long_rows, t.long_row};
-}
 
 // One item of v's neighbour row: what neighbour u adds to v's gradient (x, y, z) and to the value (w).
 __device__ __forceinline__ float4 mr_nbr_term(const MeshRegArgs& a, const float* __restrict__ x, const float4* __restrict__ delta,
@@ -82,7 +74,7 @@ __device__ __forceinline__ float4 mr_nbr_term(const MeshRegArgs& a, const float*
 // One item (4 p + role) of v's wing row.
 __device__ __forceinline__ float4 mr_wing_term(const MeshRegArgs& a, const float* __restrict__ x, int item) {
     const int p = item >> 2, role = item & 3;
-    const int4 w = reinterpret_cast<const int4*>(a.t.wings)[p];
+    const int4 w = reinterpret_cast<const int4*>(a.wings)[p];
     const mr3 xa = mr_load(x, w.x);
     const mr3 e = mr_sub(mr_load(x, w.y), xa), u = mr_sub(mr_load(x, w.z), xa), q = mr_sub(mr_load(x, w.w), xa);
     const mr3 n0 = mr_cross(e, u), n1 = mr_cross(q, e);
@@ -122,33 +114,33 @@ __device__ __forceinline__ void mr_add_long_row(const LongRows& t, int v, const 
 // ---- the hubs' neighbour sums: one workgroup per chunk of a long neighbour row ------------------------------------------
 __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_mean_chunks(MeshRegArgs a) {
     const int ch = blockIdx.x, b = blockIdx.y;
-    const float* x = a.x + (size_t)b * a.t.num_vertices * 3;
+    const float* x = a.x + (size_t)b * a.V * 3;
     float sum[3];
-    rg_chunk_sum(mr_nbr_longs(a.t).chunks[ch], sum, [&](int e, float (&acc)[3]) {
-        const mr3 xu = mr_load(x, a.t.nbr_items[e]);
+    rg_chunk_sum(a.nbr.longs.chunks[ch], sum, [&](int e, float (&acc)[3]) {
+        const mr3 xu = mr_load(x, a.nbr.items[e]);
         acc[0] += xu.x; acc[1] += xu.y; acc[2] += xu.z;
     });
     if (threadIdx.x == 0) {
-        float* out = a.mean_partials + ((size_t)b * a.t.num_nbr_chunks + ch) * 3;
+        float* out = a.mean_partials + ((size_t)b * a.nbr.longs.n_chunks + ch) * 3;
         out[0] = sum[0]; out[1] = sum[1]; out[2] = sum[2];
     }
 }
 
 // ---- delta: one lane per vertex -------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_delta(MeshRegArgs a) {
-    const int v = blockIdx.x * MR_BLOCK + threadIdx.x, b = blockIdx.y, V = a.t.num_vertices;
+    const int v = blockIdx.x * MR_BLOCK + threadIdx.x, b = blockIdx.y, V = a.V;
     if (v >= V) return;
     const float* x = a.x + (size_t)b * V * 3;
-    const int start = a.t.nbr_offsets[v], end = a.t.nbr_offsets[v + 1], deg = end - start;
+    const int start = a.nbr.offsets[v], end = a.nbr.offsets[v + 1], deg = end - start;
     float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
     if (deg > 0) {
-        const LongRows longs = mr_nbr_longs(a.t);
+        const LongRows& longs = a.nbr.longs;
         float s[3] = {0.f, 0.f, 0.f};
         if (rg_is_long(longs, deg)) {
-            rg_add_chunk_sums(longs, rg_find_long(longs, v), a.mean_partials + (size_t)b * a.t.num_nbr_chunks * 3, s);
+            rg_add_chunk_sums(longs, rg_find_long(longs, v), a.mean_partials + (size_t)b * a.nbr.longs.n_chunks * 3, s);
         } else {
             for (int e = start; e < end; e++) {
-                const mr3 xu = mr_load(x, a.t.nbr_items[e]);
+                const mr3 xu = mr_load(x, a.nbr.items[e]);
                 s[0] += xu.x; s[1] += xu.y; s[2] += xu.z;
             }
         }
@@ -161,22 +153,22 @@ __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_delta(MeshRegArgs a) {
 
 // ---- the hubs' gathered gradient and value: one workgroup per chunk of a long neighbour row, then of a long wing row ----
 __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_row_chunks(MeshRegArgs a) {
-    const int ch = blockIdx.x, b = blockIdx.y, V = a.t.num_vertices;
+    const int ch = blockIdx.x, b = blockIdx.y, V = a.V;
     const float* x = a.x + (size_t)b * V * 3;
     float acc[4] = {0.f, 0.f, 0.f, 0.f};
-    if (ch < a.t.num_nbr_chunks) {
-        const LongRows longs = mr_nbr_longs(a.t);
+    if (ch < a.nbr.longs.n_chunks) {
+        const LongRows& longs = a.nbr.longs;
         const int v = rg_chunk_owner(longs, ch);
         const float4* delta = a.delta ? a.delta + (size_t)b * V : nullptr;
         const mr3 xv = mr_load(x, v);
-        rg_lane_sum(longs.chunks[ch], acc, [&](int e, float (&t)[4]) { mr_add(t, mr_nbr_term(a, x, delta, v, xv, a.t.nbr_items[e])); });
+        rg_lane_sum(longs.chunks[ch], acc, [&](int e, float (&t)[4]) { mr_add(t, mr_nbr_term(a, x, delta, v, xv, a.nbr.items[e])); });
     } else if (a.c_nc > 0.f) {
-        rg_lane_sum(mr_wing_longs(a.t).chunks[ch - a.t.num_nbr_chunks], acc,
-                    [&](int e, float (&t)[4]) { mr_add(t, mr_wing_term(a, x, a.t.wing_items[e])); });
+        rg_lane_sum(a.wing.longs.chunks[ch - a.nbr.longs.n_chunks], acc,
+                    [&](int e, float (&t)[4]) { mr_add(t, mr_wing_term(a, x, a.wing.items[e])); });
     }
     rg_block_sum(acc);
     if (threadIdx.x == 0) {
-        float* out = a.row_partials + ((size_t)b * (a.t.num_nbr_chunks + a.t.num_wing_chunks) + ch) * 4;
+        float* out = a.row_partials + ((size_t)b * (a.nbr.longs.n_chunks + a.wing.longs.n_chunks) + ch) * 4;
         out[0] = acc[0]; out[1] = acc[1]; out[2] = acc[2]; out[3] = acc[3];
     }
 }
@@ -185,10 +177,10 @@ __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_row_chunks(MeshRegArgs a)
 // one value partial ----------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_rows(MeshRegArgs a) {
     __shared__ float staged[MR_BLOCK * 3];
-    const int v = blockIdx.x * MR_BLOCK + threadIdx.x, b = blockIdx.y, V = a.t.num_vertices;
+    const int v = blockIdx.x * MR_BLOCK + threadIdx.x, b = blockIdx.y, V = a.V;
     const float* x = a.x + (size_t)b * V * 3;
     const float4* delta = a.delta ? a.delta + (size_t)b * V : nullptr;
-    const int n_chunks = a.t.num_nbr_chunks + a.t.num_wing_chunks;
+    const int n_chunks = a.nbr.longs.n_chunks + a.wing.longs.n_chunks;
     const float* part = a.row_partials + (size_t)b * n_chunks * 4;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     if (v < V) {
@@ -198,22 +190,22 @@ __global__ void __launch_bounds__(MR_BLOCK) k_mesh_reg_rows(MeshRegArgs a) {
             acc = make_float4(s * dv.x, s * dv.y, s * dv.z, a.c_lap * (dv.x * dv.x + dv.y * dv.y + dv.z * dv.z));
         }
         if (a.c_edge > 0.f || (a.c_lap > 0.f && a.grad)) {
-            const LongRows longs = mr_nbr_longs(a.t);
-            const int start = a.t.nbr_offsets[v], end = a.t.nbr_offsets[v + 1];
+            const LongRows& longs = a.nbr.longs;
+            const int start = a.nbr.offsets[v], end = a.nbr.offsets[v + 1];
             if (rg_is_long(longs, end - start)) {
                 mr_add_long_row(longs, v, part, acc);
             } else {
                 const mr3 xv = mr_load(x, v);
-                for (int e = start; e < end; e++) mr_add(acc, mr_nbr_term(a, x, delta, v, xv, a.t.nbr_items[e]));
+                for (int e = start; e < end; e++) mr_add(acc, mr_nbr_term(a, x, delta, v, xv, a.nbr.items[e]));
             }
         }
         if (a.c_nc > 0.f) {
-            const LongRows longs = mr_wing_longs(a.t);
-            const int start = a.t.wing_offsets[v], end = a.t.wing_offsets[v + 1];
+            const LongRows& longs = a.wing.longs;
+            const int start = a.wing.offsets[v], end = a.wing.offsets[v + 1];
             if (rg_is_long(longs, end - start)) {
-                mr_add_long_row(longs, v, part + (size_t)a.t.num_nbr_chunks * 4, acc);
+                mr_add_long_row(longs, v, part + (size_t)a.nbr.longs.n_chunks * 4, acc);
             } else {
-                for (int e = start; e < end; e++) mr_add(acc, mr_wing_term(a, x, a.t.wing_items[e]));
+                for (int e = start; e < end; e++) mr_add(acc, mr_wing_term(a, x, a.wing.items[e]));
             }
         }
     }

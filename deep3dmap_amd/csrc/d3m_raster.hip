@@ -2156,37 +2156,42 @@ D3M_EXPORT int d3m_uv_texture_taps(const float* faces_uv, const int32_t* face_ma
     return check_launch();
 }
 
-// One CSR's long-row tables (d3m_row_gather.h) as an entry point receives them: counts that are not negative, long rows
-// and chunks only together, each with its arrays, and somewhere to put the chunk sums.
-static bool long_rows_ok(const void* chunks, int num_chunks, const void* long_rows, const void* long_chunk_ptr,
-                         int num_long_rows, const void* partials) {
-    if (num_chunks < 0 || num_long_rows < 0 || (num_chunks > 0) != (num_long_rows > 0)) return false;
-    return num_chunks == 0 || (chunks && long_rows && long_chunk_ptr && partials);
+// A d3m_csr as an entry point receives it (include/d3m_raster.h lists these refusals): `rows` rows, counts that are not
+// negative, long rows and chunks only together, each with its arrays, the items they cut and somewhere to put the chunk sums.
+// (Whether a CSR without chunks needs items is the node's business: an empty one has none.)
+static bool csr_counts_ok(const d3m_csr& c) {      // (what a scratch size can be computed from)
+    return c.num_rows > 0 && c.long_row >= 0 && c.num_chunks >= 0 && c.num_long_rows >= 0 &&
+           (c.num_chunks > 0) == (c.num_long_rows > 0);
+}
+static bool csr_ok(const d3m_csr* c, int rows, const void* partials) {
+    if (!c || !c->offsets || c->num_rows != rows || !csr_counts_ok(*c)) return false;
+    return c->num_chunks == 0 || (c->items && c->chunks && c->long_rows && c->long_chunk_ptr && partials);
+}
+// its device side (d3m_row_gather.h)
+static CsrRows csr_rows(const d3m_csr& c) {
+    return {c.offsets, c.items, {(const int2*)c.chunks, c.long_rows, c.long_chunk_ptr, c.num_chunks, c.num_long_rows, c.long_row}};
 }
 
-D3M_EXPORT int d3m_uv_texture_adjoint(const int32_t* row_ptr, const int32_t* entries, const int32_t* chunks, int num_chunks,
-                                      const int32_t* long_rows, const int32_t* long_chunk_ptr, int num_long_rows,
-                                      int long_row, int lanes_per_row, const float* grad_textures, float* partials,
-                                      float* grad_image, int batch_size, long num_texels, int image_height,
-                                      int image_width, d3m_stream_t stream) {
-    if (!row_ptr || !grad_textures || !grad_image) return D3M_ERR_INVALID;
-    if (batch_size <= 0 || batch_size > 65535 || num_texels <= 0 || image_height <= 0 || image_width <= 0 ||
-        long_row < 0)
+D3M_EXPORT int d3m_uv_texture_adjoint(const d3m_csr* transpose, int lanes_per_row, const float* grad_textures,
+                                      float* partials, float* grad_image, int batch_size, long num_texels,
+                                      int image_height, int image_width, d3m_stream_t stream) {
+    if (!grad_textures || !grad_image) return D3M_ERR_INVALID;
+    if (batch_size <= 0 || batch_size > 65535 || num_texels <= 0 || image_height <= 0 || image_width <= 0)
         return D3M_ERR_INVALID;
     if (lanes_per_row != 1 && lanes_per_row != 2 && lanes_per_row != 4 && lanes_per_row != 8 && lanes_per_row != 16)
         return D3M_ERR_INVALID;
     if ((long)image_height * image_width >= 0x7FFFFFFF) return D3M_ERR_INVALID;
-    if (!long_rows_ok(chunks, num_chunks, long_rows, long_chunk_ptr, num_long_rows, partials)) return D3M_ERR_INVALID;
-    if (num_chunks > 0 && !entries) return D3M_ERR_INVALID;
     const int n_pixels = image_height * image_width;
+    if (!csr_ok(transpose, n_pixels, partials)) return D3M_ERR_INVALID;
+    const CsrRows rows = csr_rows(*transpose);
+    const int num_chunks = rows.longs.n_chunks;
     hipStream_t st = (hipStream_t)stream;
     if (num_chunks > 0)
         LAUNCH("k_uv_adjoint_chunks", k_uv_adjoint_chunks, dim3(num_chunks, batch_size), dim3(UV_ADJ_BLOCK), st,
-               (const int2*)entries, (const int2*)chunks, num_chunks, grad_textures, num_texels, partials);
+               (const int2*)rows.items, rows.longs.chunks, num_chunks, grad_textures, num_texels, partials);
 #define UV_ROWS(L)                                                                                                       \
     LAUNCH("k_uv_adjoint_rows", k_uv_adjoint_rows<L>, dim3(blocks_for((long)n_pixels * L, 256), batch_size), dim3(256), st, \
-           row_ptr, (const int2*)entries, long_rows, long_chunk_ptr, num_long_rows, long_row, partials, num_chunks,       \
-           grad_textures, num_texels, grad_image, n_pixels)
+           rows, (const float*)partials, grad_textures, num_texels, grad_image, n_pixels)
     switch (lanes_per_row) {
         case 1: UV_ROWS(1); break;
         case 2: UV_ROWS(2); break;
@@ -2209,37 +2214,37 @@ D3M_EXPORT int d3m_vertex_color_textures(const float* colors, int color_batch, c
     return check_launch();
 }
 
-D3M_EXPORT int d3m_vertex_color_textures_backward(const float* grad_textures, const int32_t* adj_offsets,
-                                                  const int32_t* adj_items, const int32_t* chunks, int num_chunks,
-                                                  const int32_t* long_rows, const int32_t* long_chunk_ptr,
-                                                  int num_long_rows, int long_row, float* partials, float* grad_colors,
-                                                  int batch_size, int num_vertices, int num_tri, d3m_stream_t stream) {
-    if (!grad_textures || !adj_offsets || !adj_items || !grad_colors) return D3M_ERR_INVALID;
-    if (batch_size <= 0 || batch_size > 65535 || num_vertices <= 0 || num_tri <= 0 || long_row < 0) return D3M_ERR_INVALID;
+D3M_EXPORT int d3m_vertex_color_textures_backward(const float* grad_textures, const d3m_csr* adjacency, float* partials,
+                                                  float* grad_colors, int batch_size, int num_vertices, int num_tri,
+                                                  d3m_stream_t stream) {
+    if (!grad_textures || !grad_colors) return D3M_ERR_INVALID;
+    if (batch_size <= 0 || batch_size > 65535 || num_vertices <= 0 || num_tri <= 0) return D3M_ERR_INVALID;
     if ((long)num_tri * 3 > 0x7FFFFFFF) return D3M_ERR_INVALID;        // items are int32
-    if (!long_rows_ok(chunks, num_chunks, long_rows, long_chunk_ptr, num_long_rows, partials)) return D3M_ERR_INVALID;
+    if (!csr_ok(adjacency, num_vertices, partials) || !adjacency->items) return D3M_ERR_INVALID;
+    const CsrRows adj = csr_rows(*adjacency);
+    const int num_chunks = adj.longs.n_chunks;
     hipStream_t st = (hipStream_t)stream;
     if (num_chunks > 0)
         LAUNCH("k_vertex_color_adjoint_chunks", k_vertex_color_adjoint_chunks, dim3(num_chunks, batch_size),
-               dim3(VC_ADJ_BLOCK), st, adj_items, (const int2*)chunks, num_chunks, grad_textures, (long)num_tri, partials);
+               dim3(VC_ADJ_BLOCK), st, adj.items, adj.longs.chunks, num_chunks, grad_textures, (long)num_tri, partials);
     LAUNCH("k_vertex_color_adjoint_rows", k_vertex_color_adjoint_rows, dim3(blocks_for((long)num_vertices * 3, 256), batch_size),
-           dim3(256), st, adj_offsets, adj_items, long_rows, long_chunk_ptr, num_long_rows, long_row, partials, num_chunks,
-           grad_textures, (long)num_tri, grad_colors, num_vertices);
+           dim3(256), st, adj, (const float*)partials, grad_textures, (long)num_tri, grad_colors, num_vertices);
     return check_launch();
 }
 
 // Mesh shape regularisers (d3m_mesh_reg.h): Laplacian, edge length and normal consistency, value and gradient.
 struct MeshRegLayout { size_t delta, row_partials, mean_partials, value_partials, total; int row_blocks; };
 static bool mesh_reg_layout(int B, const d3m_mesh_topology* t, MeshRegLayout& l) {
-    if (!t || B <= 0 || B > 65535 || t->num_vertices <= 0 || t->num_edges < 0 || t->num_wings < 0 || t->long_row < 0 ||
-        t->num_nbr_chunks < 0 || t->num_nbr_long_rows < 0 || t->num_wing_chunks < 0 || t->num_wing_long_rows < 0)
+    if (!t || B <= 0 || B > 65535 || t->num_edges < 0 || t->num_wings < 0 || !csr_counts_ok(t->nbr) ||
+        !csr_counts_ok(t->wing) || t->wing.num_rows != t->nbr.num_rows)
         return false;
     if (t->num_edges > 0x3FFFFFFF || t->num_wings > 0x1FFFFFFF) return false;         // items are int32
-    l.row_blocks = blocks_for((long)t->num_vertices, MR_BLOCK);
+    const int V = t->nbr.num_rows;
+    l.row_blocks = blocks_for((long)V, MR_BLOCK);
     l.delta = 0;                                                                        // float4 per vertex
-    l.row_partials = l.delta + (size_t)B * t->num_vertices * 4;                         // float4 per chunk
-    l.mean_partials = l.row_partials + (size_t)B * ((size_t)t->num_nbr_chunks + t->num_wing_chunks) * 4;
-    l.value_partials = l.mean_partials + (size_t)B * t->num_nbr_chunks * 3;
+    l.row_partials = l.delta + (size_t)B * V * 4;                                       // float4 per chunk
+    l.mean_partials = l.row_partials + (size_t)B * ((size_t)t->nbr.num_chunks + t->wing.num_chunks) * 4;
+    l.value_partials = l.mean_partials + (size_t)B * t->nbr.num_chunks * 3;
     l.total = l.value_partials + (size_t)B * l.row_blocks;
     return true;
 }
@@ -2258,21 +2263,23 @@ D3M_EXPORT int d3m_mesh_regularizer(const float* vertices, int batch_size, const
     if (!(w_laplacian >= 0.f) || !(w_edge >= 0.f) || !(w_normal >= 0.f) || !(edge_target >= 0.f)) return D3M_ERR_INVALID;
     if (scratch_floats < l.total || ((uintptr_t)scratch & 15)) return D3M_ERR_INVALID;
     const d3m_mesh_topology& t = *topology;
-    const bool lap = w_laplacian > 0.f, edge = w_edge > 0.f && t.num_edges > 0, nc = w_normal > 0.f && t.num_wings > 0;
-    if ((lap || edge) && (!t.nbr_offsets || (t.num_edges > 0 && !t.nbr_items))) return D3M_ERR_INVALID;
-    if (nc && (!t.wings || !t.wing_offsets || !t.wing_items || ((uintptr_t)t.wings & 15))) return D3M_ERR_INVALID;
+    const int V = t.nbr.num_rows;
     // (the chunk sums of both CSRs go to scratch)
-    if (!long_rows_ok(t.nbr_chunks, t.num_nbr_chunks, t.nbr_long_rows, t.nbr_long_chunk_ptr, t.num_nbr_long_rows, scratch) ||
-        !long_rows_ok(t.wing_chunks, t.num_wing_chunks, t.wing_long_rows, t.wing_long_chunk_ptr, t.num_wing_long_rows, scratch))
-        return D3M_ERR_INVALID;
+    if (!csr_ok(&t.nbr, V, scratch) || !csr_ok(&t.wing, V, scratch)) return D3M_ERR_INVALID;
+    const bool lap = w_laplacian > 0.f, edge = w_edge > 0.f && t.num_edges > 0, nc = w_normal > 0.f && t.num_wings > 0;
+    if ((lap || edge) && t.num_edges > 0 && !t.nbr.items) return D3M_ERR_INVALID;
+    if (nc && (!t.wings || !t.wing.items || ((uintptr_t)t.wings & 15))) return D3M_ERR_INVALID;
     MeshRegArgs a;
-    a.t = t;
+    a.nbr = csr_rows(t.nbr);
+    a.wing = csr_rows(t.wing);
+    a.wings = t.wings;
+    a.V = V;
     a.x = vertices;
     a.delta = lap ? reinterpret_cast<float4*>(scratch + l.delta) : nullptr;
     a.row_partials = scratch + l.row_partials;
     a.mean_partials = scratch + l.mean_partials;
     a.value_partials = scratch + l.value_partials;
-    a.c_lap = lap ? (float)((double)w_laplacian / t.num_vertices) : 0.f;
+    a.c_lap = lap ? (float)((double)w_laplacian / V) : 0.f;
     a.c_edge = edge ? (float)((double)w_edge / t.num_edges) : 0.f;
     a.c_nc = nc ? (float)((double)w_normal / t.num_wings) : 0.f;
     a.edge_target = edge_target;
@@ -2283,10 +2290,10 @@ D3M_EXPORT int d3m_mesh_regularizer(const float* vertices, int batch_size, const
     hipStream_t st = (hipStream_t)stream;
     // (the chunk passes only where a term reads the rows they cover)
     const bool nbr_rows = edge || (lap && grad_vertices);
-    const int row_chunks = (nbr_rows || nc) ? t.num_nbr_chunks + t.num_wing_chunks : 0;
+    const int row_chunks = (nbr_rows || nc) ? t.nbr.num_chunks + t.wing.num_chunks : 0;
     if (lap) {
-        if (t.num_nbr_chunks > 0)
-            LAUNCH("k_mesh_reg_mean_chunks", k_mesh_reg_mean_chunks, dim3(t.num_nbr_chunks, batch_size), dim3(MR_BLOCK), st, a);
+        if (t.nbr.num_chunks > 0)
+            LAUNCH("k_mesh_reg_mean_chunks", k_mesh_reg_mean_chunks, dim3(t.nbr.num_chunks, batch_size), dim3(MR_BLOCK), st, a);
         LAUNCH("k_mesh_reg_delta", k_mesh_reg_delta, dim3(l.row_blocks, batch_size), dim3(MR_BLOCK), st, a);
     }
     if (row_chunks > 0)
@@ -2436,17 +2443,16 @@ D3M_EXPORT size_t d3m_smooth_shade_scratch_floats(int batch_size, int vertices_b
 }
 
 D3M_EXPORT int d3m_smooth_shade_forward(const float* vertices, int vertices_batch, const float* colors, int colors_batch,
-                                        const float* sh, int sh_batch, const int32_t* tri, const int32_t* adj_offsets,
-                                        const int32_t* adj_items, const int32_t* chunks, int num_chunks,
-                                        const int32_t* long_rows, const int32_t* long_chunk_ptr, int num_long_rows,
-                                        int long_row, float* scratch, size_t scratch_floats, float* shaded, float* normals,
+                                        const float* sh, int sh_batch, const int32_t* tri, const d3m_csr* adjacency,
+                                        float* scratch, size_t scratch_floats, float* shaded, float* normals,
                                         float* lengths, int batch_size, int num_vertices, int num_tri, d3m_stream_t stream) {
-    if (!vertices || !tri || !adj_offsets || !adj_items || !scratch || !normals || !lengths) return D3M_ERR_INVALID;
+    if (!vertices || !tri || !scratch || !normals || !lengths) return D3M_ERR_INVALID;
     if (colors ? (!sh || !shaded) : shaded != nullptr) return D3M_ERR_INVALID;
-    if (!smooth_shade_sizes(batch_size, vertices_batch, colors_batch, sh_batch, num_vertices, num_tri, colors != nullptr) ||
-        long_row < 0)
+    if (!smooth_shade_sizes(batch_size, vertices_batch, colors_batch, sh_batch, num_vertices, num_tri, colors != nullptr))
         return D3M_ERR_INVALID;
-    if (!long_rows_ok(chunks, num_chunks, long_rows, long_chunk_ptr, num_long_rows, scratch)) return D3M_ERR_INVALID;
+    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    const CsrRows adj = csr_rows(*adjacency);
+    const int num_chunks = adj.longs.n_chunks;
     const int vb = vertices_batch, V = num_vertices;
     const long F = num_tri;
     const size_t n_normals = (size_t)vb * F * 3;
@@ -2457,12 +2463,11 @@ D3M_EXPORT int d3m_smooth_shade_forward(const float* vertices, int vertices_batc
     hipStream_t st = (hipStream_t)stream;
     float* face_normals = scratch;
     float* partials = scratch + n_normals;
-    const SmoothAdj adj = {adj_offsets, adj_items, {(const int2*)chunks, long_rows, long_chunk_ptr, num_chunks, num_long_rows, long_row}};
     LAUNCH("k_smooth_shade_face_normals", k_smooth_shade_face_normals, dim3(blocks_for(F, SS_BLOCK), vb), dim3(SS_BLOCK), st,
            vertices, tri, face_normals, V, F);
     if (num_chunks > 0)
-        LAUNCH("k_smooth_shade_normal_chunks", k_smooth_shade_chunks<3>, dim3(num_chunks, vb), dim3(RG_BLOCK), st, adj_items,
-               (const int2*)chunks, num_chunks, (const float*)face_normals, F, partials);
+        LAUNCH("k_smooth_shade_normal_chunks", k_smooth_shade_chunks<3>, dim3(num_chunks, vb), dim3(RG_BLOCK), st, adj.items,
+               adj.longs.chunks, num_chunks, (const float*)face_normals, F, partials);
     LAUNCH("k_smooth_shade_vertices", k_smooth_shade_vertices, dim3(blocks_for((long)V, SS_BLOCK), vb), dim3(SS_BLOCK), st, adj,
            (const float*)face_normals, (const float*)partials, colors, colors_batch, sh, sh_batch, shaded, normals, lengths,
            batch_size, vb, V, F);
@@ -2472,19 +2477,18 @@ D3M_EXPORT int d3m_smooth_shade_forward(const float* vertices, int vertices_batc
 D3M_EXPORT int d3m_smooth_shade_backward(const float* vertices, int vertices_batch, const float* colors, int colors_batch,
                                          const float* sh, int sh_batch, const float* normals, const float* lengths,
                                          const float* grad_shaded, const float* grad_normals, const int32_t* tri,
-                                         const int32_t* adj_offsets, const int32_t* adj_items, const int32_t* chunks,
-                                         int num_chunks, const int32_t* long_rows, const int32_t* long_chunk_ptr,
-                                         int num_long_rows, int long_row, float* scratch, size_t scratch_floats,
+                                         const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
                                          float* grad_vertices, float* grad_colors, float* grad_sh, int batch_size,
                                          int num_vertices, int num_tri, d3m_stream_t stream) {
-    if (!vertices || !normals || !lengths || !tri || !adj_offsets || !adj_items || !scratch) return D3M_ERR_INVALID;
+    if (!vertices || !normals || !lengths || !tri || !scratch) return D3M_ERR_INVALID;
     if (!grad_vertices && !grad_colors && !grad_sh) return D3M_ERR_INVALID;
     if (colors ? !sh : (grad_shaded != nullptr)) return D3M_ERR_INVALID;
     if (!grad_shaded && (grad_colors || grad_sh)) return D3M_ERR_INVALID;      // (zeros: the caller leaves them out)
-    if (!smooth_shade_sizes(batch_size, vertices_batch, colors_batch, sh_batch, num_vertices, num_tri, colors != nullptr) ||
-        long_row < 0)
+    if (!smooth_shade_sizes(batch_size, vertices_batch, colors_batch, sh_batch, num_vertices, num_tri, colors != nullptr))
         return D3M_ERR_INVALID;
-    if (!long_rows_ok(chunks, num_chunks, long_rows, long_chunk_ptr, num_long_rows, scratch)) return D3M_ERR_INVALID;
+    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    const CsrRows adj = csr_rows(*adjacency);
+    const int num_chunks = adj.longs.n_chunks;
     if (scratch_floats < d3m_smooth_shade_scratch_floats(batch_size, vertices_batch, num_vertices, num_tri, num_chunks))
         return D3M_ERR_INVALID;
     if (misaligned4(vertices) || misaligned4(colors) || misaligned4(sh) || misaligned4(normals) || misaligned4(lengths) ||
@@ -2498,7 +2502,6 @@ D3M_EXPORT int d3m_smooth_shade_backward(const float* vertices, int vertices_bat
     float* sh_partial = g_s + (size_t)vb * V * 3;
     float* terms = sh_partial + (size_t)B * parts * SS_SUMS;
     float* partials = terms + (size_t)vb * F * 9;
-    const SmoothAdj adj = {adj_offsets, adj_items, {(const int2*)chunks, long_rows, long_chunk_ptr, num_chunks, num_long_rows, long_row}};
     const int walk_sets = B > 1 && (vb == 1 || (colors && colors_batch == 1)) ? 1 : 0;
     LAUNCH("k_smooth_shade_backward_vertices", k_smooth_shade_backward_vertices, dim3(parts, walk_sets ? 1 : B),
            dim3(SS_BLOCK), st, colors, colors_batch, sh, sh_batch, normals, lengths, vb, grad_shaded, grad_normals, grad_colors,
@@ -2510,8 +2513,8 @@ D3M_EXPORT int d3m_smooth_shade_backward(const float* vertices, int vertices_bat
         LAUNCH("k_smooth_shade_backward_faces", k_smooth_shade_backward_faces, dim3(blocks_for(F, SS_BLOCK), vb), dim3(SS_BLOCK),
                st, vertices, tri, (const float*)g_s, terms, V, F);
         if (num_chunks > 0)
-            LAUNCH("k_smooth_shade_term_chunks", k_smooth_shade_chunks<1>, dim3(num_chunks, vb), dim3(RG_BLOCK), st, adj_items,
-                   (const int2*)chunks, num_chunks, (const float*)terms, F * 3, partials);
+            LAUNCH("k_smooth_shade_term_chunks", k_smooth_shade_chunks<1>, dim3(num_chunks, vb), dim3(RG_BLOCK), st, adj.items,
+                   adj.longs.chunks, num_chunks, (const float*)terms, F * 3, partials);
         LAUNCH("k_smooth_shade_backward_rows", k_smooth_shade_backward_rows, dim3(blocks_for((long)V * 3, SS_BLOCK), vb),
                dim3(SS_BLOCK), st, adj, (const float*)terms, (const float*)partials, grad_vertices, V, F);
     }

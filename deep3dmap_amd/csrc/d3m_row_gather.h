@@ -1,6 +1,7 @@
 // d3m_row_gather.h -- the long-row format of a gathered CSR and its fixed summation tree, stated once for every node that
-// gathers over a CSR (d3m_textures.h: the uv transpose; d3m_vertex_colors.h: the faces' adjacency; d3m_mesh_reg.h: the
-// neighbour and the wing CSR).  The host side of the same format is neural_renderer/row_gather.py.
+// gathers over a CSR (d3m_textures.h: the uv transpose; d3m_vertex_colors.h and d3m_smooth_shade.h: the faces' adjacency;
+// d3m_mesh_reg.h: the neighbour and the wing CSR).  The ABI's d3m_csr (include/d3m_raster.h) carries it, CsrRows below is its
+// device side, and neural_renderer/row_gather.py builds it.
 //
 // A row of up to long_row items is summed by its own lane(s) in item order (how many lanes is the node's business).  A
 // longer row (a hub: pixel (0,0) of a uv layout, a fan apex, a pole) must not make one lane walk thousands of items: it is
@@ -21,12 +22,19 @@ namespace d3m {
 
 constexpr int RG_BLOCK = 256;
 
-// One CSR's long-row tables, filled by a kernel from the arguments it receives.
+// One CSR's long-row tables.
 struct LongRows {
     const int2* chunks;              // [n_chunks] item ranges [start, end)
     const int32_t* rows;             // [n_rows] the long rows, ascending
     const int32_t* chunk_ptr;        // [n_rows + 1] row l owns chunks chunk_ptr[l] .. chunk_ptr[l + 1]
     int n_chunks, n_rows, long_row;
+};
+
+// A gathered CSR as a kernel receives it: the device side of d3m_csr (include/d3m_raster.h), made by the host's csr_rows().
+struct CsrRows {
+    const int32_t* offsets;          // [rows + 1]
+    const int32_t* items;            // the node's item layout
+    LongRows longs;
 };
 
 // whether a row of n_items items went through the chunks

@@ -55,13 +55,6 @@ __host__ __device__ __forceinline__ int ss_parts(long items) {
     return n < 1 ? 1 : (n > SS_MAX_PARTS ? SS_MAX_PARTS : (int)n);
 }
 
-// The faces' adjacency as d3m_vertex_color_textures_backward takes it.
-struct SmoothAdj {
-    const int32_t* offsets;             // [V + 1]
-    const int32_t* items;               // [3 F] item = 3 f + c, ascending per vertex
-    LongRows longs;
-};
-
 __device__ __forceinline__ void ss_basis(const float* n, float* H) {
     const float nx = n[0], ny = n[1], nz = n[2];
     H[0] = SS_A0;
@@ -147,7 +140,7 @@ __global__ void __launch_bounds__(RG_BLOCK) k_smooth_shade_chunks(const int32_t*
 // grid (blocks of V, vb): one lane per (vertex set, vertex) walks its row, normalises, stores normals [vb, V, 3] and lengths
 // [vb, V]; with colours it evaluates the basis once and shades its set (vb > 1) or every set in ascending order (shared
 // vertices): shaded [B, V, 3].
-__global__ void __launch_bounds__(SS_BLOCK) k_smooth_shade_vertices(SmoothAdj adj, const float* __restrict__ face_normals,
+__global__ void __launch_bounds__(SS_BLOCK) k_smooth_shade_vertices(CsrRows adj, const float* __restrict__ face_normals,
                                                                     const float* __restrict__ partials,
                                                                     const float* __restrict__ colors, int cb,
                                                                     const float* __restrict__ sh, int sb,
@@ -310,7 +303,7 @@ __global__ void __launch_bounds__(SS_BLOCK) k_smooth_shade_backward_faces(const 
 }
 
 // grid (blocks of 3 V, vb): one lane per element of g_x [vb, V, 3].  A vertex of no face gets 0: every element is written.
-__global__ void __launch_bounds__(SS_BLOCK) k_smooth_shade_backward_rows(SmoothAdj adj, const float* __restrict__ terms,
+__global__ void __launch_bounds__(SS_BLOCK) k_smooth_shade_backward_rows(CsrRows adj, const float* __restrict__ terms,
                                                                          const float* __restrict__ partials,
                                                                          float* __restrict__ g_x, int V, long F) {
     const long i = (long)blockIdx.x * SS_BLOCK + threadIdx.x;

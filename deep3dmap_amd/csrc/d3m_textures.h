@@ -205,14 +205,13 @@ __global__ void __launch_bounds__(UV_ADJ_BLOCK) k_uv_adjoint_chunks(const int2* 
 // LPR lanes per row (a power of two up to 64, chosen from the layout's mean row length): lane `sub` of a row sums its
 // entries sub, sub + LPR, ... in order, then a butterfly over the row's lanes -- the order is fixed for a given LPR.
 template <int LPR>
-__global__ void __launch_bounds__(256) k_uv_adjoint_rows(const int32_t* __restrict__ row_ptr,
-                                                         const int2* __restrict__ entries,
-                                                         const int32_t* __restrict__ long_rows,
-                                                         const int32_t* __restrict__ long_chunk_ptr, int n_long,
-                                                         int long_row, const float* __restrict__ partials,
-                                                         int n_chunks, const float* __restrict__ grad_textures,
-                                                         long n_texels, float* __restrict__ grad_image, int n_pixels) {
-    const d3m::LongRows longs = {nullptr, long_rows, long_chunk_ptr, n_chunks, n_long, long_row};
+__global__ void __launch_bounds__(256) k_uv_adjoint_rows(d3m::CsrRows transpose, const float* __restrict__ partials,
+                                                         const float* __restrict__ grad_textures, long n_texels,
+                                                         float* __restrict__ grad_image, int n_pixels) {
+    const d3m::LongRows& longs = transpose.longs;
+    const int32_t* row_ptr = transpose.offsets;
+    const int2* entries = reinterpret_cast<const int2*>(transpose.items);
+    const int n_chunks = longs.n_chunks;
     const long t = (long)blockIdx.x * 256 + threadIdx.x;
     const int sub = (int)(t % LPR);
     const int p = (int)min(t / LPR, (long)n_pixels);          // (lanes past the last row walk an empty row: no early exit

@@ -67,26 +67,20 @@ __global__ void __launch_bounds__(VC_ADJ_BLOCK) k_vertex_color_adjoint_chunks(co
 
 // One lane per element of grad_colors [B, V, 3] (the three lanes of a vertex read adjacent floats of each texel; the store
 // is contiguous).  A vertex of no face has an empty row and gets 0: every element is written.
-__global__ void __launch_bounds__(256) k_vertex_color_adjoint_rows(const int32_t* __restrict__ adj_offsets,
-                                                                   const int32_t* __restrict__ adj_items,
-                                                                   const int32_t* __restrict__ long_rows,
-                                                                   const int32_t* __restrict__ long_chunk_ptr,
-                                                                   int n_long, int long_row,
-                                                                   const float* __restrict__ partials, int n_chunks,
+__global__ void __launch_bounds__(256) k_vertex_color_adjoint_rows(CsrRows adj, const float* __restrict__ partials,
                                                                    const float* __restrict__ grad_textures,
                                                                    long n_faces, float* __restrict__ grad_colors, int V) {
-    const LongRows longs = {nullptr, long_rows, long_chunk_ptr, n_chunks, n_long, long_row};
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const int b = blockIdx.y;
     if (i >= (long)V * 3) return;
     const int v = (int)(i / 3), k = (int)(i - (long)v * 3);
-    const int start = adj_offsets[v], end = adj_offsets[v + 1];
+    const int start = adj.offsets[v], end = adj.offsets[v + 1];
     float acc[1] = {0.0f};
-    if (rg_is_long(longs, end - start)) {
-        rg_add_chunk_sums<1, 3>(longs, rg_find_long(longs, v), partials + (size_t)b * n_chunks * 3 + k, acc);
+    if (rg_is_long(adj.longs, end - start)) {
+        rg_add_chunk_sums<1, 3>(adj.longs, rg_find_long(adj.longs, v), partials + (size_t)b * adj.longs.n_chunks * 3 + k, acc);
     } else {
         const float* g = grad_textures + (size_t)b * n_faces * 24;
-        for (int e = start; e < end; e++) acc[0] += vc_item_term(g, adj_items[e], k);
+        for (int e = start; e < end; e++) acc[0] += vc_item_term(g, adj.items[e], k);
     }
     grad_colors[(size_t)b * V * 3 + i] = acc[0];
 }

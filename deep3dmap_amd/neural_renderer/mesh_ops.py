@@ -36,7 +36,7 @@ class _GatherFaces(torch.autograd.Function):
             # instead of scattered with float atomics in arrival order
             adj = vertex_adjacency(tri, V)
             gv = torch.empty(B, V, 3, dtype=torch.float32, device=g.device)
-            _lib.check(_lib.lib().d3m_vertex_gather(_lib.ptr(g), None, _lib.ptr(adj.offsets), _lib.ptr(adj.items), _lib.ptr(gv),
+            _lib.check(_lib.lib().d3m_vertex_gather(_lib.ptr(g), None, _lib.ptr(adj.csr.offsets), _lib.ptr(adj.csr.items), _lib.ptr(gv),
                                                     B, V, Ft, int(fill_back), None, _lib.stream_ptr()), "d3m_vertex_gather")
             return gv, None, None
         gv = torch.zeros(B, V, 3, dtype=torch.float32, device=g.device)

@@ -17,16 +17,15 @@ import torch
 import torch.nn as nn
 
 from .. import _lib
-from .row_gather import LONG_ROW, BuiltCache, checked_faces as _checked_faces, csr_offsets, long_row_chunks, tensor_key
+from .row_gather import BuiltCache, build_csr, checked_faces as _checked_faces, tensor_key
 
 MAX_FACES_PER_EDGE = 16     # an edge of n faces gives n (n - 1) / 2 wing records
 
-MeshTopology = namedtuple("MeshTopology", "edges nbr_offsets nbr_items wings wing_offsets wing_items nbr_chunks nbr_long_rows "
-                          "nbr_long_chunk_ptr wing_chunks wing_long_rows wing_long_chunk_ptr num_vertices num_edges num_wings c")
+MeshTopology = namedtuple("MeshTopology", "edges wings nbr wing num_vertices num_edges num_wings c")
 MeshTopology.__doc__ = """The faces of one mesh as d3m_mesh_regularizer reads them (all i32): edges [E,2] (a < b, sorted),
-the neighbour CSR nbr_offsets [V+1] / nbr_items [2E] (a vertex's distinct neighbours, ascending), wings [P,4] = (a, b, c, d)
-ordered by (edge, i, j), the wing CSR wing_offsets [V+1] / wing_items [4P] (item = 4 p + role, ascending per vertex), the
-chunk tables of either CSR's long rows (row_gather.long_row_chunks), and `c`: the d3m_mesh_topology that points at them."""
+wings [P,4] = (a, b, c, d) ordered by (edge, i, j), nbr: the neighbour Csr of V rows (items [2E]: a vertex's distinct
+neighbours, ascending), wing: the wing Csr of V rows (items [4P]: item = 4 p + role, ascending per vertex; row_gather.Csr),
+and `c`: the d3m_mesh_topology that points at them."""
 
 
 class TopologyCache(BuiltCache):
@@ -58,7 +57,6 @@ def build_topology(faces, num_vertices):
     # neighbour CSR: both directions of every edge, sorted by (vertex, neighbour)
     directed = torch.sort(torch.cat([keys, eb * V + ea]))[0]
     nbr_rows, nbr_items = torch.div(directed, V, rounding_mode="floor"), directed % V
-    nbr_offsets, nbr_counts = csr_offsets(nbr_rows, V)
     # wings: the sides of the faces that repeat no index, sorted by (edge, face)
     proper = (tri[:, 0] != tri[:, 1]) & (tri[:, 1] != tri[:, 2]) & (tri[:, 2] != tri[:, 0])
     keep = proper[:, None].expand(F, 3).reshape(-1)
@@ -79,16 +77,12 @@ def build_topology(faces, num_vertices):
     j_side = i_side + 1 + (torch.arange(P, device=dev) - (torch.cumsum(later, 0) - later)[i_side])
     e_of = side_edge[i_side]
     wings = torch.stack([ea[e_of], eb[e_of], side_third[i_side], side_third[j_side]], 1).reshape(-1, 4)
-    wing_items = torch.argsort(wings.reshape(-1), stable=True)   # item = 4 p + role; stable: ascending per vertex
-    wing_offsets, wing_counts = csr_offsets(wings.reshape(-1), V)
-    nbr_tables = long_row_chunks(nbr_offsets, nbr_counts)
-    wing_tables = long_row_chunks(wing_offsets, wing_counts)
-    tensors = [torch.stack([ea, eb], 1).to(**i32).contiguous(), nbr_offsets.to(**i32), nbr_items.to(**i32).contiguous(),
-               wings.to(**i32).contiguous(), wing_offsets.to(**i32), wing_items.to(**i32).contiguous(), *nbr_tables, *wing_tables]
-    c = _lib.D3MMeshTopology(*[t.data_ptr() if t.numel() else None for t in tensors[1:]], V, E, P,
-                             nbr_tables[0].shape[0], nbr_tables[1].shape[0], wing_tables[0].shape[0], wing_tables[1].shape[0],
-                             LONG_ROW)
-    return MeshTopology(*tensors, V, E, P, c)
+    nbr = build_csr(nbr_rows, V, nbr_items)
+    # item = 4 p + role; stable: ascending per vertex
+    wing = build_csr(wings.reshape(-1), V, torch.argsort(wings.reshape(-1), stable=True))
+    edges, wings = torch.stack([ea, eb], 1).to(**i32).contiguous(), wings.to(**i32).contiguous()
+    c = _lib.D3MMeshTopology(nbr.c, wing.c, wings.data_ptr() if P else None, E, P)
+    return MeshTopology(edges, wings, nbr, wing, V, E, P, c)
 
 
 def mesh_topology(faces, num_vertices, cache=None):

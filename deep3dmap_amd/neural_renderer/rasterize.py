@@ -1152,8 +1152,8 @@ class _RasterizeLit(torch.autograd.Function):
                                            vertex_target=None if det else target, visibility=vis[k], unscaled=unscaled,
                                            edge_plan=m["edge_plan"][k])
                     if det:     # K4's and K6's per-face arrays -> the screen-space gradient, per vertex in a fixed order
-                        _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k4), _lib.ptr(det_k6), _lib.ptr(st.adjacency.offsets),
-                                                       _lib.ptr(st.adjacency.items), _lib.ptr(grad_sv), B, V, Ft,
+                        _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k4), _lib.ptr(det_k6), _lib.ptr(st.adjacency.csr.offsets),
+                                                       _lib.ptr(st.adjacency.csr.items), _lib.ptr(grad_sv), B, V, Ft,
                                                        int(fill_back), _lib.ptr(vis[k]), _lib.stream_ptr()),
                                    "d3m_vertex_gather")
         if G > 1:
@@ -1162,7 +1162,7 @@ class _RasterizeLit(torch.autograd.Function):
             # the light gradient -> world-space vertices through the face normals
             if det:     # the views' gradients summed in view order (torch's reduction), the adjoint gathered per vertex
                 total = det_gl.sum(0)           # (one shared mesh, one light: _deterministic_supported)
-                head = (_lib.ptr(vertices), _lib.ptr(tri), _lib.ptr(st.adjacency.offsets), _lib.ptr(st.adjacency.items),
+                head = (_lib.ptr(vertices), _lib.ptr(tri), _lib.ptr(st.adjacency.csr.offsets), _lib.ptr(st.adjacency.csr.items),
                         _lib.ptr(total), _lib.ptr(grad_vertices))
                 if dlight is None:
                     _lib.check(L.d3m_face_light_backward_gather(*head, *by_value, V, Ft, int(fill_back), _lib.stream_ptr()),
@@ -1411,8 +1411,8 @@ class _RasterizeMeshModes(torch.autograd.Function):
                 _lib.zero_raw([_lib.tensor_range(det_k4)])
                 ops.backward_pixel_map(faces, fi, None, alpha_map, None, None, det_k4, S, eps, False, True,
                                        visibility=vis, unscaled=unscaled, edge_plan=plan)
-                _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k4), None, _lib.ptr(st.adjacency.offsets),
-                                               _lib.ptr(st.adjacency.items), _lib.ptr(grad_sv), B, V, Ft, int(fill_back),
+                _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k4), None, _lib.ptr(st.adjacency.csr.offsets),
+                                               _lib.ptr(st.adjacency.csr.items), _lib.ptr(grad_sv), B, V, Ft, int(fill_back),
                                                _lib.ptr(vis), _lib.stream_ptr()), "d3m_vertex_gather")
             else:
                 ops.backward_pixel_map(faces, fi, None, alpha_map, None, None, None, S, eps, False, True, vertex_target=target,
@@ -1441,8 +1441,8 @@ class _RasterizeMeshModes(torch.autograd.Function):
             det_k6 = torch.empty(B, Fp, 3, 3, dtype=torch.float32, device=dev)
             _lib.zero_raw([_lib.tensor_range(det_k6)])
             ops.backward_depth_map(faces, dm, fi, const_tensor((0.0,), dev), wm, g_depth_map, det_k6, S)
-            _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k6), None, _lib.ptr(st.adjacency.offsets),
-                                           _lib.ptr(st.adjacency.items), _lib.ptr(grad_sv), B, V, Ft, int(fill_back),
+            _lib.check(L.d3m_vertex_gather(_lib.ptr(det_k6), None, _lib.ptr(st.adjacency.csr.offsets),
+                                           _lib.ptr(st.adjacency.csr.items), _lib.ptr(grad_sv), B, V, Ft, int(fill_back),
                                            _lib.ptr(vis), _lib.stream_ptr()), "d3m_vertex_gather")
         elif rd and not ra:
             if aa:

@@ -12,6 +12,7 @@ from collections import namedtuple
 import numpy as np
 import torch
 
+from .. import _lib
 from .built_cache import CACHE_SIZE, BuiltCache, tensor_key  # noqa: F401 (they stay importable from here)
 
 LONG_ROW = 64           # rows with more items go through the chunked reduction
@@ -43,6 +44,23 @@ def long_row_chunks(offsets, counts):
             torch.from_numpy(long_chunk_ptr.astype(np.int32)).to(dev))
 
 
+Csr = namedtuple("Csr", "offsets items chunks long_rows long_chunk_ptr num_rows num_chunks num_long_rows c")
+Csr.__doc__ = """One gathered CSR as the kernels read it (all i32, on one device): offsets [R+1], items in the node's layout,
+chunks [C,2] item ranges of the long rows, long_rows [L] (ascending), long_chunk_ptr [L+1], the counts R, C, L, and `c`: the
+d3m_csr (include/d3m_raster.h) that points at them, NULL for an empty tensor; entry points take ctypes.byref(csr.c).  Whoever
+holds the Csr keeps the tensors `c` points at."""
+
+
+def build_csr(rows, num_rows, items):
+    """The Csr of `items` (any integer dtype, one or more columns, already in row order) over num_rows rows; `rows` (i64): the
+    row index of every item, in any order (they are only counted).  Synchronises (the long rows)."""
+    offsets, counts = csr_offsets(rows, num_rows)
+    tensors = (offsets.to(torch.int32), items.to(torch.int32).contiguous(), *long_row_chunks(offsets, counts))
+    sizes = (int(num_rows), tensors[2].shape[0], tensors[3].shape[0])
+    c = _lib.D3MCsr(*[t.data_ptr() if t.numel() else None for t in tensors], *sizes, LONG_ROW)
+    return Csr(*tensors, *sizes, c)
+
+
 def checked_faces(faces):
     if not torch.is_tensor(faces) or faces.dtype not in (torch.int32, torch.int64):
         raise ValueError("faces must be an int32 or int64 tensor")
@@ -51,10 +69,9 @@ def checked_faces(faces):
     return faces
 
 
-Adjacency = namedtuple("Adjacency", "offsets items tri chunks long_rows long_chunk_ptr num_vertices num_faces")
-Adjacency.__doc__ = """The faces of one mesh as the kernels read them: tri [F,3] i32, the CSR offsets [V+1] i32 and items [3F]
-i32 (item = 3 f + c, ascending per vertex: what d3m_vertex_gather walks), chunks [C,2] i32 item ranges of the long rows,
-long_rows [L] i32 (ascending) and long_chunk_ptr [L+1] i32."""
+Adjacency = namedtuple("Adjacency", "csr tri num_vertices num_faces")
+Adjacency.__doc__ = """The faces of one mesh as the kernels read them: tri [F,3] i32 and csr, the Csr of V rows whose items [3F]
+are 3 f + c, ascending per vertex (offsets and items are what d3m_vertex_gather walks)."""
 
 
 class AdjacencyCache(BuiltCache):
@@ -78,11 +95,8 @@ def build_adjacency(faces, num_vertices):
     if lo < 0 or hi >= V:
         raise ValueError(f"faces: vertex indices must be in [0, {V}) (found {lo if lo < 0 else hi})")
     # stable: a vertex's items keep ascending order
-    items = torch.argsort(flat, stable=True).to(torch.int32).contiguous()
-    offsets, counts = csr_offsets(flat, V)
-    chunks, long_rows, long_chunk_ptr = long_row_chunks(offsets, counts)
-    return Adjacency(offsets.to(torch.int32), items, faces.reshape(-1, 3).to(torch.int32).contiguous(),
-                     chunks, long_rows, long_chunk_ptr, V, int(flat.numel() // 3))
+    csr = build_csr(flat, V, torch.argsort(flat, stable=True))
+    return Adjacency(csr, faces.reshape(-1, 3).to(torch.int32).contiguous(), V, int(flat.numel() // 3))
 
 
 def vertex_adjacency(faces, num_vertices, cache=None):

@@ -15,6 +15,7 @@ fixed order for every sum (csrc/d3m_smooth_shade.h states it): rows of the faces
 vertices through the chunks of row_gather.py, the 27 sums of grad_sh through the tree of pose.py, shared inputs summed over
 the sets in ascending order.  The adjacency is built once per faces tensor (vertex_adjacency: the one host read, outside
 any capture) and after that the node never synchronises."""
+import ctypes
 import math
 
 import torch
@@ -22,7 +23,7 @@ import torch.nn as nn
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
-from .row_gather import LONG_ROW, AdjacencyCache, checked_faces, vertex_adjacency
+from .row_gather import LONG_ROW, AdjacencyCache, checked_faces, vertex_adjacency  # noqa: F401 (LONG_ROW stays importable from here)
 
 MAX_SETS = 65535
 # the constants of the reference's fit_illumination (renderer_demo/mesh_cython/render.py:59-67)
@@ -41,15 +42,8 @@ def sh_basis(normals):
                         a3 * (ny * nz), a3 * (nx * nz), a3 * (nx * ny), a4 * (nx * nx - ny * ny)], -1)
 
 
-def _adjacency_args(A):
-    n_chunks = A.chunks.shape[0]
-    return (_lib.ptr(A.tri), _lib.ptr(A.offsets), _lib.ptr(A.items), _lib.ptr(A.chunks) if n_chunks else None, n_chunks,
-            _lib.ptr(A.long_rows) if n_chunks else None, _lib.ptr(A.long_chunk_ptr) if n_chunks else None,
-            A.long_rows.shape[0] if n_chunks else 0, LONG_ROW)
-
-
 def _scratch(B, vb, A, device):
-    n = int(_lib.lib().d3m_smooth_shade_scratch_floats(B, vb, A.num_vertices, A.num_faces, A.chunks.shape[0]))
+    n = int(_lib.lib().d3m_smooth_shade_scratch_floats(B, vb, A.num_vertices, A.num_faces, A.csr.num_chunks))
     if n == 0:
         raise ValueError("sets * vertices * 3 must stay below 2^31")
     return torch.empty(n, dtype=torch.float32, device=device), n
@@ -66,8 +60,8 @@ def forward(vertices, colors, sh, adjacency):
     lengths = torch.empty(vb, V, dtype=torch.float32, device=dev)
     _lib.check(_lib.lib().d3m_smooth_shade_forward(
         _lib.ptr(vertices), vb, _lib.ptr(colors), 1 if colors is None else colors.shape[0], _lib.ptr(sh),
-        1 if sh is None else sh.shape[0], *_adjacency_args(A), _lib.ptr(scratch), n, _lib.ptr(shaded), _lib.ptr(normals),
-        _lib.ptr(lengths), B, V, A.num_faces, _lib.stream_ptr()), "d3m_smooth_shade_forward")
+        1 if sh is None else sh.shape[0], _lib.ptr(A.tri), ctypes.byref(A.csr.c), _lib.ptr(scratch), n, _lib.ptr(shaded),
+        _lib.ptr(normals), _lib.ptr(lengths), B, V, A.num_faces, _lib.stream_ptr()), "d3m_smooth_shade_forward")
     return shaded, normals, lengths
 
 
@@ -87,8 +81,8 @@ def backward(vertices, colors, sh, normals, lengths, adjacency, grad_shaded=None
     _lib.check(_lib.lib().d3m_smooth_shade_backward(
         _lib.ptr(vertices), vb, _lib.ptr(colors), 1 if colors is None else colors.shape[0], _lib.ptr(sh),
         1 if sh is None else sh.shape[0], _lib.ptr(normals), _lib.ptr(lengths), _lib.ptr(grad_shaded), _lib.ptr(grad_normals),
-        *_adjacency_args(A), _lib.ptr(scratch), n, _lib.ptr(g_v), _lib.ptr(g_c), _lib.ptr(g_sh), B, V, A.num_faces,
-        _lib.stream_ptr()), "d3m_smooth_shade_backward")
+        _lib.ptr(A.tri), ctypes.byref(A.csr.c), _lib.ptr(scratch), n, _lib.ptr(g_v), _lib.ptr(g_c), _lib.ptr(g_sh), B, V,
+        A.num_faces, _lib.stream_ptr()), "d3m_smooth_shade_backward")
     return g_v, g_c, g_sh
 
 

@@ -10,6 +10,7 @@ chunked reduction that row_gather.py describes.
 
 The layout (faces_uv, face mask, texture size, image size, wrapping, filter) is a constant: a gradient with respect to
 faces_uv raises NotImplementedError."""
+import ctypes
 from collections import namedtuple
 
 import torch
@@ -17,12 +18,12 @@ import torch.nn as nn
 
 from .. import _lib
 from . import obj_io
-from .row_gather import CACHE_SIZE, CHUNK, LONG_ROW, BuiltCache, csr_offsets, long_row_chunks, tensor_key  # noqa: F401 (the constants stay importable from here)
+from .row_gather import CACHE_SIZE, CHUNK, LONG_ROW, BuiltCache, build_csr, csr_offsets, long_row_chunks, tensor_key  # noqa: F401 (the constants stay importable from here)
 
-Transpose = namedtuple("Transpose", "row_ptr entries chunks long_rows long_chunk_ptr lanes_per_row num_texels height width")
-Transpose.__doc__ = """The transpose of one layout's sampling map: row_ptr [H*W+1] i32, entries [nnz,2] i32 (texel, weight
-bits), chunks [C,2] i32 entry ranges of the long rows, long_rows [L] i32 (ascending), long_chunk_ptr [L+1] i32, and the lanes
-that walk each other row (a power of two, about a quarter of the mean length of a non-empty row)."""
+Transpose = namedtuple("Transpose", "csr lanes_per_row num_texels height width")
+Transpose.__doc__ = """The transpose of one layout's sampling map: csr, the row_gather.Csr of H*W rows whose items [nnz,2] are
+(texel, weight bits), and the lanes that walk each row that is not long (a power of two, about a quarter of the mean length
+of a non-empty row)."""
 
 
 def _wrapping_code(texture_wrapping):
@@ -63,20 +64,18 @@ def build_transpose(faces_uv, mask32, texture_size, height, width, wrapping, use
         _lib.ptr(pixel), _lib.ptr(weight), _lib.stream_ptr()), "d3m_uv_texture_taps")
     # stable: a pixel's entries keep ascending entry order = ascending (texel, tap); dropped entries (pixel H*W) sort last
     keys, order = torch.sort(pixel, stable=True)
-    row_ptr, counts = csr_offsets(keys.long(), n_pix + 1)
-    row_ptr, counts = row_ptr[:-1], counts[:-1]                 # (without the row of the dropped entries)
-    nnz = int(row_ptr[-1])
+    nnz = int((keys < n_pix).sum())
     order = order[:nnz]
     entries = torch.stack([torch.div(order, taps, rounding_mode="floor").to(torch.int32),
-                           weight[order].view(torch.int32)], 1).contiguous()
-    # the long rows and their chunks (few: pixel (0,0) and whatever a layout piles up)
-    chunks, long_rows, long_chunk_ptr = long_row_chunks(row_ptr, counts)
+                           weight[order].view(torch.int32)], 1)
+    # (the long rows are few: pixel (0,0) and whatever a layout piles up)
+    csr = build_csr(keys[:nnz].long(), n_pix, entries)
     # a row's walk is a chain of dependent loads: split the typical row over a few lanes (fixed per layout)
-    mean = nnz / max(1, int((counts > 0).sum()))
+    mean = nnz / max(1, int((csr.offsets[1:] > csr.offsets[:-1]).sum()))
     lanes = 1
     while lanes < 16 and lanes * 4 < mean:
         lanes *= 2
-    return Transpose(row_ptr.to(torch.int32), entries, chunks, long_rows, long_chunk_ptr, lanes, n_texels, height, width)
+    return Transpose(csr, lanes, n_texels, height, width)
 
 
 def uv_transpose(faces_uv, texture_size, height, width, texture_wrapping='REPEAT', use_bilinear=True, faces_mask=None):
@@ -95,15 +94,13 @@ def uv_texture_adjoint(transpose, grad_textures):
     T = transpose
     B = grad_textures.shape[0]
     g = grad_textures.to(torch.float32).contiguous()
-    if g.dim() != 2 or g.shape[1] != T.num_texels * 3 or g.device != T.row_ptr.device:
-        raise ValueError(f"grad_textures must be [B, {T.num_texels * 3}] on {T.row_ptr.device}")
+    if g.dim() != 2 or g.shape[1] != T.num_texels * 3 or g.device != T.csr.offsets.device:
+        raise ValueError(f"grad_textures must be [B, {T.num_texels * 3}] on {T.csr.offsets.device}")
     grad_image = torch.empty(B, T.height, T.width, 3, dtype=torch.float32, device=g.device)
-    n_chunks = T.chunks.shape[0]
-    partials = torch.empty(B, n_chunks, 3, dtype=torch.float32, device=g.device) if n_chunks else None
+    partials = torch.empty(B, T.csr.num_chunks, 3, dtype=torch.float32, device=g.device) if T.csr.num_chunks else None
     _lib.check(_lib.lib().d3m_uv_texture_adjoint(
-        _lib.ptr(T.row_ptr), _lib.ptr(T.entries), _lib.ptr(T.chunks), n_chunks, _lib.ptr(T.long_rows),
-        _lib.ptr(T.long_chunk_ptr), T.long_rows.shape[0], LONG_ROW, T.lanes_per_row, _lib.ptr(g), _lib.ptr(partials), _lib.ptr(grad_image),
-        B, T.num_texels, T.height, T.width, _lib.stream_ptr()), "d3m_uv_texture_adjoint")
+        ctypes.byref(T.csr.c), T.lanes_per_row, _lib.ptr(g), _lib.ptr(partials), _lib.ptr(grad_image), B, T.num_texels,
+        T.height, T.width, _lib.stream_ptr()), "d3m_uv_texture_adjoint")
     return grad_image
 
 

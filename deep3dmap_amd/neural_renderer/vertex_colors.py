@@ -12,13 +12,15 @@ on every run.  A hub vertex (a fan apex, a pole) must not make one lane walk tho
 items go through the chunked reduction that row_gather.py describes.  The adjacency is built once per (faces tensor,
 version, V) with torch operators -- where the indices are checked against V -- and kept in row_gather's bounded LRU cache,
 the one the deterministic mode's per-vertex gathers read theirs from."""
+import ctypes
+
 import torch
 import torch.nn as nn
 
 from .. import _lib
 # (the adjacency, its cache and the constants stay importable from here)
-from .row_gather import (CACHE_SIZE, CHUNK, LONG_ROW, Adjacency, AdjacencyCache, BuiltCache, _cache, _faces_key,  # noqa: F401
-                         build_adjacency, checked_faces as _checked_faces, csr_offsets, long_row_chunks, tensor_key,
+from .row_gather import (CACHE_SIZE, CHUNK, LONG_ROW, Adjacency, AdjacencyCache, BuiltCache, Csr, _cache, _faces_key,  # noqa: F401
+                         build_adjacency, build_csr, checked_faces as _checked_faces, csr_offsets, long_row_chunks, tensor_key,
                          vertex_adjacency)
 
 
@@ -26,16 +28,13 @@ def vertex_color_adjoint(adjacency, grad_textures):
     """grad_colors [B,V,3] of grad_textures [B,F,2,2,2,3] through the adjacency (d3m_vertex_color_textures_backward)."""
     A = adjacency
     g = grad_textures.to(torch.float32).contiguous()
-    if g.dim() != 6 or tuple(g.shape[1:]) != (A.num_faces, 2, 2, 2, 3) or g.device != A.offsets.device:
-        raise ValueError(f"grad_textures must be [B, {A.num_faces}, 2, 2, 2, 3] on {A.offsets.device}")
+    if g.dim() != 6 or tuple(g.shape[1:]) != (A.num_faces, 2, 2, 2, 3) or g.device != A.tri.device:
+        raise ValueError(f"grad_textures must be [B, {A.num_faces}, 2, 2, 2, 3] on {A.tri.device}")
     B = g.shape[0]
     grad_colors = torch.empty(B, A.num_vertices, 3, dtype=torch.float32, device=g.device)
-    n_chunks = A.chunks.shape[0]
-    partials = torch.empty(B, n_chunks, 3, dtype=torch.float32, device=g.device) if n_chunks else None
+    partials = torch.empty(B, A.csr.num_chunks, 3, dtype=torch.float32, device=g.device) if A.csr.num_chunks else None
     _lib.check(_lib.lib().d3m_vertex_color_textures_backward(
-        _lib.ptr(g), _lib.ptr(A.offsets), _lib.ptr(A.items), _lib.ptr(A.chunks) if n_chunks else None, n_chunks,
-        _lib.ptr(A.long_rows) if n_chunks else None, _lib.ptr(A.long_chunk_ptr) if n_chunks else None,
-        A.long_rows.shape[0], LONG_ROW, _lib.ptr(partials), _lib.ptr(grad_colors), B, A.num_vertices, A.num_faces,
+        _lib.ptr(g), ctypes.byref(A.csr.c), _lib.ptr(partials), _lib.ptr(grad_colors), B, A.num_vertices, A.num_faces,
         _lib.stream_ptr()), "d3m_vertex_color_textures_backward")
     return grad_colors
 

@@ -835,19 +835,34 @@ int d3m_textures_from_image(const float* image, int image_batch, const float* fa
 int d3m_uv_texture_taps(const float* faces_uv, const int32_t* face_mask, int num_faces, int texture_size, int image_height,
                         int image_width, int texture_wrapping, int use_bilinear, int32_t* pixel, float* weight,
                         d3m_stream_t stream);
+/* A gathered CSR with its long-row tables: what every fixed-order adjoint below walks (device arrays of i32, built once by
+ * the caller; every index in range: the caller checks).  Row r owns items[offsets[r] .. offsets[r+1]) in the node's item
+ * layout.  A row of up to long_row items is summed by its own lane(s) in item order.  A longer row (a hub) is listed in
+ * long_rows (ascending) and cut into chunks, item ranges [start, end) i32x2 of at most 1024 items in row order; long row l
+ * owns chunks[long_chunk_ptr[l] .. long_chunk_ptr[l+1]).  Each chunk is reduced by one workgroup in a fixed order
+ * (csrc/d3m_row_gather.h states it) into the entry point's partials (scratch, plainly stored), and the row adds its chunks'
+ * sums in chunk order.
+ * Every entry point that takes one returns D3M_ERR_INVALID for: a NULL d3m_csr, NULL offsets, num_rows that is not the row
+ * count it walks, a negative count, long_row < 0, long rows without chunks or chunks without long rows, chunks with a NULL
+ * items / chunks / long_rows / long_chunk_ptr or without partials. */
+typedef struct d3m_csr {
+    const int32_t *offsets;         /* [num_rows + 1] */
+    const int32_t *items;           /* the node's item layout (adjacency: 3 f + c; uv: (texel, weight bits) pairs) */
+    const int32_t *chunks;          /* [num_chunks, 2] or NULL */
+    const int32_t *long_rows;       /* [num_long_rows] ascending, or NULL */
+    const int32_t *long_chunk_ptr;  /* [num_long_rows + 1] or NULL */
+    int num_rows, num_chunks, num_long_rows, long_row;
+} d3m_csr;
 /* The adjoint (no float atomics, the same bits on every run): WRITES grad_image [batch_size, H, W, 3] from grad_textures
- * [batch_size, num_texels, 3] through the transpose row_ptr [H*W+1] i32, entries [nnz, 2] i32 (texel, weight's f32
- * bits), each row in ascending texel order.  Rows of more than long_row entries are listed in long_rows [num_long_rows]
- * (ascending); the chunks of long row l are chunks[long_chunk_ptr[l] .. long_chunk_ptr[l+1]), each an entry range
- * [start, end) i32x2, reduced in a fixed order into partials [batch_size, num_chunks, 3] f32 (scratch) and added in chunk
- * order.  The other rows are walked by lanes_per_row (1, 2, 4, 8 or 16) lanes each: lane s sums entries s, s +
- * lanes_per_row, ... and the lanes' sums are combined by a butterfly -- a fixed order for a given lanes_per_row.
- * D3M_ERR_INVALID: NULL row_ptr / grad_textures / grad_image, a size <= 0, batch_size > 65535, long_row < 0,
- * lanes_per_row not a listed value, long rows without chunks, chunks without entries or partials. */
-int d3m_uv_texture_adjoint(const int32_t* row_ptr, const int32_t* entries, const int32_t* chunks, int num_chunks,
-                           const int32_t* long_rows, const int32_t* long_chunk_ptr, int num_long_rows, int long_row,
-                           int lanes_per_row, const float* grad_textures, float* partials, float* grad_image,
-                           int batch_size, long num_texels, int image_height, int image_width, d3m_stream_t stream);
+ * [batch_size, num_texels, 3] through the transpose: a d3m_csr of H*W rows whose items [nnz, 2] are (texel, weight's f32
+ * bits), each row in ascending texel order (NULL where nnz = 0); partials [batch_size, num_chunks, 3] f32.  The rows that
+ * are not long are walked by lanes_per_row (1, 2, 4, 8 or 16) lanes each: lane s sums entries s, s + lanes_per_row, ... and
+ * the lanes' sums are combined by a butterfly -- a fixed order for a given lanes_per_row.
+ * D3M_ERR_INVALID: what d3m_csr lists, NULL grad_textures / grad_image, a size <= 0, batch_size > 65535, lanes_per_row not a
+ * listed value. */
+int d3m_uv_texture_adjoint(const d3m_csr* transpose, int lanes_per_row, const float* grad_textures, float* partials,
+                           float* grad_image, int batch_size, long num_texels, int image_height, int image_width,
+                           d3m_stream_t stream);
 /* Learnable per-vertex colours of an indexed mesh: the map colours -> 2x2x2 cubes and its adjoint.
  * colors [color_batch, V, 3], tri [F, 3] i32 (every index in [0, V): the caller checks).  WRITES textures
  * [color_batch, F, 2, 2, 2, 3]: texel idx of face f, channel k, is (C[idx][0] c0 + C[idx][1] c1) + C[idx][2] c2 with
@@ -857,33 +872,24 @@ int d3m_uv_texture_adjoint(const int32_t* row_ptr, const int32_t* entries, const
 int d3m_vertex_color_textures(const float* colors, int color_batch, const int32_t* tri, float* textures, int num_vertices,
                               int num_tri, d3m_stream_t stream);
 /* The adjoint (no float atomics, the same bits on every run): WRITES every element of grad_colors [batch_size, V, 3] from
- * grad_textures [batch_size, F, 2, 2, 2, 3] through the CSR adjacency d3m_vertex_gather walks (adj_offsets [V+1], adj_items
- * [3 F], item = 3 f + c ascending per vertex): the sum, in item order, of each item's term t = sum over idx ascending of
- * C[idx][c] * grad_textures[b, f, idx, k]; a vertex of no face gets 0.  Rows of more than long_row items are listed in
- * long_rows [num_long_rows] (ascending); the chunks of long row l are chunks[long_chunk_ptr[l] .. long_chunk_ptr[l+1]), each
- * an item range [start, end) i32x2, reduced in a fixed order into partials [batch_size, num_chunks, 3] f32 (scratch) and
- * added in chunk order.
- * D3M_ERR_INVALID: NULL grad_textures / adj_offsets / adj_items / grad_colors, a size <= 0, batch_size > 65535,
- * long_row < 0, 3 F beyond int32, long rows without chunks, chunks without partials. */
-int d3m_vertex_color_textures_backward(const float* grad_textures, const int32_t* adj_offsets, const int32_t* adj_items,
-                                       const int32_t* chunks, int num_chunks, const int32_t* long_rows,
-                                       const int32_t* long_chunk_ptr, int num_long_rows, int long_row, float* partials,
+ * grad_textures [batch_size, F, 2, 2, 2, 3] through the faces' adjacency: a d3m_csr of V rows, the one d3m_vertex_gather
+ * walks (items [3 F], item = 3 f + c ascending per vertex): the sum, in item order, of each item's term t = sum over idx
+ * ascending of C[idx][c] * grad_textures[b, f, idx, k]; a vertex of no face gets 0.  partials [batch_size, num_chunks, 3] f32.
+ * D3M_ERR_INVALID: what d3m_csr lists, NULL grad_textures / items / grad_colors, a size <= 0, batch_size > 65535, 3 F beyond
+ * int32. */
+int d3m_vertex_color_textures_backward(const float* grad_textures, const d3m_csr* adjacency, float* partials,
                                        float* grad_colors, int batch_size, int num_vertices, int num_tri,
                                        d3m_stream_t stream);
-/* Shape regularisers of an indexed mesh (no float atomics, the same bits on every run).  The topology of the faces, device
- * arrays of i32 built once by the caller (neural_renderer/mesh_regularizers.py; every index in range: the caller checks):
- * the E unique edges as a neighbour CSR (nbr_offsets [V+1], nbr_items [2E]: the distinct neighbours of a vertex, ascending);
- * the P wing records wings [P,4] = (a, b, c, d): an edge a < b and the third vertices c, d of two faces on it; the wing CSR
- * (wing_offsets [V+1], wing_items [4P]: item = 4 p + role, role 0..3 for a, b, c, d, ascending per vertex).  Rows of more
- * than long_row items of either CSR are listed in *_long_rows (ascending) with their chunks (item ranges [start, end) i32x2)
- * chunks[long_chunk_ptr[l] .. long_chunk_ptr[l+1]), as for d3m_vertex_color_textures_backward. */
+/* Shape regularisers of an indexed mesh (no float atomics, the same bits on every run).  The topology of the faces, built
+ * once by the caller (neural_renderer/mesh_regularizers.py; every index in range: the caller checks), two d3m_csr of V rows
+ * each and the wing records: nbr, the E unique edges as a neighbour CSR (items [2E]: the distinct neighbours of a vertex,
+ * ascending; NULL where E = 0); wings [P,4] i32 = (a, b, c, d): an edge a < b and the third vertices c, d of two faces on it;
+ * wing, the wing CSR (items [4P]: item = 4 p + role, role 0..3 for a, b, c, d, ascending per vertex).  The vertex count is
+ * nbr.num_rows, and wing.num_rows equals it. */
 typedef struct d3m_mesh_topology {
-    const int32_t *nbr_offsets, *nbr_items, *wings, *wing_offsets, *wing_items;
-    const int32_t *nbr_chunks, *nbr_long_rows, *nbr_long_chunk_ptr;
-    const int32_t *wing_chunks, *wing_long_rows, *wing_long_chunk_ptr;
-    int num_vertices, num_edges, num_wings;
-    int num_nbr_chunks, num_nbr_long_rows, num_wing_chunks, num_wing_long_rows;
-    int long_row;
+    d3m_csr nbr, wing;
+    const int32_t* wings;
+    int num_edges, num_wings;
 } d3m_mesh_topology;
 /* Floats of scratch d3m_mesh_regularizer needs for batch_size vertex sets (0 for an invalid argument). */
 size_t d3m_mesh_regularizer_scratch_floats(int batch_size, const d3m_mesh_topology* topology);
@@ -896,9 +902,9 @@ size_t d3m_mesh_regularizer_scratch_floats(int batch_size, const d3m_mesh_topolo
  * accumulate != 0 both are ADDED to what is there.  grad_vertices NULL: the value only.  scratch: 16-byte aligned,
  * scratch_floats >= d3m_mesh_regularizer_scratch_floats().  At most 3 launches (k_mesh_reg_delta, k_mesh_reg_rows,
  * k_mesh_reg_finish), 2 more on a mesh with long rows (k_mesh_reg_mean_chunks, k_mesh_reg_row_chunks).
- * D3M_ERR_INVALID, before any launch: NULL vertices / topology / loss_out / scratch / a NULL array of the topology that the
- * enabled terms read, a size <= 0 (V; E and P < 0), batch_size > 65535, a negative (or NaN) weight or edge_target, 2E or 4P
- * beyond int32, long rows without chunks, chunks without their ranges, a scratch that is too small or misaligned. */
+ * D3M_ERR_INVALID, before any launch: what d3m_csr lists of either CSR (V = nbr.num_rows rows; the partials are in scratch),
+ * NULL vertices / topology / loss_out / scratch / items or wings that the enabled terms read, E or P < 0, batch_size outside
+ * [1, 65535], a negative (or NaN) weight or edge_target, 2E or 4P beyond int32, a scratch that is too small or misaligned. */
 int d3m_mesh_regularizer(const float* vertices, int batch_size, const d3m_mesh_topology* topology, float w_laplacian,
                          float w_edge, float edge_target, float w_normal, float* scratch, size_t scratch_floats,
                          const float* grad_scale, float* loss_out, float* grad_vertices, int accumulate,
@@ -974,8 +980,8 @@ int d3m_pose_backward(const float* vertices, int vertices_batch, const float* po
 /* Smooth per-vertex normals of an indexed mesh and a 9-term spherical-harmonic light on per-vertex albedo, with the adjoint
  * (no float atomics, the same bits on every run; plain f32; csrc/d3m_smooth_shade.h states the order of every sum).
  * vertices [vertices_batch, V, 3], colors [colors_batch, V, 3], sh [sh_batch, 3, 9]: each batch is 1 (shared by all sets) or
- * batch_size.  tri [F, 3] i32 and the adjacency (adj_offsets [V+1], adj_items [3 F], the long-row tables) are those of
- * d3m_vertex_color_textures_backward (every index in range: the caller checks).
+ * batch_size.  tri [F, 3] i32 and the adjacency (a d3m_csr of V rows, item = 3 f + c) are those of
+ * d3m_vertex_color_textures_backward (every index in range: the caller checks); the partials are in scratch.
  *   N_f = (x1 - x0) x (x2 - x0);  s[b,v] = the sum of N_f over v's items in ascending order;  r = |s|;  n = s / max(r, 1e-6)
  *   H(n) = (a0, a1 nx, a1 ny, a1 nz, a2 (2 nz^2 - nx^2 - ny^2), a3 ny nz, a3 nx nz, a3 nx ny, a4 (nx^2 - ny^2)) with
  *   a0 = sqrt(1/4pi), a1 = sqrt(3/4pi), a2 = a1 / 2, a3 = 3 sqrt(5/12pi), a4 = a3 / 2
@@ -984,14 +990,12 @@ int d3m_pose_backward(const float* vertices, int vertices_batch, const float* po
  * [batch_size, V, 3].  colors NULL: the normals only (shaded NULL, batch_size == vertices_batch; sh is not read).  At most
  * three launches (k_smooth_shade_face_normals, k_smooth_shade_normal_chunks on a mesh with long rows, k_smooth_shade_vertices).
  * scratch_floats >= d3m_smooth_shade_scratch_floats().
- * D3M_ERR_INVALID, before any launch: NULL vertices / tri / adj_offsets / adj_items / scratch / normals / lengths, colors
+ * D3M_ERR_INVALID, before any launch: what d3m_csr lists, NULL vertices / tri / items / scratch / normals / lengths, colors
  * without sh or shaded, shaded without colors, batch_size outside [1, 65535], a batch that is neither 1 nor batch_size, a
- * size <= 0, 3 F beyond int32, batch_size * V * 3 >= 2^31, long_row < 0, long rows without chunks, a scratch that is too
- * small, a pointer that is not 4-byte aligned. */
+ * size <= 0, 3 F beyond int32, batch_size * V * 3 >= 2^31, a scratch that is too small, a pointer that is not 4-byte
+ * aligned. */
 int d3m_smooth_shade_forward(const float* vertices, int vertices_batch, const float* colors, int colors_batch,
-                             const float* sh, int sh_batch, const int32_t* tri, const int32_t* adj_offsets,
-                             const int32_t* adj_items, const int32_t* chunks, int num_chunks, const int32_t* long_rows,
-                             const int32_t* long_chunk_ptr, int num_long_rows, int long_row, float* scratch,
+                             const float* sh, int sh_batch, const int32_t* tri, const d3m_csr* adjacency, float* scratch,
                              size_t scratch_floats, float* shaded, float* normals, float* lengths, int batch_size,
                              int num_vertices, int num_tri, d3m_stream_t stream);
 /* Floats of scratch the two entry points need (0 for sizes they refuse): vertices_batch * (3 V + 9 F + 3 num_chunks) +
@@ -1008,10 +1012,9 @@ size_t d3m_smooth_shade_scratch_floats(int batch_size, int vertices_batch, int n
 int d3m_smooth_shade_backward(const float* vertices, int vertices_batch, const float* colors, int colors_batch,
                               const float* sh, int sh_batch, const float* normals, const float* lengths,
                               const float* grad_shaded, const float* grad_normals, const int32_t* tri,
-                              const int32_t* adj_offsets, const int32_t* adj_items, const int32_t* chunks, int num_chunks,
-                              const int32_t* long_rows, const int32_t* long_chunk_ptr, int num_long_rows, int long_row,
-                              float* scratch, size_t scratch_floats, float* grad_vertices, float* grad_colors,
-                              float* grad_sh, int batch_size, int num_vertices, int num_tri, d3m_stream_t stream);
+                              const d3m_csr* adjacency, float* scratch, size_t scratch_floats, float* grad_vertices,
+                              float* grad_colors, float* grad_sh, int batch_size, int num_vertices, int num_tri,
+                              d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row

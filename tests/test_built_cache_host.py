@@ -55,14 +55,14 @@ CASES = [
     _Case("transpose", uvt.TransposeCache, uvt, "_cache", built_cache.CACHE_SIZE, "transpose.*capture"),
     _Case("adjacency", vc.AdjacencyCache, vc, "_cache", built_cache.CACHE_SIZE, "adjacency.*capture",
           tensors=lambda: (_faces(),), use=lambda cache, t, V: vc.vertex_adjacency(t[0], V, cache=cache),
-          read=lambda A: A.offsets, takes_v=True),
+          read=lambda A: A.csr.offsets, takes_v=True),
     # ... as rasterize.py and mesh_ops.py reach it in the deterministic mode: the int32 index tensor [1,F,3] of a render node
     _Case("deterministic_adjacency", rg.AdjacencyCache, rg, "_cache", built_cache.CACHE_SIZE, "adjacency.*capture",
           tensors=lambda: (_faces(1, dtype=torch.int32),), use=lambda cache, t, V: rg.vertex_adjacency(t[0], V, cache=cache),
-          read=lambda A: A.items, takes_v=True),
+          read=lambda A: A.csr.items, takes_v=True),
     _Case("topology", mr.TopologyCache, mr, "_cache", built_cache.CACHE_SIZE, "topology.*capture",
           tensors=lambda: (_faces(),), use=lambda cache, t, V: mr.mesh_topology(t[0], V, cache=cache),
-          read=lambda T: T.nbr_offsets, takes_v=True),
+          read=lambda T: T.nbr.offsets, takes_v=True),
     _Case("landmarks", pose.LandmarkCache, pose, "_checked_landmarks", 8, "landmark.*capture",
           tensors=lambda: (torch.tensor([0, 3, 3, 1]),),            # int64: the int32 form is the cache's alone
           use=_through_module_cache(pose, "_checked_landmarks", lambda t, V: pose._landmarks_in_range(t[0], V)),
@@ -157,7 +157,7 @@ def test_cache_key_of_each_structure():
     A = vc.vertex_adjacency(faces, 4, cache=cache)
     faces[1, 2] = 0
     B = vc.vertex_adjacency(faces, 4, cache=cache)
-    assert B is not A and B.offsets.tolist() == [0, 2, 4, 6, 6]
+    assert B is not A and B.csr.offsets.tolist() == [0, 2, 4, 6, 6]
     cache = mr.TopologyCache(size=2)
     U = mr.mesh_topology(faces, 4, cache=cache)
     assert U.edges.tolist() == [[0, 1], [0, 2], [1, 2]] and U.num_wings == 3
@@ -265,12 +265,49 @@ def test_vertex_adjacency_equals_a_restatement(name):
     flat = tri_np.reshape(-1).astype(np.int64)
     offsets = np.concatenate([[0], np.cumsum(np.bincount(flat, minlength=V))]).astype(np.int32)
     items = np.argsort(flat, kind="stable").astype(np.int32)
-    assert A.offsets.dtype == torch.int32 and A.items.dtype == torch.int32
-    assert A.offsets.is_contiguous() and A.items.is_contiguous()
-    assert torch.equal(A.offsets, torch.from_numpy(offsets)) and torch.equal(A.items, torch.from_numpy(items))
+    assert A.csr.offsets.dtype == torch.int32 and A.csr.items.dtype == torch.int32
+    assert A.csr.offsets.is_contiguous() and A.csr.items.is_contiguous()
+    assert torch.equal(A.csr.offsets, torch.from_numpy(offsets)) and torch.equal(A.csr.items, torch.from_numpy(items))
     assert (A.num_vertices, A.num_faces) == (V, tri_np.shape[0]) and torch.equal(A.tri, tri[0])
     for v in (0, V // 2, V - 1):                            # item = 3 f + c names the corners that hold v, ascending
         row = items[offsets[v]:offsets[v + 1]]
         assert np.all(flat[row] == v) and np.all(np.diff(row) > 0)
     n_long = int((np.diff(offsets) > rg.LONG_ROW).sum())
-    assert A.long_rows.numel() == n_long == (1 if name == "fan(200)" else 0) and A.chunks.shape[0] == n_long
+    assert A.csr.long_rows.numel() == n_long == (1 if name == "fan(200)" else 0) and A.csr.chunks.shape[0] == n_long
+
+
+def _assert_struct_points_at(csr):
+    """csr.c, the d3m_csr the entry points read: every pointer is its tensor's (NULL for an empty one), every count its own"""
+    for name in ("offsets", "items", "chunks", "long_rows", "long_chunk_ptr"):
+        t = getattr(csr, name)
+        assert t.dtype == torch.int32 and t.is_contiguous(), name
+        assert getattr(csr.c, name) == (t.data_ptr() if t.numel() else None), name
+    assert (csr.c.num_rows, csr.c.num_chunks, csr.c.num_long_rows) == (csr.num_rows, csr.num_chunks, csr.num_long_rows) == \
+        (csr.offsets.numel() - 1, csr.chunks.shape[0], csr.long_rows.numel())
+    assert csr.long_chunk_ptr.numel() == csr.num_long_rows + 1 and csr.c.long_row == rg.LONG_ROW
+
+
+@pytest.mark.parametrize("name", list(_meshes()))
+def test_csr_struct_points_at_its_tensors(name):
+    tri_np, V = _meshes()[name]
+    faces = torch.from_numpy(np.ascontiguousarray(tri_np)).long()
+    A = rg.build_adjacency(faces, V)
+    _assert_struct_points_at(A.csr)
+    assert (A.csr.num_rows, A.csr.num_long_rows) == (V, 1 if name == "fan(200)" else 0)
+    assert (A.csr.c.chunks is None) == (A.csr.c.long_rows is None) == (name != "fan(200)")
+    T = mr.build_topology(faces, V)
+    _assert_struct_points_at(T.nbr)
+    _assert_struct_points_at(T.wing)
+    # the topology nests copies of both structs
+    for kind in ("nbr", "wing"):
+        nested, own = getattr(T.c, kind), getattr(T, kind).c
+        assert all(getattr(nested, f) == getattr(own, f) for f, _ in own._fields_), kind
+    assert T.c.wings == (T.wings.data_ptr() if T.num_wings else None) and (T.c.num_edges, T.c.num_wings) == (T.num_edges, T.num_wings)
+
+
+def test_csr_of_no_items_has_null_pointers_and_zero_counts():
+    csr = rg.build_csr(torch.zeros(0, dtype=torch.int64), 5, torch.zeros(0, 2, dtype=torch.int64))
+    _assert_struct_points_at(csr)
+    assert csr.offsets.tolist() == [0] * 6 and csr.long_chunk_ptr.tolist() == [0]
+    assert csr.c.items is None and csr.c.chunks is None and csr.c.long_rows is None
+    assert (csr.c.num_rows, csr.c.num_chunks, csr.c.num_long_rows) == (5, 0, 0)

@@ -18,9 +18,13 @@ def _bits(t):
     return t.detach().contiguous().view(torch.int32)
 
 
+def _holds(r, t):
+    return r is t or (isinstance(r, tuple) and any(_holds(x, t) for x in r))
+
+
 def _kept(refs, alive):
-    """`alive()` (a tensor) is, or is a field of, one of the objects the captured step holds."""
-    return any(r is alive() or (isinstance(r, tuple) and any(x is alive() for x in r)) for r in refs)
+    """`alive()` (a tensor) is, or is a field (of a field: Adjacency.csr.items) of, one of the objects the captured step holds."""
+    return any(_holds(r, alive()) for r in refs)
 
 
 def _replays_equal(captured, eager):
@@ -51,7 +55,7 @@ def test_deterministic_lit_step_keeps_its_adjacency_after_eviction():
         fit.capture_graph()
         adjacency = rg.vertex_adjacency(fit.triangles[None], v.shape[0])       # (a hit: what the node's state holds)
         assert adjacency.num_faces == tri.shape[0]
-        items = weakref.ref(adjacency.items)
+        items = weakref.ref(adjacency.csr.items)
         _evict_adjacency()
         del adjacency
         gc.collect()
@@ -95,7 +99,7 @@ def test_deterministic_step_keeps_its_adjacency_after_eviction(node):
         assert float(eager[0].abs().max()) > 0 and torch.equal(_bits(eager[0]), _bits(eager[1]))
         captured = CapturedStep(step).capture()
         adjacency = rg.vertex_adjacency(tri, V)
-        items = weakref.ref(adjacency.items)
+        items = weakref.ref(adjacency.csr.items)
         _evict_adjacency()
         del adjacency
         gc.collect()

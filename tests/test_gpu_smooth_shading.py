@@ -3,6 +3,7 @@ restatement of tests/smooth_shading_scenes.py within max(8 E32, 16 2^-24 max|ref
 restatement's own deviation, computed here), needles through the fixed trees, bit identities (two runs, batched against
 unbatched, shared against expanded, eager against a captured step), the kernels that run, the chain into a render, and
 mesh_cython.fit_illumination against the reference's outputs."""
+import ctypes
 import functools
 import math
 
@@ -132,17 +133,17 @@ def _raw(B, nan_fill):
     A = ss.vertex_adjacency(faces, x.shape[1])
     V, L = x.shape[1], _lib.lib()
     new = lambda *shape: torch.full(shape, nan_fill, dtype=torch.float32, device="cuda")       # noqa: E731
-    n = int(L.d3m_smooth_shade_scratch_floats(B, B, V, A.num_faces, A.chunks.shape[0]))
+    n = int(L.d3m_smooth_shade_scratch_floats(B, B, V, A.num_faces, A.csr.num_chunks))
     out = dict(shaded=new(B, V, 3), normals=new(B, V, 3), lengths=new(B, V), g_x=new(B, V, 3), g_colors=new(B, V, 3),
                g_sh=new(B, 3, 9))
     scratch = new(n)
-    _lib.check(L.d3m_smooth_shade_forward(_lib.ptr(x), B, _lib.ptr(colors), B, _lib.ptr(sh), B, *ss._adjacency_args(A),
-                                          _lib.ptr(scratch), n, _lib.ptr(out["shaded"]), _lib.ptr(out["normals"]),
+    _lib.check(L.d3m_smooth_shade_forward(_lib.ptr(x), B, _lib.ptr(colors), B, _lib.ptr(sh), B, _lib.ptr(A.tri),
+                                          ctypes.byref(A.csr.c), _lib.ptr(scratch), n, _lib.ptr(out["shaded"]), _lib.ptr(out["normals"]),
                                           _lib.ptr(out["lengths"]), B, V, A.num_faces, _lib.stream_ptr()), "forward")
     scratch2 = new(n)
     _lib.check(L.d3m_smooth_shade_backward(_lib.ptr(x), B, _lib.ptr(colors), B, _lib.ptr(sh), B, _lib.ptr(out["normals"]),
-                                           _lib.ptr(out["lengths"]), _lib.ptr(g), _lib.ptr(gn), *ss._adjacency_args(A),
-                                           _lib.ptr(scratch2), n, _lib.ptr(out["g_x"]), _lib.ptr(out["g_colors"]),
+                                           _lib.ptr(out["lengths"]), _lib.ptr(g), _lib.ptr(gn), _lib.ptr(A.tri),
+                                           ctypes.byref(A.csr.c), _lib.ptr(scratch2), n, _lib.ptr(out["g_x"]), _lib.ptr(out["g_colors"]),
                                            _lib.ptr(out["g_sh"]), B, V, A.num_faces, _lib.stream_ptr()), "backward")
     torch.cuda.synchronize()
     return out
@@ -243,7 +244,7 @@ def test_needles_through_the_hub_rows_of_the_vertex_gradient():
     V = v.shape[0]
     x, faces = torch.from_numpy(v)[None].cuda(), torch.from_numpy(f).cuda()
     A = ss.vertex_adjacency(faces, V)
-    assert A.long_rows.cpu().tolist() == sorted(h for h, (c, _) in hubs.items() if c > ss.LONG_ROW)
+    assert A.csr.long_rows.cpu().tolist() == sorted(h for h, (c, _) in hubs.items() if c > ss.LONG_ROW)
     _, normals, lengths = ss.forward(x, None, None, A)
     n, r = normals[0].cpu().numpy(), lengths[0].cpu().numpy()
     e = np.array([0.5, -0.75, 1.25], np.float32)

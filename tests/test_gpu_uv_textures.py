@@ -184,7 +184,7 @@ def hot_pixel_layout():
     uv = _dev(_random_layout(rng, F))
     T = uv_transpose(uv, ts, H, W, "REPEAT", True)
     g = rng.standard_normal((B, F * ts ** 3, 3)).astype(np.float32)
-    entries = T.entries.cpu().numpy()
+    entries = T.csr.items.cpu().numpy()
     weight = np.ascontiguousarray(entries[:, 1]).view(np.float32)
     terms = weight[:, None, None] * g[:, entries[:, 0], :].transpose(1, 0, 2)          # [nnz, B, 3]
     return dict(T=T, uv=uv, g=g, terms=terms.reshape(-1, B * 3), B=B, H=H, W=W)
@@ -198,11 +198,11 @@ def test_adjoint_has_the_bits_of_the_shared_order(hot_pixel_layout, lanes):
     from row_gather_replay import replay_gather
     c = hot_pixel_layout
     T, B, H, W = c["T"], c["B"], c["H"], c["W"]
-    row_ptr = T.row_ptr.cpu().numpy()
-    assert int(row_ptr[1] - row_ptr[0]) > 2 * uv_textures.CHUNK and int(T.long_chunk_ptr[1]) >= 3
+    row_ptr = T.csr.offsets.cpu().numpy()
+    assert int(row_ptr[1] - row_ptr[0]) > 2 * uv_textures.CHUNK and int(T.csr.long_chunk_ptr[1]) >= 3
     got = uv_textures.uv_texture_adjoint(T._replace(lanes_per_row=lanes), _dev(c["g"]).reshape(B, -1))
-    want = replay_gather(c["terms"], row_ptr, T.chunks.cpu().numpy(), T.long_rows.cpu().numpy(),
-                         T.long_chunk_ptr.cpu().numpy(), uv_textures.LONG_ROW, lanes_per_row=lanes)
+    want = replay_gather(c["terms"], row_ptr, T.csr.chunks.cpu().numpy(), T.csr.long_rows.cpu().numpy(),
+                         T.csr.long_chunk_ptr.cpu().numpy(), uv_textures.LONG_ROW, lanes_per_row=lanes)
     want = torch.from_numpy(np.ascontiguousarray(want.reshape(H, W, B, 3).transpose(2, 0, 1, 3)))
     assert torch.equal(_bits(got).cpu(), _bits(want))
 

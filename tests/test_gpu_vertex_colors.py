@@ -2,6 +2,7 @@
 get_textures_from_im on a grid mesh and against the element-wise restatement on an irregular mesh with hubs, the fixed-order
 adjoint against float64 within the derived bound (tests/test_vertex_colors_host.py: adjoint_bound), determinism, the chain
 through a render, graph capture, and MultiViewFit(vertex_colors=...) on one rank and on two."""
+import ctypes
 import os
 import socket
 import subprocess
@@ -91,11 +92,10 @@ def test_irregular_mesh_forward_and_adjoint(irregular, batch, dtype):
     # the C entry point, raw, on a NaN-filled output: every element is written, the unused vertex gets an exact 0
     A = vc.vertex_adjacency(faces, V)
     raw = torch.full((batch, V, 3), float("nan"), device="cuda")
-    partials = torch.full((batch, A.chunks.shape[0], 3), float("nan"), device="cuda")
+    partials = torch.full((batch, A.csr.num_chunks, 3), float("nan"), device="cuda")
     _lib.check(_lib.lib().d3m_vertex_color_textures_backward(
-        _lib.ptr(g_int), _lib.ptr(A.offsets), _lib.ptr(A.items), _lib.ptr(A.chunks), A.chunks.shape[0],
-        _lib.ptr(A.long_rows), _lib.ptr(A.long_chunk_ptr), A.long_rows.shape[0], vc.LONG_ROW, _lib.ptr(partials),
-        _lib.ptr(raw), batch, V, faces.shape[0], _lib.stream_ptr()), "d3m_vertex_color_textures_backward")
+        _lib.ptr(g_int), ctypes.byref(A.csr.c), _lib.ptr(partials), _lib.ptr(raw), batch, V, faces.shape[0],
+        _lib.stream_ptr()), "d3m_vertex_color_textures_backward")
     assert torch.equal(_bits(raw), _bits(got_int))
     unused = raw[:, notes["unused"]]
     assert torch.equal(_bits(unused), torch.zeros_like(_bits(unused)))
@@ -113,18 +113,18 @@ def test_adjoint_has_the_bits_of_the_shared_order(irregular):
     V, B = c["V"], 3
     A = vc.vertex_adjacency(c["faces"].cuda(), V)
     got = vc.vertex_color_adjoint(A, c["g"].cuda())
-    counts = (A.offsets[1:] - A.offsets[:-1]).cpu()
+    counts = (A.csr.offsets[1:] - A.csr.offsets[:-1]).cpu()
     assert {int(counts[h]) for h in c["notes"]["hubs"]} == {vc.LONG_ROW, vc.LONG_ROW + 1, 2 * vc.CHUNK + 1}
-    assert A.long_rows.shape[0] == 2 and A.chunks.shape[0] == 4
-    items = A.items.cpu().numpy()
+    assert A.csr.long_rows.shape[0] == 2 and A.csr.chunks.shape[0] == 4
+    items = A.csr.items.cpu().numpy()
     f, corner = items // 3, items % 3
     C = np.array(_CUBE, np.float32)
     g = c["g"].numpy().reshape(B, -1, 8, 3)
     t = np.zeros((items.shape[0], B, 3), np.float32)
     for idx in range(8):
         t = t + C[idx, corner][:, None, None] * g[:, f, idx, :].transpose(1, 0, 2)
-    want = replay_gather(t.reshape(-1, B * 3), A.offsets.cpu().numpy(), A.chunks.cpu().numpy(), A.long_rows.cpu().numpy(),
-                         A.long_chunk_ptr.cpu().numpy(), vc.LONG_ROW)
+    want = replay_gather(t.reshape(-1, B * 3), A.csr.offsets.cpu().numpy(), A.csr.chunks.cpu().numpy(), A.csr.long_rows.cpu().numpy(),
+                         A.csr.long_chunk_ptr.cpu().numpy(), vc.LONG_ROW)
     want = torch.from_numpy(np.ascontiguousarray(want.reshape(V, B, 3).transpose(1, 0, 2)))
     assert torch.equal(_bits(got).cpu(), _bits(want))
 

@@ -216,20 +216,20 @@ def test_topology_equals_the_loop_built_one(mesh, dtype):
     T = build_topology(faces.to(dtype), V)
     E, P = edges.shape[0], wings.shape[0]
     assert (T.num_vertices, T.num_edges, T.num_wings) == (V, E, P) == (V, 18705, 18569)
-    for name in T._fields[:12]:
-        assert getattr(T, name).dtype == torch.int32, name
+    for t in (T.edges, T.wings, *T.nbr[:5], *T.wing[:5]):
+        assert t.dtype == torch.int32
     assert torch.equal(T.edges.long(), edges) and torch.equal(T.wings.long(), wings)
     # the neighbour CSR: both directions of every edge, rows ascending
     both = torch.cat([edges, edges.flip(1)])
     both = both[torch.argsort(both[:, 0] * V + both[:, 1])]
     counts = torch.bincount(both[:, 0], minlength=V)
-    off = T.nbr_offsets.long()
+    off = T.nbr.offsets.long()
     assert off.shape == (V + 1,) and int(off[0]) == 0 and torch.equal(off[1:] - off[:-1], counts)
-    assert torch.equal(T.nbr_items.long(), both[:, 1])
+    assert torch.equal(T.nbr.items.long(), both[:, 1])
     same_row = both[1:, 0] == both[:-1, 0]
     assert bool((both[1:, 1] > both[:-1, 1])[same_row].all())
     # the wing CSR: items 4 p + role of the row's vertex, ascending per row, every item once
-    woff, items = T.wing_offsets.long(), T.wing_items.long()
+    woff, items = T.wing.offsets.long(), T.wing.items.long()
     wcounts = woff[1:] - woff[:-1]
     row_of = torch.repeat_interleave(torch.arange(V), wcounts)
     assert items.shape == (4 * P,) and torch.equal(wings.reshape(-1)[items], row_of)
@@ -240,16 +240,16 @@ def test_topology_equals_the_loop_built_one(mesh, dtype):
     at_limit, above = notes["fan_at_limit"], notes["fan_above_limit"]
     assert int(counts[north]) == int(counts[south]) == 2 * CHUNK + 1
     assert int(counts[at_limit]) == LONG_ROW and int(counts[above]) == LONG_ROW + 1
-    assert T.nbr_long_rows.tolist() == [north, south, above] and T.nbr_long_chunk_ptr.tolist() == [0, 3, 6, 7]
-    ch = T.nbr_chunks.tolist()
+    assert T.nbr.long_rows.tolist() == [north, south, above] and T.nbr.long_chunk_ptr.tolist() == [0, 3, 6, 7]
+    ch = T.nbr.chunks.tolist()
     assert ch[:3] == [[0, CHUNK], [CHUNK, 2 * CHUNK], [2 * CHUNK, 2 * CHUNK + 1]]
     assert ch[3][0] == int(off[south]) and ch[5] == [int(off[south]) + 2 * CHUNK, int(off[south + 1])]
     assert ch[6] == [int(off[above]), int(off[above + 1])]
     # (a pole's wing row: an endpoint of 2 CHUNK + 1 spokes, the third vertex across 2 CHUNK + 1 ring edges)
     assert int(wcounts[north]) == int(wcounts[south]) == 2 * (2 * CHUNK + 1)
     assert int(wcounts[at_limit]) == LONG_ROW - 2 and int(wcounts[above]) == LONG_ROW - 1
-    assert T.wing_long_rows.tolist() == [north, south] and T.wing_long_chunk_ptr.tolist() == [0, 5, 10]
-    wch = T.wing_chunks.tolist()
+    assert T.wing.long_rows.tolist() == [north, south] and T.wing.long_chunk_ptr.tolist() == [0, 5, 10]
+    wch = T.wing.chunks.tolist()
     assert wch[0] == [0, CHUNK] and wch[4] == [4 * CHUNK, 4 * CHUNK + 2] and wch[9][1] == int(woff[south + 1])
     # the isolated vertex: empty rows
     iso = notes["isolated"]
@@ -262,16 +262,16 @@ def test_topology_equals_the_loop_built_one(mesh, dtype):
     assert int((ab == shared).all(1).sum()) == 3
     doubled = torch.tensor(notes["doubled"])
     assert int((edges == doubled).all(1).sum()) == 1 and not bool((ab == doubled).all(1).any())
-    assert int(counts[doubled[0]]) == 1 and T.nbr_items[off[doubled[0]]] == doubled[1]
+    assert int(counts[doubled[0]]) == 1 and T.nbr.items[off[doubled[0]]] == doubled[1]
 
 
 def test_topology_errors_and_small_cases():
     from deep3dmap_amd.neural_renderer.mesh_regularizers import MAX_FACES_PER_EDGE, build_topology
     T = build_topology(torch.tensor([[0, 1, 2], [2, 1, 3]]), 5)
     assert T.edges.tolist() == [[0, 1], [0, 2], [1, 2], [1, 3], [2, 3]] and T.wings.tolist() == [[1, 2, 0, 3]]
-    assert T.nbr_offsets.tolist() == [0, 2, 5, 8, 10, 10] and T.nbr_items.tolist() == [1, 2, 0, 2, 3, 0, 1, 3, 1, 2]
-    assert T.wing_offsets.tolist() == [0, 1, 2, 3, 4, 4] and T.wing_items.tolist() == [2, 0, 1, 3]
-    assert T.nbr_chunks.shape == (0, 2) and T.wing_long_rows.numel() == 0 and T.wing_long_chunk_ptr.tolist() == [0]
+    assert T.nbr.offsets.tolist() == [0, 2, 5, 8, 10, 10] and T.nbr.items.tolist() == [1, 2, 0, 2, 3, 0, 1, 3, 1, 2]
+    assert T.wing.offsets.tolist() == [0, 1, 2, 3, 4, 4] and T.wing.items.tolist() == [2, 0, 1, 3]
+    assert T.nbr.chunks.shape == (0, 2) and T.wing.long_rows.numel() == 0 and T.wing.long_chunk_ptr.tolist() == [0]
     only_doubled = build_topology(torch.tensor([[1, 1, 1], [0, 0, 2]]), 3)
     assert only_doubled.edges.tolist() == [[0, 2]] and only_doubled.num_wings == 0 and only_doubled.wings.shape == (0, 4)
     with pytest.raises(ValueError, match="indices"):
@@ -321,34 +321,39 @@ def test_entry_points_return_invalid_before_any_launch():
     p = 256                                                 # never dereferenced: every call below returns before a launch
     INVALID = 1
     assert L.d3m_error_string(INVALID) == b"invalid argument"
-    names = [n for n, _ in _lib.D3MMeshTopology._fields_]
-    ok_topo = dict(zip(names, [p, p, p, p, p, None, None, None, None, None, None, 8, 12, 10, 0, 0, 0, 0, 64]))
+    csr = dict(offsets=p, items=p, chunks=None, long_rows=None, long_chunk_ptr=None, num_rows=8, num_chunks=0, num_long_rows=0,
+               long_row=64)
 
-    def topo(**change):
-        return _lib.D3MMeshTopology(**dict(ok_topo, **change))
+    def topo(nbr={}, wing={}, both={}, **change):
+        return _lib.D3MMeshTopology(**dict(dict(nbr=_lib.D3MCsr(**dict(csr, **both, **nbr)),
+                                                wing=_lib.D3MCsr(**dict(csr, **both, **wing)), wings=p, num_edges=12, num_wings=10),
+                                           **change))
     need = L.d3m_mesh_regularizer_scratch_floats
     assert need(1, ctypes.byref(topo())) == 8 * 4 + 1 and need(3, ctypes.byref(topo())) == 3 * (8 * 4 + 1)
-    assert need(2, ctypes.byref(topo(num_nbr_chunks=2, num_nbr_long_rows=1, num_wing_chunks=1, num_wing_long_rows=1))) == \
+    assert need(2, ctypes.byref(topo(nbr=dict(num_chunks=2, num_long_rows=1), wing=dict(num_chunks=1, num_long_rows=1)))) == \
         2 * (8 * 4 + 3 * 4 + 2 * 3 + 1)
-    for b, change in ((0, {}), (65536, {}), (1, dict(num_vertices=0)), (1, dict(num_edges=-1)), (1, dict(long_row=-1))):
-        assert need(b, ctypes.byref(topo(**change))) == 0
+    for b, t in ((0, topo()), (65536, topo()), (1, topo(both=dict(num_rows=0))), (1, topo(num_edges=-1)),
+                 (1, topo(both=dict(long_row=-1)))):
+        assert need(b, ctypes.byref(t)) == 0
     assert need(1, None) == 0
     ok = dict(x=p, batch=1, topo=topo(), lap=1.0, edge=1.0, target=0.5, normal=1.0, scratch=p, floats=1 << 20, scale=None,
               loss=p, grad=p, accumulate=0)
-    chunked = dict(num_nbr_chunks=1, num_nbr_long_rows=1, nbr_chunks=p, nbr_long_rows=p, nbr_long_chunk_ptr=p)
+    chunked = dict(num_chunks=1, num_long_rows=1, chunks=p, long_rows=p, long_chunk_ptr=p)
     bad = [dict(x=None), dict(topo=None), dict(scratch=None), dict(loss=None), dict(batch=0), dict(batch=65536),
            dict(lap=-1.0), dict(edge=-1.0), dict(target=-0.1), dict(normal=-1.0), dict(lap=float("nan")),
            dict(floats=8 * 4), dict(scratch=260),                       # too small; not 16-byte aligned
-           dict(topo=topo(num_vertices=0)), dict(topo=topo(num_vertices=-4)), dict(topo=topo(num_edges=-1)),
+           dict(topo=topo(both=dict(num_rows=0))), dict(topo=topo(both=dict(num_rows=-4))), dict(topo=topo(num_edges=-1)),
            dict(topo=topo(num_wings=-1)), dict(topo=topo(num_edges=1 << 30)), dict(topo=topo(num_wings=1 << 29)),
-           dict(topo=topo(long_row=-1)), dict(topo=topo(nbr_offsets=None)), dict(topo=topo(nbr_items=None)),
-           dict(topo=topo(wings=None)), dict(topo=topo(wing_offsets=None)), dict(topo=topo(wing_items=None)),
-           dict(topo=topo(num_nbr_long_rows=1, nbr_long_rows=p, nbr_long_chunk_ptr=p)),       # long rows without chunks
-           dict(topo=topo(num_wing_long_rows=1, wing_long_rows=p, wing_long_chunk_ptr=p)),
-           dict(topo=topo(**dict(chunked, nbr_chunks=None))),                                  # chunks without their ranges
-           dict(topo=topo(**dict(chunked, nbr_long_rows=None))),
-           dict(topo=topo(**chunked), floats=8 * 4 + 1),                                       # chunks without partials
-           dict(topo=topo(num_wing_chunks=1, wing_chunks=p))]                                  # chunks without long rows
+           dict(topo=topo(both=dict(long_row=-1))), dict(topo=topo(nbr=dict(offsets=None))), dict(topo=topo(nbr=dict(items=None))),
+           dict(topo=topo(wings=None)), dict(topo=topo(wing=dict(offsets=None))), dict(topo=topo(wing=dict(items=None))),
+           dict(topo=topo(nbr=dict(num_long_rows=1, long_rows=p, long_chunk_ptr=p))),         # long rows without chunks
+           dict(topo=topo(wing=dict(num_long_rows=1, long_rows=p, long_chunk_ptr=p))),
+           dict(topo=topo(nbr=dict(chunked, chunks=None))),                                    # chunks without their ranges
+           dict(topo=topo(nbr=dict(chunked, long_rows=None))),
+           dict(topo=topo(nbr=chunked), floats=8 * 4 + 1),                                     # chunks without partials
+           dict(topo=topo(wing=dict(num_chunks=1, chunks=p))),                                 # chunks without long rows
+           dict(topo=topo(wing=dict(num_rows=7))), dict(topo=topo(wing=dict(num_rows=9))),     # not the V rows of nbr
+           dict(topo=topo(nbr=dict(long_row=-1))), dict(topo=topo(wing=dict(long_row=-1)))]
     for change in bad:
         a = dict(ok, **change)
         topo_arg = None if a["topo"] is None else ctypes.byref(a["topo"])

@@ -147,7 +147,7 @@ def test_the_adjacency_is_reused(monkeypatch):
     first, batched = ss._checked(x, faces, x, torch.rand(3, 9), cache)
     again, _ = ss._checked(x[None], faces, x, torch.rand(2, 3, 9), cache)
     assert first is again and built == [1] and not batched
-    assert first.offsets.tolist() == [0, 1, 3, 5, 6] and (first.num_vertices, first.num_faces) == (4, 2)
+    assert first.csr.offsets.tolist() == [0, 1, 3, 5, 6] and (first.num_vertices, first.num_faces) == (4, 2)
     other, _ = ss._checked(x, faces.clone(), None, None, cache)
     assert other is not first and built == [1, 1]
     with pytest.raises(ValueError, match="indices"):
@@ -170,24 +170,32 @@ def test_entry_points_return_invalid_before_any_launch():
                  (1, 1, 4, 2 ** 30, 0), (4, 4, 2 ** 28, 2, 0)):
         assert L.d3m_smooth_shade_scratch_floats(*args) == 0, args
     big = 1 << 20
-    fwd_ok = dict(x=p, vb=1, col=p, cb=1, sh=p, sb=1, tri=p, off=p, items=p, chunks=None, n_chunks=0, long_rows=None, lcp=None,
-                  n_long=0, long_row=64, scratch=p, floats=big, shaded=p, normals=p, lengths=p, B=1, V=4, F=2)
-    common = [dict(x=None), dict(tri=None), dict(off=None), dict(items=None), dict(scratch=None), dict(B=0), dict(B=65536),
+    q = 256                                                 # the same address as a field of the d3m_csr
+    csr = dict(offsets=q, items=q, chunks=None, long_rows=None, long_chunk_ptr=None, num_rows=4, num_chunks=0, num_long_rows=0,
+               long_row=64)
+
+    def refused(entry, ok, change):
+        assert set(change) <= set(ok) | set(csr), change
+        a = dict(ok, **{k: v for k, v in change.items() if k in ok})
+        if a["csr"]:
+            a["csr"] = ctypes.byref(_lib.D3MCsr(**dict(csr, **{k: v for k, v in change.items() if k in csr})))
+        return entry(*a.values(), None) == INVALID
+    fwd_ok = dict(x=p, vb=1, col=p, cb=1, sh=p, sb=1, tri=p, csr=True, scratch=p, floats=big, shaded=p, normals=p, lengths=p,
+                  B=1, V=4, F=2)
+    common = [dict(x=None), dict(tri=None), dict(offsets=None), dict(items=None), dict(scratch=None), dict(B=0), dict(B=65536),
               dict(V=0), dict(F=0), dict(F=-3), dict(F=2 ** 30), dict(vb=2), dict(cb=2), dict(sb=2), dict(vb=0),
-              dict(B=3, vb=3, cb=2), dict(long_row=-1), dict(n_chunks=-1), dict(n_long=-1),
-              dict(n_long=1, long_rows=p, lcp=p),          # long rows without chunks
-              dict(n_chunks=1, chunks=p),                  # chunks without their rows
-              dict(floats=5), dict(x=ctypes.c_void_p(258)), dict(col=p, sh=None)]
+              dict(B=3, vb=3, cb=2), dict(long_row=-1), dict(num_chunks=-1), dict(num_long_rows=-1),
+              dict(num_long_rows=1, long_rows=q, long_chunk_ptr=q),    # long rows without chunks
+              dict(num_chunks=1, chunks=q),                            # chunks without their rows
+              dict(floats=5), dict(x=ctypes.c_void_p(258)), dict(col=p, sh=None),
+              dict(csr=None), dict(num_rows=5), dict(num_rows=3)]      # no d3m_csr; not the V rows the entry point walks
     fwd_bad = common + [dict(normals=None), dict(lengths=None), dict(shaded=None), dict(col=None, sh=None),
                         dict(col=None, sh=None, shaded=None, B=2, vb=1)]
     for change in fwd_bad:
-        a = dict(fwd_ok, **change)
-        assert L.d3m_smooth_shade_forward(*a.values(), None) == INVALID, change
-    bwd_ok = dict(x=p, vb=1, col=p, cb=1, sh=p, sb=1, normals=p, lengths=p, g=p, gn=None, tri=p, off=p, items=p, chunks=None,
-                  n_chunks=0, long_rows=None, lcp=None, n_long=0, long_row=64, scratch=p, floats=big, gx=p, gc=p, gsh=p, B=1,
-                  V=4, F=2)
+        assert refused(L.d3m_smooth_shade_forward, fwd_ok, change), change
+    bwd_ok = dict(x=p, vb=1, col=p, cb=1, sh=p, sb=1, normals=p, lengths=p, g=p, gn=None, tri=p, csr=True, scratch=p, floats=big,
+                  gx=p, gc=p, gsh=p, B=1, V=4, F=2)
     bwd_bad = common + [dict(normals=None), dict(lengths=None), dict(gx=None, gc=None, gsh=None), dict(g=None, gn=p),
                         dict(g=None, gn=p, gx=p, gc=None, gsh=p), dict(col=None, sh=None, gc=None, gsh=None)]
     for change in bwd_bad:
-        a = dict(bwd_ok, **change)
-        assert L.d3m_smooth_shade_backward(*a.values(), None) == INVALID, change
+        assert refused(L.d3m_smooth_shade_backward, bwd_ok, change), change

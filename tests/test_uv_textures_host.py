@@ -220,3 +220,30 @@ def test_faces_uv_gradient_raises():
 
 
 # (the transpose cache: tests/test_built_cache_host.py, once for every cache of the package)
+
+
+# ---- the C entry point refuses bad arguments before any launch -----------------------------------------------------------
+def test_adjoint_entry_point_returns_invalid_before_any_launch():
+    import ctypes
+    from deep3dmap_amd import _lib
+    L = _lib.lib()
+    p, q = ctypes.c_void_p(256), 256                        # never dereferenced: every call below returns before a launch
+    INVALID = 1
+    csr = dict(offsets=q, items=q, chunks=None, long_rows=None, long_chunk_ptr=None, num_rows=6, num_chunks=0, num_long_rows=0,
+               long_row=64)
+    ok = dict(csr=True, lanes=4, g=p, partials=None, out=p, batch=1, texels=32, H=2, W=3)
+    chunked = dict(num_chunks=1, num_long_rows=1, chunks=q, long_rows=q, long_chunk_ptr=q, partials=p)
+    bad = [dict(g=None), dict(out=None), dict(offsets=None), dict(batch=0), dict(batch=65536), dict(texels=0), dict(H=0),
+           dict(W=-1), dict(H=1 << 16, W=1 << 15), dict(lanes=0), dict(lanes=3), dict(lanes=32), dict(long_row=-1),
+           dict(num_chunks=-1), dict(num_long_rows=-1),
+           dict(num_long_rows=1, long_rows=q, long_chunk_ptr=q),        # long rows without chunks
+           dict(num_chunks=1, chunks=q, partials=p),                    # chunks without long rows
+           dict(chunked, items=None), dict(chunked, partials=None),     # chunks without entries or partials
+           dict(chunked, chunks=None), dict(chunked, long_rows=None), dict(chunked, long_chunk_ptr=None),
+           dict(csr=None), dict(num_rows=7), dict(num_rows=5)]          # no d3m_csr; not the H * W rows the entry point walks
+    for change in bad:
+        assert set(change) <= set(ok) | set(csr), change
+        a = dict(ok, **{k: v for k, v in change.items() if k in ok})
+        if a["csr"]:
+            a["csr"] = ctypes.byref(_lib.D3MCsr(**dict(csr, **{k: v for k, v in change.items() if k in csr})))
+        assert L.d3m_uv_texture_adjoint(*a.values(), None) == INVALID, change

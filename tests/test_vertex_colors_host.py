@@ -118,8 +118,8 @@ def test_adjacency_rows(dtype):
     faces, V, notes = irregular_mesh()
     A = build_adjacency(faces.to(dtype), V)
     F = faces.shape[0]
-    off, items = A.offsets.long(), A.items.long()
-    assert A.offsets.dtype == A.items.dtype == A.tri.dtype == torch.int32
+    off, items = A.csr.offsets.long(), A.csr.items.long()
+    assert A.csr.offsets.dtype == A.csr.items.dtype == A.tri.dtype == torch.int32
     assert off.shape == (V + 1,) and items.shape == (3 * F,) and int(off[0]) == 0 and int(off[-1]) == 3 * F
     assert torch.equal(A.tri.long(), faces) and (A.num_vertices, A.num_faces) == (V, F)
     flat = faces.reshape(-1)
@@ -136,9 +136,9 @@ def test_adjacency_rows(dtype):
     counts = (off[1:] - off[:-1])
     for hub, n in notes["hubs"].items():
         assert int(counts[hub]) == n
-    assert A.long_rows.tolist() == [0, 2] and A.long_chunk_ptr.tolist() == [0, 3, 4]
-    assert int(counts[1]) == LONG_ROW and 1 not in A.long_rows.tolist()
-    ch = A.chunks.tolist()
+    assert A.csr.long_rows.tolist() == [0, 2] and A.csr.long_chunk_ptr.tolist() == [0, 3, 4]
+    assert int(counts[1]) == LONG_ROW and 1 not in A.csr.long_rows.tolist()
+    ch = A.csr.chunks.tolist()
     assert ch[:3] == [[0, CHUNK], [CHUNK, 2 * CHUNK], [2 * CHUNK, 2 * CHUNK + 1]]
     assert ch[3] == [int(off[2]), int(off[3])]
 
@@ -146,8 +146,8 @@ def test_adjacency_rows(dtype):
 def test_adjacency_without_long_rows_and_index_errors():
     from deep3dmap_amd.neural_renderer.vertex_colors import build_adjacency
     A = build_adjacency(torch.tensor([[0, 1, 2], [2, 1, 3]]), 5)
-    assert A.offsets.tolist() == [0, 1, 3, 5, 6, 6] and A.items.tolist() == [0, 1, 4, 2, 3, 5]
-    assert A.chunks.shape == (0, 2) and A.long_rows.numel() == 0 and A.long_chunk_ptr.tolist() == [0]
+    assert A.csr.offsets.tolist() == [0, 1, 3, 5, 6, 6] and A.csr.items.tolist() == [0, 1, 4, 2, 3, 5]
+    assert A.csr.chunks.shape == (0, 2) and A.csr.long_rows.numel() == 0 and A.csr.long_chunk_ptr.tolist() == [0]
     with pytest.raises(ValueError, match="indices"):
         build_adjacency(torch.tensor([[0, 1, 5]]), 5)
     with pytest.raises(ValueError, match="indices"):
@@ -215,14 +215,20 @@ def test_entry_points_return_invalid_before_any_launch():
                  (p, 65536, p, p, 4, 2), (p, 1, p, p, 0, 2), (p, 1, p, p, 4, 0), (p, 1, p, p, 4, -1)):
         assert fwd(*args, None) == INVALID, args
     bwd = L.d3m_vertex_color_textures_backward
-    ok = dict(g=p, off=p, items=p, chunks=None, n_chunks=0, long_rows=None, lcp=None, n_long=0, long_row=64, partials=None,
-              out=p, batch=1, V=4, F=2)
-    bad = [dict(g=None), dict(off=None), dict(items=None), dict(out=None), dict(batch=0), dict(batch=65536), dict(V=0),
-           dict(F=0), dict(F=-3), dict(long_row=-1), dict(n_chunks=-1), dict(n_long=-1),
-           dict(n_long=1, long_rows=p, lcp=p),              # long rows without chunks
-           dict(n_chunks=1, chunks=p),                      # chunks without partials
-           dict(n_chunks=1, partials=p),                    # ... or without their ranges
-           dict(n_long=1, n_chunks=1, chunks=p, partials=p), dict(F=2 ** 30)]
+    q = 256                                                 # the same address as a field of the d3m_csr
+    csr = dict(offsets=q, items=q, chunks=None, long_rows=None, long_chunk_ptr=None, num_rows=4, num_chunks=0, num_long_rows=0,
+               long_row=64)
+    ok = dict(g=p, csr=True, partials=None, out=p, batch=1, V=4, F=2)
+    bad = [dict(g=None), dict(offsets=None), dict(items=None), dict(out=None), dict(batch=0), dict(batch=65536), dict(V=0),
+           dict(F=0), dict(F=-3), dict(long_row=-1), dict(num_chunks=-1), dict(num_long_rows=-1),
+           dict(num_long_rows=1, long_rows=q, long_chunk_ptr=q),        # long rows without chunks
+           dict(num_chunks=1, chunks=q),                                # chunks without partials
+           dict(num_chunks=1, partials=p),                              # ... or without their ranges
+           dict(num_long_rows=1, num_chunks=1, chunks=q, partials=p), dict(F=2 ** 30),
+           dict(csr=None), dict(num_rows=5), dict(num_rows=3)]          # no d3m_csr; not the V rows the entry point walks
     for change in bad:
-        a = dict(ok, **change)
+        assert set(change) <= set(ok) | set(csr), change
+        a = dict(ok, **{k: v for k, v in change.items() if k in ok})
+        if a["csr"]:
+            a["csr"] = ctypes.byref(_lib.D3MCsr(**dict(csr, **{k: v for k, v in change.items() if k in csr})))
         assert bwd(*a.values(), None) == INVALID, change

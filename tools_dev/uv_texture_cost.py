@@ -76,13 +76,13 @@ def kernels(uv, reps):
                 adj = median_ms(lambda: uv_textures.uv_texture_adjoint(T, g), reps)
                 sweep = {str(L): median_ms(lambda: uv_textures.uv_texture_adjoint(T._replace(lanes_per_row=L), g), reps)
                          for L in (1, 2, 4, 8, 16)}
-                nnz = int(T.entries.shape[0])
-                csr_bytes = 4 * (T.row_ptr.numel() + T.entries.numel())
+                nnz = int(T.csr.items.shape[0])
+                csr_bytes = 4 * (T.csr.offsets.numel() + T.csr.items.numel())
                 out.append({"ts": ts, "image": size, "bilinear": bilinear, "forward_ms": fwd, "adjoint_ms": adj,
                             "build_ms": sorted(builds)[1], "entries": nnz, "csr_bytes": csr_bytes,
-                            "long_rows": int(T.long_rows.numel()), "chunks": int(T.chunks.shape[0]),
+                            "long_rows": int(T.csr.num_long_rows), "chunks": int(T.csr.num_chunks),
                             "lanes_per_row": T.lanes_per_row, "adjoint_ms_by_lanes": sweep,
-                            "mean_row": nnz / max(1, int((T.row_ptr[1:] > T.row_ptr[:-1]).sum())),
+                            "mean_row": nnz / max(1, int((T.csr.offsets[1:] > T.csr.offsets[:-1]).sum())),
                             "adjoint_bytes_model": csr_bytes + 4 * g.numel() + 12 * size * size})
                 del T
     return out

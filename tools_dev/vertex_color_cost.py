@@ -68,8 +68,8 @@ def kernels(reps, n=225):
                 times[f"{name}_adjoint_ms"].append(t_a)
     res = {k: median(x) for k, x in times.items()}
     same = torch.equal(forms["hip"]().detach(), forms["eager"]().detach())
-    res.update(vertices=V, faces=F, adjacency_build_ms=median(builds), long_rows=int(A.long_rows.numel()),
-               max_valence=int((A.offsets[1:] - A.offsets[:-1]).max()), forward_equals_eager_bitwise=bool(same),
+    res.update(vertices=V, faces=F, adjacency_build_ms=median(builds), long_rows=int(A.csr.num_long_rows),
+               max_valence=int((A.csr.offsets[1:] - A.csr.offsets[:-1]).max()), forward_equals_eager_bitwise=bool(same),
                timing="events around each call (eager launch, host time included), forms alternating, median")
     return res
 
