@@ -45,6 +45,13 @@ class D3MCsr(ctypes.Structure):
                 [(n, _I) for n in ("num_rows", "num_chunks", "num_long_rows", "long_row")])
 
 
+class D3MFragments(ctypes.Structure):
+    """d3m_fragments (include/d3m_raster.h): a coverage record as the attribute-image entry points read it."""
+    _fields_ = ([(n, _P) for n in ("face_index_map", "weight_map", "depth_map", "faces", "tri", "visibility")] +
+                [("visibility_size", _SZ)] +
+                [(n, _I) for n in ("batch_size", "num_tri", "fill_back", "image_size", "anti_aliasing")])
+
+
 class D3MMeshTopology(ctypes.Structure):
     """d3m_mesh_topology (include/d3m_raster.h): the neighbour CSR, the wing CSR and the wing records of a faces tensor."""
     _fields_ = [("nbr", D3MCsr), ("wing", D3MCsr), ("wings", _P), ("num_edges", _I), ("num_wings", _I)]
@@ -205,6 +212,10 @@ _SIGNATURES = {
     "d3m_uv_texture_adjoint": (_I, [ctypes.POINTER(D3MCsr), _I, _P, _P, _P, _I, _L, _I, _I, _P]),
     "d3m_vertex_color_textures": (_I, [_P, _I, _P, _P, _I, _I, _P]),
     "d3m_vertex_color_textures_backward": (_I, [_P, ctypes.POINTER(D3MCsr), _P, _P, _I, _I, _I, _P]),
+    "d3m_vertex_attribute_images": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _I, _I, _P, _P, _P, _P]),
+    "d3m_vertex_attribute_scratch_floats": (_SZ, [_I, _I, _I, ctypes.POINTER(D3MCsr)]),
+    "d3m_vertex_attribute_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, ctypes.POINTER(D3MCsr), _P, _SZ, _P, _I, _I,
+                                                  _I, _P]),
     "d3m_mesh_regularizer_scratch_floats": (_SZ, [_I, ctypes.POINTER(D3MMeshTopology)]),
     "d3m_mesh_regularizer": (_I, [_P, _I, ctypes.POINTER(D3MMeshTopology), _F, _F, _F, _F, _P, _SZ, _P, _P, _P, _I, _P]),
     "d3m_morphable_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -14,6 +14,7 @@
 #include "d3m_morphable.h"
 #include "d3m_pose.h"
 #include "d3m_smooth_shade.h"
+#include "d3m_attributes.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -2518,6 +2519,77 @@ D3M_EXPORT int d3m_smooth_shade_backward(const float* vertices, int vertices_bat
         LAUNCH("k_smooth_shade_backward_rows", k_smooth_shade_backward_rows, dim3(blocks_for((long)V * 3, SS_BLOCK), vb),
                dim3(SS_BLOCK), st, adj, (const float*)terms, (const float*)partials, grad_vertices, V, F);
     }
+    return check_launch();
+}
+
+// Per-vertex attribute images (d3m_attributes.h): C channels interpolated over a coverage record, and the fixed-order adjoint.
+// What both entry points refuse of the record and the sizes; `m` is the record as the kernels read it.
+static bool fragments_ok(const d3m_fragments* fr, int attributes_batch, int num_vertices, int num_channels, AttrMaps& m) {
+    if (!fr || !fr->face_index_map || !fr->weight_map || !fr->depth_map || !fr->faces || !fr->tri) return false;
+    if (fr->batch_size <= 0 || fr->batch_size > 65535 || fr->num_tri <= 0 || fr->image_size <= 0 || fr->image_size > 16384)
+        return false;
+    const long Fp = (long)(fr->fill_back ? 2 : 1) * fr->num_tri;
+    if (Fp * fr->batch_size > 0x7FFFFFFFl) return false;               // (the visibility list's entries are int32)
+    if (attributes_batch != 1 && attributes_batch != fr->batch_size) return false;
+    if (num_vertices <= 0 || num_channels < 1 || num_channels > VA_MAX_CHANNELS) return false;
+    m = AttrMaps{fr->face_index_map, fr->weight_map, fr->depth_map, fr->faces, fr->tri, fr->batch_size,
+                 fr->image_size * (fr->anti_aliasing ? 2 : 1), fr->num_tri, (int)Fp, fr->anti_aliasing ? 1 : 0};
+    return true;
+}
+
+D3M_EXPORT int d3m_vertex_attribute_images(const d3m_fragments* fragments, const float* attributes, int attributes_batch,
+                                           int num_vertices, int num_channels, const float* background, float* images,
+                                           float* alpha, d3m_stream_t stream) {
+    AttrMaps m;
+    if (!attributes || !images || !alpha) return D3M_ERR_INVALID;
+    if (!fragments_ok(fragments, attributes_batch, num_vertices, num_channels, m)) return D3M_ERR_INVALID;
+    const long n = (long)fragments->image_size * fragments->image_size;
+    LAUNCH("k_vertex_attribute_images", k_vertex_attribute_images, dim3(blocks_for(n, 256), m.B), dim3(256), (hipStream_t)stream,
+           m, attributes, attributes_batch, num_vertices, num_channels, background, images, alpha);
+    return check_launch();
+}
+
+D3M_EXPORT size_t d3m_vertex_attribute_scratch_floats(int batch_size, int num_faces, int num_channels, const d3m_csr* adjacency) {
+    if (batch_size <= 0 || batch_size > 65535 || num_faces <= 0 || num_channels < 1 || num_channels > VA_MAX_CHANNELS ||
+        !adjacency || !csr_counts_ok(*adjacency))
+        return 0;
+    return ((size_t)batch_size * num_faces * 3 + (size_t)batch_size * adjacency->num_chunks) * num_channels;
+}
+
+D3M_EXPORT int d3m_vertex_attribute_images_backward(const d3m_fragments* fragments, const float* grad_images,
+                                                    const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
+                                                    float* grad_attributes, int attributes_batch, int num_vertices,
+                                                    int num_channels, d3m_stream_t stream) {
+    AttrMaps m;
+    if (!grad_images || !scratch || !grad_attributes) return D3M_ERR_INVALID;
+    if (!fragments_ok(fragments, attributes_batch, num_vertices, num_channels, m)) return D3M_ERR_INVALID;
+    if ((long)m.Ft * 3 > 0x7FFFFFFFl) return D3M_ERR_INVALID;          // items are int32
+    const long nf = (long)m.B * m.Fp;
+    if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
+    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if (scratch_floats < d3m_vertex_attribute_scratch_floats(m.B, m.Fp, num_channels, adjacency)) return D3M_ERR_WORKSPACE;
+    const CsrRows adj = csr_rows(*adjacency);
+    const int num_chunks = adj.longs.n_chunks, C = num_channels, c_chunks = (C + VA_CHUNK - 1) / VA_CHUNK;
+    const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
+    float* G = scratch;
+    float* partials = G + (size_t)nf * 3 * C;
+    hipStream_t st = (hipStream_t)stream;
+    // 1. per visible face: fixed grids striding over the visibility list (its length is only known on the device)
+    const unsigned small_blocks = std::min(blocks_for(nf, FM_FACES_PER_BLOCK), 2048u);
+    LAUNCH("k_vertex_attribute_face_sums", k_vertex_attribute_face_sums, dim3(small_blocks, c_chunks), dim3(256), st, m,
+           grad_images, C, (const int*)vis.list, (const int*)vis.count, G);
+    const unsigned large_blocks = std::min(blocks_for(nf, RG_BLOCK), 256u);
+    LAUNCH("k_vertex_attribute_large_face_sums", k_vertex_attribute_large_face_sums, dim3(large_blocks, c_chunks),
+           dim3(RG_BLOCK), st, m, grad_images, C, (const int*)vis.list, (const int*)vis.count, G);
+    // 2. per vertex, over the adjacency
+    if (num_chunks > 0)
+        LAUNCH("k_vertex_attribute_adjoint_chunks", k_vertex_attribute_adjoint_chunks, dim3(num_chunks, m.B, c_chunks),
+               dim3(RG_BLOCK), st, adj.items, adj.longs.chunks, num_chunks, (const float*)G, (const int*)vis.flags, m.Ft,
+               m.Fp, C, partials);
+    const int shared = attributes_batch == 1 ? 1 : 0;
+    LAUNCH("k_vertex_attribute_adjoint_rows", k_vertex_attribute_adjoint_rows,
+           dim3(blocks_for((long)num_vertices * C, 256), shared ? 1 : m.B), dim3(256), st, adj, (const float*)partials,
+           (const float*)G, (const int*)vis.flags, m.B, m.Ft, m.Fp, num_vertices, C, shared, grad_attributes);
     return check_launch();
 }
 

@@ -1,5 +1,6 @@
 """MI355X-native mirror of the `neural_renderer` package surface deep3dmap imports
 (pnpmodules/neural_renderer/neural_renderer/__init__.py:1-12)."""
+from .attributes import Fragments, interpolate_vertex_attributes, rasterize_fragments
 from .cameras import get_points_from_angles, look, look_at, perspective, projection
 from .mesh_ops import lighting, vertices_to_faces
 from .mesh_regularizers import (MeshRegularizer, edge_length_loss, laplacian_loss, mesh_regularizer, mesh_topology,

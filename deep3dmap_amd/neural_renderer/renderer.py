@@ -8,7 +8,7 @@ import numpy
 import torch
 import torch.nn as nn
 
-from . import cameras, mesh_ops
+from . import attributes as _attributes, cameras, mesh_ops
 from .rasterize import (light_on_device, rasterize, rasterize_depth, rasterize_lit, rasterize_lit_fit,
                         rasterize_lit_image_grid, rasterize_mesh_modes, rasterize_rgbad, rasterize_silhouettes)
 
@@ -201,6 +201,21 @@ class Renderer(nn.Module):
         textures = self._lit_textures(vertices, faces, textures)
         return rasterize(f, textures, self.image_size, self.anti_aliasing, self.near, self.far,
                          self.rasterizer_eps, self.background_color)
+
+    def fragments(self, vertices, faces, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
+        """The coverage record (attributes.Fragments) of this renderer's view of the mesh: _transform, then
+        rasterize_fragments with near / far / fill_back / image_size / anti_aliasing as render() passes them.  A constant of
+        the graph: vertices (or camera parameters) that require grad raise NotImplementedError -- detach them."""
+        sv = self._transform(vertices, K, R, t, dist_coeffs, orig_size)
+        return _attributes.rasterize_fragments(sv, faces, self.image_size, self.anti_aliasing, self.fill_back, self.near,
+                                               self.far)
+
+    def render_attributes(self, vertices, faces, attributes, background=None, K=None, R=None, t=None, dist_coeffs=None,
+                          orig_size=None):
+        """(images [B,C,s,s], alpha [B,s,s]) of per-vertex attributes [V,C] or [B,V,C]: fragments() followed by
+        interpolate_vertex_attributes, differentiable in the attributes only."""
+        fr = self.fragments(vertices, faces, K, R, t, dist_coeffs, orig_size)
+        return _attributes.interpolate_vertex_attributes(attributes, fr, background)
 
     def render_rgb_image_grid(self, vertices, image, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         """render_rgb of the grid mesh of a depth map (vertices [B,h*w,3], one per pixel, row-major) textured by `image`

@@ -1015,6 +1015,47 @@ int d3m_smooth_shade_backward(const float* vertices, int vertices_batch, const f
                               const d3m_csr* adjacency, float* scratch, size_t scratch_floats, float* grad_vertices,
                               float* grad_colors, float* grad_sh, int batch_size, int num_vertices, int num_tri,
                               d3m_stream_t stream);
+/* Per-vertex attribute images (an addition; csrc/d3m_attributes.h states the semantics and the order of every sum): C
+ * channels of per-vertex data interpolated over a COVERAGE RECORD with the sampler's perspective-correct weights.  The record
+ * is what d3m_forward_face_index_map_mesh left for batch_size views of ONE shared topology at the raster size S = image_size
+ * (anti_aliasing == 0) or 2 image_size: face_index_map [B,S,S] (every entry in [-1, F'), F' = (fill_back ? 2 : 1) num_tri),
+ * weight_map [B,S,S,3], depth_map [B,S,S], faces [B,F',3,3] (the dense copy: only owners' entries are read), tri [num_tri,3]
+ * i32 (every index in [0, num_vertices): the caller checks, where it builds the adjacency), and the visibility blob that
+ * d3m_visibility finished (visibility_size >= d3m_visibility_bytes(B, F'); read by the adjoint only, may be NULL forward). */
+typedef struct d3m_fragments {
+    const int32_t* face_index_map;
+    const float* weight_map;
+    const float* depth_map;
+    const float* faces;
+    const int32_t* tri;
+    const void* visibility;
+    size_t visibility_size;
+    int batch_size, num_tri, fill_back, image_size, anti_aliasing;
+} d3m_fragments;
+/* attributes [attributes_batch, V, C] f32, attributes_batch 1 (shared by the views) or B; background [C] or NULL (zeros).
+ * WRITES every element of images [B, C, image_size, image_size] and alpha [B, image_size, image_size] (rows top to bottom;
+ * with anti-aliasing the mean of the 2x2 internal pixels, background included).  One launch (k_vertex_attribute_images).
+ * D3M_ERR_INVALID, before any launch: a NULL record or a NULL map / faces / tri in it, NULL attributes / images / alpha,
+ * batch_size not in [1, 65535], num_tri or image_size <= 0, image_size beyond 16384, B F' beyond 2^31 - 1, attributes_batch
+ * neither 1 nor B, num_vertices <= 0, num_channels not in [1, 1024]. */
+int d3m_vertex_attribute_images(const d3m_fragments* fragments, const float* attributes, int attributes_batch,
+                                int num_vertices, int num_channels, const float* background, float* images, float* alpha,
+                                d3m_stream_t stream);
+/* Floats of scratch the adjoint needs: B F' 3 C per-face sums and B num_chunks C chunk sums of the adjacency's long rows
+ * (0 for sizes the adjoint refuses). */
+size_t d3m_vertex_attribute_scratch_floats(int batch_size, int num_faces, int num_channels, const d3m_csr* adjacency);
+/* The adjoint with respect to the attributes: grad_images [B, C, image_size, image_size] -> grad_attributes
+ * [attributes_batch, V, C], every element WRITTEN (a vertex of no visible face gets +0; shared attributes: summed over the
+ * views in ascending order).  adjacency: the faces' d3m_csr of V rows (item = 3 f + c).  scratch needs no initialisation.  No
+ * float atomics, nothing cleared; three launches (k_vertex_attribute_face_sums, k_vertex_attribute_large_face_sums,
+ * k_vertex_attribute_adjoint_rows) and k_vertex_attribute_adjoint_chunks on a mesh with long rows.
+ * D3M_ERR_INVALID, before any launch: what d3m_vertex_attribute_images refuses of the record and the sizes, a NULL or too
+ * small visibility blob, what d3m_csr lists (num_rows = num_vertices), NULL items / grad_images / scratch / grad_attributes,
+ * 3 num_tri beyond 2^31 - 1; D3M_ERR_WORKSPACE: scratch_floats below d3m_vertex_attribute_scratch_floats(). */
+int d3m_vertex_attribute_images_backward(const d3m_fragments* fragments, const float* grad_images,
+                                         const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
+                                         float* grad_attributes, int attributes_batch, int num_vertices, int num_channels,
+                                         d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
