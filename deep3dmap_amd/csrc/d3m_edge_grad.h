@@ -31,8 +31,9 @@
 //                     factored distance.  The walks never touch global memory;
 //      k_edge_overflow  crossings without a usable record (a workspace smaller than the scene needs, a line fuller than its
 //                     one-pass slice) are walked from global memory by one thread each; leaves at once otherwise;
-//   6. k_edge_gather  six lanes per visible face fetch their crossings' results (xpos) and add them in order; stored to
-//                     grad_faces or accumulated into the vertex gradient (VertexTarget).
+//   6. k_edge_gather  a block of 42 visible faces fetches its crossings' results (xpos) with all its threads into LDS, the
+//                     six lanes per face add their own in order; stored to grad_faces or accumulated into the vertex
+//                     gradient (VertexTarget).
 // Deterministic up to the final vertex atomics.  The reference OVERWRITES the 9 entries of every front-facing face
 // (KCU:501-502) and leaves culled ones alone (KCU:270); with the caller's zero-initialised grad_faces
 // (rasterize.py:111, a precondition of the C ABI) writing only the faces that own a pixel is the same thing: every
@@ -201,9 +202,23 @@ __device__ __forceinline__ EdgeSlopes edge_slopes(float p00, float p01, float p1
     return EdgeSlopes{(p11 - p01) / (p10 - p00), (p21 - p01) / (p20 - p00), (p11 - p21) / (p10 - p20)};
 }
 
-template <class Owner>
-__device__ __forceinline__ XGeom crossing_geometry(float p00, float p01, float p10, float p11, float p20, float p21,
-                                                   const EdgeSlopes sl, int axis, int fn, int is, int d0, Owner&& owner) {
+// crossing_geometry in three steps, so that every owner look-up of a crossing is requested before any is used:
+//   crossing_shape    everything that follows from the geometry alone (no look-up): all of XGeom but XG_OWNER / XG_IDLE;
+//   crossing_owners   the in-pixel's owner and, for an inward range short enough to be looked through, the owners of its
+//                     pixels -- 1 + XG_DEAD_SCAN INDEPENDENT loads (the lazy form -- in-pixel first, then the range pixel by
+//                     pixel, each load behind the test of the one before -- was a chain of up to seven dependent round
+//                     trips, and a wave advances with its slowest lane).  Positions past the range repeat its last pixel and
+//                     a crossing without a short range repeats its in-pixel: no address outside [in_from, in_to] of the
+//                     crossing's own line, nothing loaded that the lazy form could not have loaded;
+//   crossing_decide   XG_OWNER / XG_IDLE from the fetched values: the decisions of KCU:354 / :470 as before.
+struct XOwners {
+    int in_pixel;
+    int range[XG_DEAD_SCAN];
+};
+__device__ __forceinline__ bool crossing_short_range(const XGeom& g) { return g.in_to - g.in_from < XG_DEAD_SCAN; }
+
+__device__ __forceinline__ XGeom crossing_shape(float p00, float p01, float p10, float p11, float p20, float p21,
+                                                const EdgeSlopes sl, int axis, int is, int d0) {
     XGeom g;
     const int direction = (axis == 0) ? ((p00 < p10) ? -1 : 1) : ((p00 < p10) ? 1 : -1);   // KCU:297-308
     const float fd0 = (float)d0;
@@ -219,7 +234,6 @@ __device__ __forceinline__ XGeom crossing_geometry(float p00, float p01, float p
     // geometry_to_record)
     g.q0 = (p10 - p00) / (p10 - fd0);
     g.q1 = (p10 - p00) / (fd0 - p00);
-    if (owner(d0, g.d1_in) == fn) g.bits |= XG_OWNER;                                       // KCU:354
     // inward: in-pixel .. opposite edge (KCU:417-431)
     float d0_cross2;
     if ((fd0 - p00) * (fd0 - p20) < 0) d0_cross2 = sl.s02 * (fd0 - p00) + p01;
@@ -229,14 +243,39 @@ __device__ __forceinline__ XGeom crossing_geometry(float p00, float p01, float p
     g.in_to = min(max(g.d1_in, d1_limit), is - 1);
     // all pixels on the expected side of the crossing (see "FACTORED DISTANCE"): decided before clipping
     if ((0 < direction) ? g.in_to == g.d1_in : g.in_from == g.d1_in) g.bits |= XG_ORIENTED;
+    return g;
+}
+
+// (an alive crossing's; owner(d0, d1) returns face_index_map at that line position)
+template <class Owner>
+__device__ __forceinline__ XOwners crossing_owners(const XGeom& g, int d0, Owner&& owner) {
+    XOwners o;
+    const bool scan = crossing_short_range(g);
+    o.in_pixel = owner(d0, g.d1_in);
+#pragma unroll
+    for (int k = 0; k < XG_DEAD_SCAN; k++) o.range[k] = owner(d0, scan ? min(g.in_from + k, g.in_to) : g.d1_in);
+    return o;
+}
+
+__device__ __forceinline__ void crossing_decide(XGeom& g, int fn, const XOwners& o) {
+    if (o.in_pixel == fn) g.bits |= XG_OWNER;                                               // KCU:354
     // NEITHER WALK CAN CONTRIBUTE: the outward walk only exists when the in-pixel is the face's (KCU:354), and the inward
     // walk only counts pixels of the face (KCU:470).  A short inward range is looked through here (owners only, no
     // gradients needed); a crossing that fails both needs no record, no set-up and no result.
-    if (!(g.bits & XG_OWNER) && g.in_to - g.in_from < XG_DEAD_SCAN) {
+    if (!(g.bits & XG_OWNER) && crossing_short_range(g)) {
         bool own = false;
-        for (int d1 = g.in_from; d1 <= g.in_to; d1++) own = own || owner(d0, d1) == fn;
+#pragma unroll
+        for (int k = 0; k < XG_DEAD_SCAN; k++) own = own || o.range[k] == fn;      // (the repeats are pixels of the range)
         if (!own) g.bits |= XG_IDLE;
     }
+}
+
+template <class Owner>
+__device__ __forceinline__ XGeom crossing_geometry(float p00, float p01, float p10, float p11, float p20, float p21,
+                                                   const EdgeSlopes sl, int axis, int fn, int is, int d0, Owner&& owner) {
+    XGeom g = crossing_shape(p00, p01, p10, p11, p20, p21, sl, axis, is, d0);
+    if (!(g.bits & XG_ALIVE)) return g;
+    crossing_decide(g, fn, crossing_owners(g, d0, owner));
     return g;
 }
 
@@ -1707,11 +1746,17 @@ __global__ void __launch_bounds__(EGA_THREADS) k_edge_lines_alpha(EdgeGradArgs a
 // `parts` (> 1 only with a vertex target, whose sums are ADDED): a block's lanes are dealt to that many workgroups, each
 // taking every parts-th group of four crossings of every lane -- a coarse mesh's lane has hundreds of crossings to add up, one
 // dependent round trip per four (8 triangles @1024^2: 165 us for one workgroup's six-times-eight lanes).
+// parts == 1 takes the FLAT form (in the kernel): chunks of EG_GATHER_CHUNK crossings (16 KB of LDS, eight workgroups per
+// CU), in ascending order -- a coarse mesh's block holds many chunks.
+constexpr int EG_GATHER_PER = 4;                            // crossings fetched per thread and chunk
+constexpr int EG_GATHER_CHUNK = 256 * EG_GATHER_PER;
 template <class FS>
 __global__ void __launch_bounds__(256) k_edge_gather(FS fs, EdgePlan w, const float2* __restrict__ lane_partial,
                                                     const float* __restrict__ go, float* __restrict__ grad_faces,
                                                     VertexTarget vt, int parts) {
     __shared__ float2 s_g[256];
+    __shared__ float4 s_res[EG_GATHER_CHUNK];
+    __shared__ int s_total;
     if (blockIdx.x == 0 && threadIdx.x == 0) w.alloc[EG_ALLOC_LEFT] = 0;    // (k_edge_lines_alpha's list of left lines)
     const int n_vis = *w.n_visible;
     const int n_blocks = (n_vis + EG_FACES_PER_BLOCK - 1) / EG_FACES_PER_BLOCK;
@@ -1728,7 +1773,54 @@ __global__ void __launch_bounds__(256) k_edge_gather(FS fs, EdgePlan w, const fl
         const int pos = blk * EG_FACES_PER_BLOCK + t / 6, ea = t % 6;
         const bool on = t < EG_FACES_PER_BLOCK * 6 && pos < n_vis;
         float2 g = make_float2(0.0f, 0.0f);
-        if (on) {
+        long gi_top = 0;
+        if (parts == 1) {
+            // FLAT (uniform branch).  Everything the iteration needs from the plan is requested at once; then the block's
+            // crossings -- ONE contiguous run of indices, lane after lane -- are fetched by all 256 threads, a chunk at a time:
+            // positions (coalesced), then the results they point to, every load of the chunk in flight together, staged in
+            // LDS in crossing order.  A lane adds its own run from there in the order of the loop below: the same sums, bit
+            // for bit, without a chain of two round trips per four crossings of the wave's longest lane.
+            const bool use = on && records;
+            const int2 lc = use ? w.lane_cross[(size_t)pos * 6 + ea] : make_int2(0, 0);
+            const long cb = records ? (long)w.lane_block[blk] : 0;
+            if (on && !complete) g = lane_partial[(size_t)pos * 6 + ea];
+            if (on && ea == 0) gi_top = w.visible_list[pos];
+            // (the block's last listed lane ends the run)
+            if (t == min(EG_FACES_PER_BLOCK, n_vis - blk * EG_FACES_PER_BLOCK) * 6 - 1) s_total = lc.x + lc.y;
+            __syncthreads();
+            const int total = (int)max(min((long)s_total, (long)w.cap - cb), 0l);
+            const int my_end = min(lc.x + lc.y, total);
+            const float4* res4 = (const float4*)w.results;
+            for (int k0 = 0; k0 < total; k0 += EG_GATHER_CHUNK) {
+                int at[EG_GATHER_PER];
+#pragma unroll
+                for (int j = 0; j < EG_GATHER_PER; j++) {
+                    const int k = k0 + j * 256 + t;
+                    at[j] = k < total ? w.xpos[cb + k] : -1;
+                }
+                float4 r[EG_GATHER_PER];
+#pragma unroll
+                for (int j = 0; j < EG_GATHER_PER; j++)   // (at < 0: the crossing got no record because its walks cannot contribute)
+                    r[j] = at[j] >= 0 ? res4[at[j]] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll
+                for (int j = 0; j < EG_GATHER_PER; j++) s_res[j * 256 + t] = r[j];
+                __syncthreads();
+                const int hi = min(my_end, k0 + EG_GATHER_CHUNK);
+                for (int k = max(lc.x, k0); k < hi; k += 4) {
+                    float4 q[4];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) q[j] = s_res[min(k + j, hi - 1) - k0];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        if (k + j < hi) {
+                            g.x += q[j].x; g.y += q[j].y;
+                            g.x += q[j].z; g.y += q[j].w;
+                        }
+                    }
+                }
+                __syncthreads();
+            }
+        } else if (on) {
             if (!complete && part == 0) g = lane_partial[(size_t)pos * 6 + ea];
             // slots (2c, 2c+1) of the lane's crossings c, contiguous and 16-byte aligned: one float4 per crossing, four
             // crossings requested per round, added in slot order
@@ -1761,7 +1853,7 @@ __global__ void __launch_bounds__(256) k_edge_gather(FS fs, EdgePlan w, const fl
                 acc[edge * 2 + (1 - axis)] += r.x;                    // vertex pi[0] = edge, component 1 - axis (KCU:406)
                 acc[((edge + 1) % 3) * 2 + (1 - axis)] += r.y;        // vertex pi[1] = edge + 1            (KCU:411)
             }
-            const long gi = w.visible_list[pos];
+            const long gi = parts == 1 ? gi_top : (long)w.visible_list[pos];
             if (vt.gv) {
                 const int Fp = fs.num_faces();
                 const int b = (int)(gi / Fp), f = (int)(gi % Fp);
