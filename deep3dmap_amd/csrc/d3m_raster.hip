@@ -15,6 +15,7 @@
 #include "d3m_pose.h"
 #include "d3m_smooth_shade.h"
 #include "d3m_attributes.h"
+#include "d3m_uv_texture.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -2590,6 +2591,85 @@ D3M_EXPORT int d3m_vertex_attribute_images_backward(const d3m_fragments* fragmen
     LAUNCH("k_vertex_attribute_adjoint_rows", k_vertex_attribute_adjoint_rows,
            dim3(blocks_for((long)num_vertices * C, 256), shared ? 1 : m.B), dim3(256), st, adj, (const float*)partials,
            (const float*)G, (const int*)vis.flags, m.B, m.Ft, m.Fp, num_vertices, C, shared, grad_attributes);
+    return check_launch();
+}
+
+// Per-pixel uv texture images (d3m_uv_texture.h): a texture image looked up at every pixel's interpolated uv, and the
+// order-independent adjoint with respect to the image.  What the entry points refuse; `m`, `tx`: what the kernels read.
+static int ceil_log2(unsigned long long n) {
+    int k = 0;
+    while (k < 64 && (1ull << k) < n) k++;
+    return k;
+}
+
+static bool uv_texture_sizes_ok(int image_batch, int H, int W, int C) {
+    return image_batch >= 1 && image_batch <= 65535 && H >= 1 && H <= UVT_MAX_SIZE && W >= 1 && W <= UVT_MAX_SIZE && C >= 1 &&
+           C <= UVT_MAX_CHANNELS;
+}
+
+static bool uv_texture_ok(const d3m_fragments* fr, const float* faces_uv, int image_batch, int H, int W, int C, int wrapping,
+                          AttrMaps& m, UvTexture& tx) {
+    if (!faces_uv || misaligned4(faces_uv) || !uv_texture_sizes_ok(image_batch, H, W, C)) return false;
+    if (wrapping != D3M_WRAP_REPEAT && wrapping != D3M_WRAP_MIRRORED_REPEAT && wrapping != D3M_WRAP_CLAMP_TO_EDGE) return false;
+    if (!fragments_ok(fr, image_batch, 1, C, m)) return false;
+    tx = UvTexture{faces_uv, H, W, C, image_batch, wrapping};
+    return true;
+}
+
+D3M_EXPORT int d3m_uv_texture_images(const d3m_fragments* fragments, const float* faces_uv, const float* image,
+                                     int image_batch, int image_height, int image_width, int num_channels,
+                                     int texture_wrapping, const float* background, float* images, float* alpha,
+                                     d3m_stream_t stream) {
+    AttrMaps m;
+    UvTexture tx;
+    if (!image || !images || !alpha) return D3M_ERR_INVALID;
+    if (misaligned4(image) || misaligned4(background) || misaligned4(images) || misaligned4(alpha)) return D3M_ERR_INVALID;
+    if (!uv_texture_ok(fragments, faces_uv, image_batch, image_height, image_width, num_channels, texture_wrapping, m, tx))
+        return D3M_ERR_INVALID;
+    const long n = (long)fragments->image_size * fragments->image_size;
+    LAUNCH("k_uv_texture_images", k_uv_texture_images, dim3(blocks_for(n, 256), m.B), dim3(256), (hipStream_t)stream, m, tx,
+           image, background, images, alpha);
+    return check_launch();
+}
+
+D3M_EXPORT size_t d3m_uv_texture_images_scratch_bytes(int image_batch, int image_height, int image_width, int num_channels,
+                                                      int batch_size, int raster_size) {
+    if (!uv_texture_sizes_ok(image_batch, image_height, image_width, num_channels)) return 0;
+    if (batch_size < 1 || batch_size > 65535 || raster_size < 1 || raster_size > 32768) return 0;
+    if (image_batch != 1 && image_batch != batch_size) return 0;
+    if ((unsigned long long)batch_size * raster_size * raster_size > (1ull << 32)) return 0;
+    return (size_t)image_batch * image_height * image_width * num_channels * sizeof(long long) +
+           (size_t)UVT_MAX_BLOCKS * sizeof(unsigned);
+}
+
+D3M_EXPORT int d3m_uv_texture_images_backward(const d3m_fragments* fragments, const float* faces_uv, const float* grad_images,
+                                              int image_batch, int image_height, int image_width, int num_channels,
+                                              int texture_wrapping, void* scratch, size_t scratch_bytes, float* grad_image,
+                                              d3m_stream_t stream) {
+    AttrMaps m;
+    UvTexture tx;
+    if (!grad_images || !scratch || !grad_image) return D3M_ERR_INVALID;
+    if (misaligned4(grad_images) || misaligned4(grad_image) || ((uintptr_t)scratch & 7)) return D3M_ERR_INVALID;
+    if (!uv_texture_ok(fragments, faces_uv, image_batch, image_height, image_width, num_channels, texture_wrapping, m, tx))
+        return D3M_ERR_INVALID;
+    const size_t need = d3m_uv_texture_images_scratch_bytes(image_batch, image_height, image_width, num_channels, m.B, m.S);
+    if (need == 0) return D3M_ERR_INVALID;                              // (B S^2 beyond 2^32)
+    if (scratch_bytes < need) return D3M_ERR_WORKSPACE;
+    const long n_acc = (long)image_batch * image_height * image_width * num_channels;
+    const long s = fragments->image_size, n_g = (long)m.B * num_channels * s * s, n_px = (long)m.B * m.S * m.S;
+    const int frac = 62 - ceil_log2((unsigned long long)n_px);
+    unsigned long long* acc = (unsigned long long*)scratch;
+    unsigned* block_max = (unsigned*)(acc + n_acc);
+    hipStream_t st = (hipStream_t)stream;
+    const int n_max = (int)std::min(blocks_for(std::max(n_acc, n_g), 256), (unsigned)UVT_MAX_BLOCKS);
+    LAUNCH("k_uv_texture_images_clear_max", k_uv_texture_images_clear_max, dim3(n_max), dim3(256), st, grad_images, n_g,
+           m.aa ? 0.25f : 1.0f, acc, n_acc, block_max);
+    LAUNCH("k_uv_texture_images_scatter", k_uv_texture_images_scatter,
+           dim3(std::min(blocks_for(n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, m, tx, grad_images,
+           (const unsigned*)block_max, n_max, frac, acc);
+    LAUNCH("k_uv_texture_images_convert", k_uv_texture_images_convert,
+           dim3(std::min(blocks_for(n_acc, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)acc, n_acc,
+           (const unsigned*)block_max, n_max, frac, grad_image);
     return check_launch();
 }
 

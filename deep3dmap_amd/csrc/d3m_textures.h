@@ -43,6 +43,19 @@ struct TexelTaps {
     float w[4];
 };
 
+// The four bilinear taps of the texture-space position (pos_x, pos_y), 0 <= pos_x <= W - 1 and 0 <= pos_y <= H - 1, in LTK's
+// order p00, p10, p01, p11 (shared by texel_taps and by the per-pixel lookup of d3m_uv_texture.h).
+__device__ __forceinline__ void bilinear_taps(float pos_x, float pos_y, int image_height, int image_width, TexelTaps& t) {
+    const int xi = (int)pos_x, yi = (int)pos_y;
+    const float wx1 = pos_x - (float)xi, wx0 = 1 - wx1, wy1 = pos_y - (float)yi, wy0 = 1 - wy1;
+    // (int)(pos_y + 1), not yi + 1: the f32 sum can round up to the next integer (LTK)
+    const int y1 = min((int)(pos_y + 1), image_height - 1), x1 = min(xi + 1, image_width - 1);
+    t.pix[0] = (long)yi * image_width + xi; t.w[0] = wx0 * wy0;
+    t.pix[1] = (long)y1 * image_width + xi; t.w[1] = wx0 * wy1;
+    t.pix[2] = (long)yi * image_width + x1; t.w[2] = wx1 * wy0;
+    t.pix[3] = (long)y1 * image_width + x1; t.w[3] = wx1 * wy1;
+}
+
 __device__ __forceinline__ int texel_taps(const float* __restrict__ face_uv, int r, int ts, int image_height,
                                           int image_width, int wrapping, int use_bilinear, TexelTaps& t) {
     if (wrapping == D3M_WRAP_CLAMP_TO_BORDER) return 0;        // LTK:97,109
@@ -54,14 +67,7 @@ __device__ __forceinline__ int texel_taps(const float* __restrict__ face_uv, int
     const float pos_x = (uv[0] * dim0 + uv[2] * dim1 + uv[4] * dim2) * (float)(image_width - 1);
     const float pos_y = (uv[1] * dim0 + uv[3] * dim1 + uv[5] * dim2) * (float)(image_height - 1);
     if (use_bilinear) {
-        const int xi = (int)pos_x, yi = (int)pos_y;
-        const float wx1 = pos_x - (float)xi, wx0 = 1 - wx1, wy1 = pos_y - (float)yi, wy0 = 1 - wy1;
-        // (int)(pos_y + 1), not yi + 1: the f32 sum can round up to the next integer (LTK)
-        const int y1 = min((int)(pos_y + 1), image_height - 1), x1 = min(xi + 1, image_width - 1);
-        t.pix[0] = (long)yi * image_width + xi; t.w[0] = wx0 * wy0;
-        t.pix[1] = (long)y1 * image_width + xi; t.w[1] = wx0 * wy1;
-        t.pix[2] = (long)yi * image_width + x1; t.w[2] = wx1 * wy0;
-        t.pix[3] = (long)y1 * image_width + x1; t.w[3] = wx1 * wy1;
+        bilinear_taps(pos_x, pos_y, image_height, image_width, t);
         return 4;
     }
     t.pix[0] = (long)(int)roundf(pos_y) * image_width + (int)roundf(pos_x);

@@ -8,7 +8,7 @@ import numpy
 import torch
 import torch.nn as nn
 
-from . import attributes as _attributes, cameras, mesh_ops
+from . import attributes as _attributes, cameras, mesh_ops, uv_texture_images as _uv_texture_images
 from .rasterize import (light_on_device, rasterize, rasterize_depth, rasterize_lit, rasterize_lit_fit,
                         rasterize_lit_image_grid, rasterize_mesh_modes, rasterize_rgbad, rasterize_silhouettes)
 
@@ -216,6 +216,13 @@ class Renderer(nn.Module):
         interpolate_vertex_attributes, differentiable in the attributes only."""
         fr = self.fragments(vertices, faces, K, R, t, dist_coeffs, orig_size)
         return _attributes.interpolate_vertex_attributes(attributes, fr, background)
+
+    def render_uv_texture(self, vertices, faces, image, faces_uv, texture_wrapping='REPEAT', background=None, K=None, R=None,
+                          t=None, dist_coeffs=None, orig_size=None):
+        """(images [B,C,s,s], alpha [B,s,s]) of a texture image [H,W,C] or [B,H,W,C] looked up at every pixel's interpolated
+        uv (faces_uv [F,3,2]): fragments() followed by sample_uv_texture, differentiable in the image only."""
+        fr = self.fragments(vertices, faces, K, R, t, dist_coeffs, orig_size)
+        return _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background)
 
     def render_rgb_image_grid(self, vertices, image, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         """render_rgb of the grid mesh of a depth map (vertices [B,h*w,3], one per pixel, row-major) textured by `image`

@@ -1056,6 +1056,34 @@ int d3m_vertex_attribute_images_backward(const d3m_fragments* fragments, const f
                                          const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
                                          float* grad_attributes, int attributes_batch, int num_vertices, int num_channels,
                                          d3m_stream_t stream);
+/* Per-pixel uv texture images (an addition; csrc/d3m_uv_texture.h states the semantics): image [image_batch, H, W, C] f32
+ * (channels last; image_batch 1 -- shared by the views -- or B) looked up bilinearly at the interpolated uv of every pixel of
+ * a coverage record; faces_uv [num_tri, 3, 2] f32 is the per-corner uv of d3m_load_textures, wrapped per corner with
+ * texture_wrapping 0 REPEAT, 1 MIRRORED_REPEAT or 2 CLAMP_TO_EDGE; background [C] or NULL (zeros).  WRITES every element of
+ * images [B, C, image_size, image_size] and alpha [B, image_size, image_size] (alpha: the bits of
+ * d3m_vertex_attribute_images').  One launch (k_uv_texture_images).
+ * D3M_ERR_INVALID, before any launch: what d3m_vertex_attribute_images refuses of the record, a NULL or misaligned faces_uv /
+ * image / images / alpha, image_batch neither 1 nor B, H or W not in [1, 32768], C not in [1, 64], texture_wrapping 3
+ * (CLAMP_TO_BORDER) or outside 0..2. */
+int d3m_uv_texture_images(const d3m_fragments* fragments, const float* faces_uv, const float* image, int image_batch,
+                          int image_height, int image_width, int num_channels, int texture_wrapping,
+                          const float* background, float* images, float* alpha, d3m_stream_t stream);
+/* Bytes of scratch the adjoint needs for a record of batch_size views at the raster size S: image_batch H W C int64
+ * accumulators and 1024 block maxima.  0 for sizes the adjoint refuses, batch_size S S beyond 2^32 among them. */
+size_t d3m_uv_texture_images_scratch_bytes(int image_batch, int image_height, int image_width, int num_channels,
+                                           int batch_size, int raster_size);
+/* The adjoint with respect to the image: grad_images [B, C, image_size, image_size] -> grad_image [image_batch, H, W, C],
+ * every element WRITTEN, the same bits whatever the order of arrival: each term is rounded to a multiple of the quantum
+ * 2^(ilogb(max |scale g|) + 1 - frac), frac = 62 - ceil(log2(B S S)), and added to an int64 accumulator with an integer
+ * atomic; no float atomics, nothing read back.  A texel no sample reaches, and every texel when grad_images is all zeros,
+ * gets +0; an Inf or NaN anywhere in grad_images makes every element NaN (no error status).  scratch (8-byte aligned) needs no
+ * initialisation.  Three launches (k_uv_texture_images_clear_max, k_uv_texture_images_scatter, k_uv_texture_images_convert).
+ * D3M_ERR_INVALID, before any launch: what d3m_uv_texture_images refuses, NULL grad_images / scratch / grad_image, a
+ * misaligned scratch, B S S beyond 2^32; D3M_ERR_WORKSPACE: scratch_bytes below d3m_uv_texture_images_scratch_bytes(). */
+int d3m_uv_texture_images_backward(const d3m_fragments* fragments, const float* faces_uv, const float* grad_images,
+                                   int image_batch, int image_height, int image_width, int num_channels,
+                                   int texture_wrapping, void* scratch, size_t scratch_bytes, float* grad_image,
+                                   d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
