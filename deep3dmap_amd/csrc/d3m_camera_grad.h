@@ -7,12 +7,13 @@
 //                    distortion chain                                                        (23 sums)
 // and the look / look_at rows go through the adjoint of the basis (z = normalise(at - eye) or normalise(direction),
 // x = normalise(up x z), y = normalise(z x x); F.normalize(eps=1e-5): in the clamped branch the gradient does not flow
-// through the norm).  Two stages in a FIXED order, no float atomics, as d3m_light_grad.h: k_camera_params_partial -- per
-// (view, vertex chunk) partials, each lane's vertices in ascending order, butterfly sums within the wave, the waves in
-// order -- then k_camera_params_finish, one workgroup that adds each view's partials in order, applies the basis adjoint,
-// and sums the views of a parameter of batch 1 in view order.  The same bits on every run.
+// through the norm).  Two stages in the FIXED order of d3m_set_sums.h, with WaveTree::XorButterfly, 12 or 23 sums (row
+// stride 23, the tail stored as 0) and 1024 vertices per part up to 128 parts: k_camera_params_partial, then
+// k_camera_params_finish, one workgroup that applies the basis adjoint to each view's sums and routes the rows.  The same
+// bits on every run.
 #pragma once
 #include "d3m_aux.h"
+#include "d3m_set_sums.h"
 
 namespace d3m {
 
@@ -20,12 +21,10 @@ constexpr int CAM_SUMS = 23;            // the projection's sums (look / look_at
 constexpr int CAM_ROW = 23;             // one view's gradients: projection R 9, t 3, K[0..5] 6, dist 5;
                                         // look / look_at eye 3, at_or_direction 3, up 3, rows 9
 constexpr int CAM_OUT = 26;             // ... and the projection's K[6..8] (zeros, as the reference's)
-constexpr int CAM_MAX_PARTS = 128;      // workgroups per view
+constexpr int CAM_PER_PART = 1024;      // vertices per workgroup ...
+constexpr int CAM_MAX_PARTS = 128;      // ... and workgroups per view
 
-__host__ __device__ __forceinline__ int camera_parts(int V) {
-    const int n = (V + 1023) / 1024;
-    return n < 1 ? 1 : (n > CAM_MAX_PARTS ? CAM_MAX_PARTS : n);
-}
+__host__ __device__ __forceinline__ int camera_parts(int V) { return set_parts(V, CAM_PER_PART, CAM_MAX_PARTS); }
 
 // grid (parts, B): partial [B, parts, CAM_SUMS]
 template <bool PROJ>
@@ -81,22 +80,7 @@ __global__ void __launch_bounds__(256) k_camera_params_partial(const float* __re
             }
         }
     }
-#pragma unroll
-    for (int k = 0; k < NS; k++) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < NS; k++) s_wave[wave][k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < CAM_SUMS) {
-        const int k = threadIdx.x;
-        partial[((size_t)b * parts + blockIdx.x) * CAM_SUMS + k] =
-            k < NS ? ((s_wave[0][k] + s_wave[1][k]) + s_wave[2][k]) + s_wave[3][k] : 0.0f;
-    }
+    set_store_partial<NS, WaveTree::XorButterfly, CAM_SUMS>(acc, s_wave, partial, b, parts);
 }
 
 // adjoint of u = v / max(|v|, 1e-5) (normalize3): gu -> gv
@@ -126,12 +110,7 @@ __global__ void __launch_bounds__(256) k_camera_params_finish(Cam c, CamBasis bs
     const bool proj = c.mode == D3M_CAMERA_PROJECTION;
     for (int b = threadIdx.x; b < B; b += 256) {
         float s[CAM_SUMS];
-#pragma unroll
-        for (int k = 0; k < CAM_SUMS; k++) s[k] = 0.0f;
-        for (int p = 0; p < parts; p++) {
-#pragma unroll
-            for (int k = 0; k < CAM_SUMS; k++) s[k] += partial[((size_t)b * parts + p) * CAM_SUMS + k];
-        }
+        set_add_parts(partial, b, parts, s);
         float* row = rows + (size_t)b * CAM_ROW;
         if (proj) {
 #pragma unroll
@@ -181,34 +160,20 @@ __global__ void __launch_bounds__(256) k_camera_params_finish(Cam c, CamBasis bs
         for (int k = 0; k < 9; k++) row[9 + k] = s[k];
     }
     __syncthreads();
-    // entry j of a view's gradients -> (output, its batch, column, width)
-    for (int e = threadIdx.x; e < CAM_OUT * (B + 1); e += 256) {
-        const int b = e / CAM_OUT, j = e % CAM_OUT;      // b == B: the sum over the views (parameters of batch 1)
-        float* dst = nullptr;
-        int nb = 1, col = 0, width = 3;
+    set_route_rows<CAM_ROW, CAM_OUT>(rows, B, [&](int j) -> SetRoute {
         if (proj) {
-            if (j < 9) { dst = out.rot; nb = out.rot_b; col = j; width = 9; }
-            else if (j < 12) { dst = out.eye_or_t; nb = out.eye_b; col = j - 9; }
-            else if (j < 18) { dst = out.K; nb = out.K_b; col = j - 12; width = 9; }
-            else if (j < 23) { dst = out.dist; nb = out.dist_b; col = j - 18; width = 5; }
-            else { dst = out.K; nb = out.K_b; col = j - 17; width = 9; }       // K's last row: zeros
-        } else {
-            if (j < 3) { dst = out.eye_or_t; nb = out.eye_b; col = j; }
-            else if (j < 6) { dst = out.at; nb = out.at_b; col = j - 3; }
-            else if (j < 9) { dst = out.up; nb = out.up_b; col = j - 6; }
-            else if (j < 18) { dst = out.rot; nb = out.rot_b; col = j - 9; width = 9; }
+            if (j < 9) return {out.rot, out.rot_b, j, 9, false};
+            if (j < 12) return {out.eye_or_t, out.eye_b, j - 9, 3, false};
+            if (j < 18) return {out.K, out.K_b, j - 12, 9, false};
+            if (j < 23) return {out.dist, out.dist_b, j - 18, 5, false};
+            return {out.K, out.K_b, j - 17, 9, true};                          // K's last row: zeros
         }
-        if (!dst) continue;
-        const bool zero = proj && j >= CAM_ROW;
-        if (nb > 1 && b < B) {
-            dst[(size_t)b * width + col] = zero ? 0.0f : rows[(size_t)b * CAM_ROW + j];
-        } else if (nb <= 1 && b == B) {
-            float t = 0.0f;
-            if (!zero)
-                for (int r = 0; r < B; r++) t += rows[(size_t)r * CAM_ROW + j];
-            dst[col] = t;
-        }
-    }
+        if (j < 3) return {out.eye_or_t, out.eye_b, j, 3, false};
+        if (j < 6) return {out.at, out.at_b, j - 3, 3, false};
+        if (j < 9) return {out.up, out.up_b, j - 6, 3, false};
+        if (j < 18) return {out.rot, out.rot_b, j - 9, 9, false};
+        return {nullptr, 1, 0, 3, false};
+    });
 }
 
 }  // namespace d3m

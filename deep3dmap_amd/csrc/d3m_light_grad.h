@@ -5,23 +5,21 @@
 //   d ia = ca . sum G            d ca = ia * sum G
 //   d id = cd . sum r G          d cd = id * sum r G          d dir = id * sum [n.d > 0] (G . cd) n
 // so one pass over the faces reduces nine sums per row; a term whose intensity is 0 is skipped (lighting.py:36,40) and its
-// parameters get zeros.  Two stages in a FIXED order, no float atomics: k_light_params_partial -- per-workgroup partials,
-// each lane's faces in ascending order, butterfly sums within the wave, the waves in order -- then k_light_params_finish, one
-// workgroup that adds the partials in order, forms each row's gradients and sums the rows of a parameter of batch 1 in view
-// order.  The same bits on every run, in every mode.
+// parameters get zeros.  Two stages in the FIXED order of d3m_set_sums.h, with WaveTree::XorButterfly, 9 sums and 1024 faces
+// per part up to 128 parts: k_light_params_partial, then k_light_params_finish, one workgroup that forms each row's
+// gradients from its sums and routes them.  The same bits on every run, in every mode.
 #pragma once
 #include "d3m_aux.h"
+#include "d3m_set_sums.h"
 
 namespace d3m {
 
 constexpr int LIGHT_SUMS = 9;           // sum G, sum r G, sum [n.d > 0] (G . cd) n
 constexpr int LIGHT_PARAMS = 11;        // ia, id, ca[3], cd[3], dir[3]
-constexpr int LIGHT_MAX_PARTS = 128;    // workgroups per light row
+constexpr int LIGHT_PER_PART = 1024;    // faces per workgroup ...
+constexpr int LIGHT_MAX_PARTS = 128;    // ... and workgroups per light row
 
-__host__ __device__ __forceinline__ int light_parts(int Fp) {
-    const int n = (Fp + 1023) / 1024;
-    return n < 1 ? 1 : (n > LIGHT_MAX_PARTS ? LIGHT_MAX_PARTS : n);
-}
+__host__ __device__ __forceinline__ int light_parts(int Fp) { return set_parts(Fp, LIGHT_PER_PART, LIGHT_MAX_PARTS); }
 
 // grid (parts, Bl): partial [Bl, parts, 9]
 __global__ void __launch_bounds__(256) k_light_params_partial(IndexedFaces fs, DevLight dl, const float* __restrict__ g_light,
@@ -49,21 +47,7 @@ __global__ void __launch_bounds__(256) k_light_params_partial(IndexedFaces fs, D
             acc[6 + k] += gd * nrm[k];
         }
     }
-#pragma unroll
-    for (int k = 0; k < LIGHT_SUMS; k++) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < LIGHT_SUMS; k++) s_wave[wave][k] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < LIGHT_SUMS) {
-        const int k = threadIdx.x;
-        partial[((size_t)b * parts + blockIdx.x) * LIGHT_SUMS + k] = ((s_wave[0][k] + s_wave[1][k]) + s_wave[2][k]) + s_wave[3][k];
-    }
+    set_store_partial<LIGHT_SUMS, WaveTree::XorButterfly>(acc, s_wave, partial, b, parts);
 }
 
 // One workgroup.  rows [Bl, 11]: each row's gradients (workspace); `out` the parameters' gradients (NULL fields skipped).
@@ -75,12 +59,7 @@ __global__ void __launch_bounds__(256) k_light_params_finish(DevLight dl, const 
                                                             float* __restrict__ rows, LightGradOut out) {
     for (int b = threadIdx.x; b < Bl; b += 256) {
         float s[LIGHT_SUMS];
-#pragma unroll
-        for (int k = 0; k < LIGHT_SUMS; k++) s[k] = 0.0f;
-        for (int p = 0; p < parts; p++) {
-#pragma unroll
-            for (int k = 0; k < LIGHT_SUMS; k++) s[k] += partial[((size_t)b * parts + p) * LIGHT_SUMS + k];
-        }
+        set_add_parts(partial, b, parts, s);
         const LightParams lp = light_at(dl, b);
         const bool amb = lp.ia != 0, dir = lp.id != 0;
         float* row = rows + (size_t)b * LIGHT_PARAMS;
@@ -94,25 +73,13 @@ __global__ void __launch_bounds__(256) k_light_params_finish(DevLight dl, const 
         }
     }
     __syncthreads();
-    // parameter j of the row -> (output, its batch, column)
-    for (int e = threadIdx.x; e < LIGHT_PARAMS * (Bl + 1); e += 256) {
-        const int b = e / LIGHT_PARAMS, j = e % LIGHT_PARAMS;      // b == Bl: the sum over the rows (parameters of batch 1)
-        float* dst;
-        int nb, col, width;
-        if (j == 0) { dst = out.ia; nb = out.ia_b; col = 0; width = 1; }
-        else if (j == 1) { dst = out.id; nb = out.id_b; col = 0; width = 1; }
-        else if (j < 5) { dst = out.ca; nb = out.ca_b; col = j - 2; width = 3; }
-        else if (j < 8) { dst = out.cd; nb = out.cd_b; col = j - 5; width = 3; }
-        else { dst = out.dir; nb = out.dir_b; col = j - 8; width = 3; }
-        if (!dst) continue;
-        if (nb > 1 && b < Bl) {
-            dst[(size_t)b * width + col] = rows[(size_t)b * LIGHT_PARAMS + j];
-        } else if (nb <= 1 && b == Bl) {
-            float t = 0.0f;
-            for (int r = 0; r < Bl; r++) t += rows[(size_t)r * LIGHT_PARAMS + j];
-            dst[col] = t;
-        }
-    }
+    set_route_rows<LIGHT_PARAMS, LIGHT_PARAMS>(rows, Bl, [&](int j) -> SetRoute {
+        if (j == 0) return {out.ia, out.ia_b, 0, 1, false};
+        if (j == 1) return {out.id, out.id_b, 0, 1, false};
+        if (j < 5) return {out.ca, out.ca_b, j - 2, 3, false};
+        if (j < 8) return {out.cd, out.cd_b, j - 5, 3, false};
+        return {out.dir, out.dir_b, j - 8, 3, false};
+    });
 }
 
 }  // namespace d3m

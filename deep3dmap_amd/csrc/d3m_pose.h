@@ -17,17 +17,17 @@
 //   k_pose_forward          grid (parts, B): lanes stride over the V vertices, then over the L landmarks (the same
 //                           expression on the gathered point, so lm equals the rows of posed bit for bit).
 //   k_pose_backward_chunks  grid (parts, B), or (parts, 1) with shared vertices, where the workgroup walks the sets in
-//                           ascending order and adds into its own g_x elements.  A lane takes the vertices part 256 + lane,
-//                           + parts 256, ... in ascending order into 12 sums (M row-major, then n); wave_sum within the
-//                           wave; the four waves in wave order; one plainly stored partial per (set, part).  g_x is written
-//                           from the same read of G.
-//   k_pose_backward_finish  a lane per set adds the set's partials in ascending part order, then the landmark terms in
+//                           ascending order and adds into its own g_x elements.  The 12 sums (M row-major, then n) of a
+//                           set: WaveTree::DppRows, PS_BLOCK vertices per part up to PS_MAX_PARTS parts, see
+//                           d3m_set_sums.h.  g_x is written from the same read of G.
+//   k_pose_backward_finish  a lane per set adds the set's partials (d3m_set_sums.h, step 4), then the landmark terms in
 //                           ascending l, and applies the Euler adjoint.  Further workgroups of the same launch add the
 //                           landmark gradients to g_x: per-set vertices, a lane per (set, coordinate) that walks l in
 //                           ascending order; shared vertices, one workgroup that first sums every (l, coordinate) over the
 //                           sets in ascending order in LDS, then three lanes walk l in ascending order.
 #pragma once
 #include "d3m_aux.h"
+#include "d3m_set_sums.h"
 
 namespace d3m {
 
@@ -39,10 +39,7 @@ constexpr int PS_STAGE = 64;            // rotations staged in LDS at a time
 constexpr int PS_ROT = 13;              // R (9), s, tau t (3)
 constexpr int PS_MAX_LANDMARKS = 1024;
 
-__host__ __device__ __forceinline__ int pose_parts(long items) {
-    const long n = (items + PS_BLOCK - 1) / PS_BLOCK;
-    return n < 1 ? 1 : (n > PS_MAX_PARTS ? PS_MAX_PARTS : (int)n);
-}
+__host__ __device__ __forceinline__ int pose_parts(long items) { return set_parts(items, PS_BLOCK, PS_MAX_PARTS); }
 
 // the clamped angles' factors
 __device__ __forceinline__ void pose_factors(const float* p, float limit, float* mx, float* my, float* mz, float* cs) {
@@ -116,7 +113,7 @@ __global__ void __launch_bounds__(PS_BLOCK) k_pose_backward_chunks(const float* 
                                                                    float* __restrict__ partial, int B, int V) {
     __shared__ float s_rot[PS_STAGE][PS_ROT];
     __shared__ float s_wave[2][4][PS_SUMS];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, parts = gridDim.x;
+    const int t = threadIdx.x, parts = gridDim.x;
     const bool shared = vb <= 1;
     const int b_begin = shared ? 0 : blockIdx.y, b_end = shared ? B : b_begin + 1;
     for (int b0 = b_begin; b0 < b_end; b0 += PS_STAGE) {
@@ -156,18 +153,9 @@ __global__ void __launch_bounds__(PS_BLOCK) k_pose_backward_chunks(const float* 
                     }
                 }
             }
-            if (partial) {                                  // (uniform: the barrier is met by every lane)
-#pragma unroll
-                for (int j = 0; j < PS_SUMS; j++) acc[j] = wave_sum(acc[j]);
-                float(*w)[PS_SUMS] = s_wave[k & 1];         // two buffers: set k + 1 is written while set k is read
-                if (lane == 0) {
-#pragma unroll
-                    for (int j = 0; j < PS_SUMS; j++) w[wave][j] = acc[j];
-                }
-                __syncthreads();
-                if (t < PS_SUMS)
-                    partial[((size_t)b * parts + blockIdx.x) * PS_SUMS + t] = ((w[0][t] + w[1][t]) + w[2][t]) + w[3][t];
-            }
+            if (partial)                                    // (uniform: the barrier is met by every lane)
+                set_store_partial<PS_SUMS, WaveTree::DppRows>(      // two buffers: set k + 1 is written while set k is read
+                    acc, s_wave[k & 1], partial, b, parts);
         }
     }
 }
@@ -190,12 +178,7 @@ __global__ void __launch_bounds__(PS_FINISH_SETS) k_pose_backward_finish(const f
         const int b = blockIdx.x * PS_FINISH_SETS + t;
         if (b >= B) return;
         float m[PS_SUMS];
-#pragma unroll
-        for (int j = 0; j < PS_SUMS; j++) m[j] = 0.f;
-        for (int p = 0; p < parts; p++) {
-#pragma unroll
-            for (int j = 0; j < PS_SUMS; j++) m[j] += partial[((size_t)b * parts + p) * PS_SUMS + j];
-        }
+        set_add_parts(partial, b, parts, m);
         if (g_lm) {
             const float* x0 = vertices + (size_t)(vb > 1 ? b : 0) * V * 3;
             for (int l = 0; l < L; l++) {

@@ -9,14 +9,16 @@
 // long_chunk_ptr[l] .. long_chunk_ptr[l + 1].  THE ORDER of a long row's sum, the same bits on every run:
 //   1. one workgroup of RG_BLOCK lanes per chunk; lane t adds the terms of items start + t, start + t + RG_BLOCK, ... in
 //      that order, from 0;
-//   2. the 64 lanes of a wave are combined by the butterfly v += __shfl_xor(v, off, 64), off = 32, 16, ..., 1;
-//   3. lane 0 of each wave stages its sum; after one barrier the chunk's sum is s = 0; s += wave[w] for w = 0 .. 3;
+//   2. the 64 lanes of a wave are combined by the butterfly v += __shfl_xor(v, off, 64), off = 32, 16, ..., 1
+//      (d3m_set_sums.h's WaveTree::XorButterfly; its DppRows is another tree and is not used here);
+//   3. lane 0 of each wave stages its sum; after one barrier the chunk's sum is s = 0; s += wave[w] for w = 0 .. 3
+//      (from 0: not the combine of d3m_set_sums.h, which starts from wave 0's value);
 //   4. the row adds its chunks' sums in chunk order, onto whatever it holds already.
 // No float atomics, and no workgroup waits for another: the chunk sums go through a partials array between two launches.
-// (d3m_device.h's wave_sum() is another tree: it is not used here.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "d3m_set_sums.h"
 
 namespace d3m {
 
@@ -65,9 +67,7 @@ __device__ __forceinline__ int rg_chunk_owner(const LongRows& t, int ch) {
 template <int N>
 __device__ __forceinline__ void rg_block_sum(float (&v)[N]) {
     __shared__ float staged[RG_BLOCK / 64][N];
-#pragma unroll
-    for (int k = 0; k < N; k++)
-        for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    wave_tree_sums<WaveTree::XorButterfly>(v);
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
         for (int k = 0; k < N; k++) staged[threadIdx.x >> 6][k] = v[k];

@@ -23,10 +23,8 @@
 //   rows (s and g_x)   a row of up to long_row items: its lane adds the items' terms in ascending item order, from 0.  A
 //                      longer row: the chunk sums of d3m_row_gather.h (which states their order), added in chunk order.
 //   L, g_n             j ascending from the first product; k ascending from 0; g_normals last.
-//   g_sh               workgroup p of a set's ss_parts(V) takes the vertices 256 p + lane, + 256 parts, ... in ascending
-//                      order per lane into 27 sums (k-major); wave_sum within the wave; the four waves in wave order; one
-//                      plainly stored partial per (set, p); k_smooth_shade_backward_finish adds a set's partials in
-//                      ascending p.  (The tree of d3m_pose.h, with its constants.)
+//   g_sh               27 sums per set (k-major): WaveTree::DppRows, SS_BLOCK vertices per part up to SS_MAX_PARTS parts,
+//                      see d3m_set_sums.h; k_smooth_shade_backward_finish is its step 4.
 //   shared inputs      the gradient of an input without a set dimension is summed over the sets in ascending order by the
 //                      lane that owns the element: g_colors and g_n (g_s is linear in g_n: one projection, after the last
 //                      set) in k_smooth_shade_backward_vertices, g_sh in the finish (each set's sum first, then the sets).
@@ -39,6 +37,7 @@
 #pragma once
 #include "d3m_aux.h"
 #include "d3m_row_gather.h"
+#include "d3m_set_sums.h"
 
 namespace d3m {
 
@@ -50,10 +49,7 @@ constexpr float SS_EPS = 1e-6f;
 constexpr float SS_A0 = 0.28209479177387814f, SS_A1 = 0.4886025119029199f, SS_A2 = 0.24430125595145996f,
                 SS_A3 = 1.0925484305920792f, SS_A4 = 0.5462742152960396f;
 
-__host__ __device__ __forceinline__ int ss_parts(long items) {
-    const long n = (items + SS_BLOCK - 1) / SS_BLOCK;
-    return n < 1 ? 1 : (n > SS_MAX_PARTS ? SS_MAX_PARTS : (int)n);
-}
+__host__ __device__ __forceinline__ int ss_parts(long items) { return set_parts(items, SS_BLOCK, SS_MAX_PARTS); }
 
 __device__ __forceinline__ void ss_basis(const float* n, float* H) {
     const float nx = n[0], ny = n[1], nz = n[2];
@@ -194,7 +190,7 @@ __global__ void __launch_bounds__(SS_BLOCK) k_smooth_shade_backward_vertices(con
                                                                              float* __restrict__ sh_partial, int B, int V,
                                                                              int walk_sets) {
     __shared__ float s_wave[2][SS_BLOCK / 64][SS_SUMS];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63, parts = gridDim.x;
+    const int t = threadIdx.x, parts = gridDim.x;
     const int b_begin = walk_sets ? 0 : blockIdx.y, b_end = walk_sets ? B : b_begin + 1;
     for (int b = b_begin; b < b_end; b++) {
         const float* shp = sh ? sh + (size_t)(sb > 1 ? b : 0) * SS_SUMS : nullptr;
@@ -247,18 +243,9 @@ __global__ void __launch_bounds__(SS_BLOCK) k_smooth_shade_backward_vertices(con
                 g_s[nat] = gn[0]; g_s[nat + 1] = gn[1]; g_s[nat + 2] = gn[2];
             }
         }
-        if (sh_partial) {                                   // (uniform: the barrier is met by every lane)
-#pragma unroll
-            for (int j = 0; j < SS_SUMS; j++) acc[j] = wave_sum(acc[j]);
-            float(*w)[SS_SUMS] = s_wave[(b - b_begin) & 1];   // two buffers: the next set is written while this one is read
-            if (lane == 0) {
-#pragma unroll
-                for (int j = 0; j < SS_SUMS; j++) w[wave][j] = acc[j];
-            }
-            __syncthreads();
-            if (t < SS_SUMS)
-                sh_partial[((size_t)b * parts + blockIdx.x) * SS_SUMS + t] = ((w[0][t] + w[1][t]) + w[2][t]) + w[3][t];
-        }
+        if (sh_partial)                                     // (uniform: the barrier is met by every lane)
+            set_store_partial<SS_SUMS, WaveTree::DppRows>(    // two buffers: the next set is written while this one is read
+                acc, s_wave[(b - b_begin) & 1], sh_partial, b, parts);
     }
 }
 
@@ -272,9 +259,9 @@ __global__ void __launch_bounds__(SS_BLOCK) k_smooth_shade_backward_finish(const
     const int b_begin = sb > 1 ? i / SS_SUMS : 0, b_end = sb > 1 ? b_begin + 1 : B;
     float total = 0.f;
     for (int b = b_begin; b < b_end; b++) {
-        float s = 0.f;
-        for (int p = 0; p < parts; p++) s += sh_partial[((size_t)b * parts + p) * SS_SUMS + q];
-        total = b == b_begin ? s : total + s;
+        float s[1];
+        set_add_parts<1, SS_SUMS>(sh_partial + q, b, parts, s);
+        total = b == b_begin ? s[0] : total + s[0];
     }
     g_sh[i] = total;
 }
