@@ -16,6 +16,7 @@
 #include "d3m_smooth_shade.h"
 #include "d3m_attributes.h"
 #include "d3m_uv_texture.h"
+#include "d3m_uv_texture_mip.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -30,6 +31,7 @@
 #include "d3m_light_grad.h"
 #include "d3m_camera_grad.h"
 #include <climits>
+#include <cmath>
 #include <cstdlib>
 #include <atomic>
 
@@ -2670,6 +2672,112 @@ D3M_EXPORT int d3m_uv_texture_images_backward(const d3m_fragments* fragments, co
     LAUNCH("k_uv_texture_images_convert", k_uv_texture_images_convert,
            dim3(std::min(blocks_for(n_acc, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)acc, n_acc,
            (const unsigned*)block_max, n_max, frac, grad_image);
+    return check_launch();
+}
+
+// Mip-mapped per-pixel uv texture images (d3m_uv_texture_mip.h).  `mp`: the level offsets, as the kernels read them.
+static bool uv_mip_ok(int H, int W, int levels, float lod_bias, UvMip& mp) {
+    if (levels < 1 || levels > UVT_MAX_LEVEL || H < 1 || W < 1 || H > UVT_MAX_SIZE || W > UVT_MAX_SIZE) return false;
+    if ((H & ((1 << levels) - 1)) || (W & ((1 << levels) - 1)) || !std::isfinite(lod_bias)) return false;
+    mp.L = levels;
+    mp.lod_bias = lod_bias;
+    long T = 0;
+    for (int l = 0; l <= UVT_MAX_LEVEL; l++) {
+        mp.offset[l] = T;
+        if (l <= levels) T += (long)(H >> l) * (W >> l);
+    }
+    mp.T = T;
+    return true;
+}
+
+D3M_EXPORT int d3m_texture_mip_pyramid(const float* image, int image_batch, int image_height, int image_width,
+                                       int num_channels, int levels, float* pyramid, d3m_stream_t stream) {
+    UvMip mp;
+    if (!image || !pyramid || misaligned4(image) || misaligned4(pyramid)) return D3M_ERR_INVALID;
+    if (!uv_texture_sizes_ok(image_batch, image_height, image_width, num_channels)) return D3M_ERR_INVALID;
+    if (!uv_mip_ok(image_height, image_width, levels, 0.0f, mp)) return D3M_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned tiles = blocks_for(image_width, UVT_TILE) * blocks_for(image_height, UVT_TILE);
+    LAUNCH("k_texture_mip_tile", k_texture_mip_tile, dim3(tiles, image_batch), dim3(256), st, image, mp, image_height,
+           image_width, num_channels, pyramid);
+    if (levels > UVT_TILE_LEVELS)
+        LAUNCH("k_texture_mip_tail", k_texture_mip_tail, dim3(image_batch), dim3(UVT_TAIL_BLOCK), st, mp, image_height,
+               image_width, num_channels, pyramid);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_uv_texture_lod(const d3m_fragments* fragments, const float* faces_uv, int image_height, int image_width,
+                                  int texture_wrapping, int levels, float lod_bias, float* lod, d3m_stream_t stream) {
+    AttrMaps m;
+    UvTexture tx;
+    UvMip mp;
+    if (!lod || misaligned4(lod)) return D3M_ERR_INVALID;
+    if (!uv_texture_ok(fragments, faces_uv, 1, image_height, image_width, 1, texture_wrapping, m, tx)) return D3M_ERR_INVALID;
+    if (!uv_mip_ok(image_height, image_width, levels, lod_bias, mp)) return D3M_ERR_INVALID;
+    const long n_px = (long)m.B * m.S * m.S;
+    LAUNCH("k_uv_texture_lod", k_uv_texture_lod, dim3(blocks_for(n_px, 256)), dim3(256), (hipStream_t)stream, m, tx, mp, lod);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_uv_texture_mip_images(const d3m_fragments* fragments, const float* faces_uv, const float* pyramid,
+                                         int image_batch, int image_height, int image_width, int num_channels,
+                                         int texture_wrapping, int levels, float lod_bias, const float* background,
+                                         float* images, float* alpha, d3m_stream_t stream) {
+    AttrMaps m;
+    UvTexture tx;
+    UvMip mp;
+    if (!pyramid || !images || !alpha) return D3M_ERR_INVALID;
+    if (misaligned4(pyramid) || misaligned4(background) || misaligned4(images) || misaligned4(alpha)) return D3M_ERR_INVALID;
+    if (!uv_texture_ok(fragments, faces_uv, image_batch, image_height, image_width, num_channels, texture_wrapping, m, tx))
+        return D3M_ERR_INVALID;
+    if (!uv_mip_ok(image_height, image_width, levels, lod_bias, mp)) return D3M_ERR_INVALID;
+    const long n = (long)fragments->image_size * fragments->image_size;
+    LAUNCH("k_uv_texture_mip_images", k_uv_texture_mip_images, dim3(blocks_for(n, 256), m.B), dim3(256), (hipStream_t)stream, m,
+           tx, mp, pyramid, background, images, alpha);
+    return check_launch();
+}
+
+D3M_EXPORT size_t d3m_uv_texture_mip_images_scratch_bytes(int image_batch, int image_height, int image_width, int num_channels,
+                                                          int levels, int batch_size, int raster_size) {
+    UvMip mp;
+    if (d3m_uv_texture_images_scratch_bytes(image_batch, image_height, image_width, num_channels, batch_size, raster_size) == 0)
+        return 0;
+    if (!uv_mip_ok(image_height, image_width, levels, 0.0f, mp)) return 0;
+    return (size_t)image_batch * mp.T * num_channels * sizeof(long long) + (size_t)UVT_MAX_BLOCKS * sizeof(unsigned);
+}
+
+D3M_EXPORT int d3m_uv_texture_mip_images_backward(const d3m_fragments* fragments, const float* faces_uv,
+                                                  const float* grad_images, int image_batch, int image_height,
+                                                  int image_width, int num_channels, int texture_wrapping, int levels,
+                                                  float lod_bias, void* scratch, size_t scratch_bytes, float* grad_image,
+                                                  d3m_stream_t stream) {
+    AttrMaps m;
+    UvTexture tx;
+    UvMip mp;
+    if (!grad_images || !scratch || !grad_image) return D3M_ERR_INVALID;
+    if (misaligned4(grad_images) || misaligned4(grad_image) || ((uintptr_t)scratch & 7)) return D3M_ERR_INVALID;
+    if (!uv_texture_ok(fragments, faces_uv, image_batch, image_height, image_width, num_channels, texture_wrapping, m, tx))
+        return D3M_ERR_INVALID;
+    if (!uv_mip_ok(image_height, image_width, levels, lod_bias, mp)) return D3M_ERR_INVALID;
+    const size_t need = d3m_uv_texture_mip_images_scratch_bytes(image_batch, image_height, image_width, num_channels, levels,
+                                                                m.B, m.S);
+    if (need == 0 || scratch_bytes < need) return D3M_ERR_INVALID;      // (B S^2 beyond 2^32; a scratch that is too small)
+    const long n_acc = (long)image_batch * mp.T * num_channels;
+    const long n_out = (long)image_batch * image_height * image_width * num_channels;
+    const long s = fragments->image_size, n_g = (long)m.B * num_channels * s * s, n_px = (long)m.B * m.S * m.S;
+    const int frac = 62 - ceil_log2((unsigned long long)n_px);
+    unsigned long long* acc = (unsigned long long*)scratch;
+    unsigned* block_max = (unsigned*)(acc + n_acc);
+    hipStream_t st = (hipStream_t)stream;
+    const int n_max = (int)std::min(blocks_for(std::max(n_acc, n_g), 256), (unsigned)UVT_MAX_BLOCKS);
+    LAUNCH("k_uv_texture_images_clear_max", k_uv_texture_images_clear_max, dim3(n_max), dim3(256), st, grad_images, n_g,
+           m.aa ? 0.25f : 1.0f, acc, n_acc, block_max);
+    LAUNCH("k_uv_texture_mip_images_scatter", k_uv_texture_mip_images_scatter,
+           dim3(std::min(blocks_for(n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, m, tx, mp, grad_images,
+           (const unsigned*)block_max, n_max, frac, acc);
+    LAUNCH("k_uv_texture_mip_images_convert", k_uv_texture_mip_images_convert,
+           dim3(std::min(blocks_for(n_out, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)acc, mp,
+           image_batch, image_height, image_width, num_channels, (const unsigned*)block_max, n_max, frac, grad_image);
     return check_launch();
 }
 

@@ -56,24 +56,37 @@ struct UvtTaps {
     float w[4];
 };
 
-// the taps of internal pixel q (index into the batch's maps) of view b, owned by fn
-__device__ __forceinline__ void uvt_pixel_taps(const AttrMaps& m, const UvTexture& tx, int b, size_t q, int fn, UvtTaps& t) {
+struct UvtCorners {
+    float u[3], cx[3], cy[3];            // va_weights; the owner's wrapped corner uv (a fill_back copy: corners 2 - c)
+};
+
+// the level-0 position of internal pixel q (index into the batch's maps) owned by fn, whose corner depths are z[0..2]: the
+// one statement of pos for this node and for the mip-mapped one (d3m_uv_texture_mip.h), which also reads the corners
+__device__ __forceinline__ void uvt_pixel_position(const AttrMaps& m, const UvTexture& tx, size_t q, int fn, const float* z,
+                                                   UvtCorners& k, float& pos_x, float& pos_y) {
     const bool back = fn >= m.Ft;
     const float* uvf = tx.faces_uv + (size_t)(back ? fn - m.Ft : fn) * 6;
-    const float* face = m.faces + ((size_t)b * m.Fp + fn) * 9;
-    const float z[3] = {face[2], face[5], face[8]};
-    float u[3], cx[3], cy[3];
-    va_weights(m, q, z, u);
+    va_weights(m, q, z, k.u);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         const int cc = back ? 2 - c : c;
-        cx[c] = wrap_uv(uvf[2 * cc], tx.wrapping);
-        cy[c] = wrap_uv(uvf[2 * cc + 1], tx.wrapping);
+        k.cx[c] = wrap_uv(uvf[2 * cc], tx.wrapping);
+        k.cy[c] = wrap_uv(uvf[2 * cc + 1], tx.wrapping);
     }
-    const float pu = (u[0] * cx[0] + u[1] * cx[1]) + u[2] * cx[2];
-    const float pv = (u[0] * cy[0] + u[1] * cy[1]) + u[2] * cy[2];
+    const float pu = (k.u[0] * k.cx[0] + k.u[1] * k.cx[1]) + k.u[2] * k.cx[2];
+    const float pv = (k.u[0] * k.cy[0] + k.u[1] * k.cy[1]) + k.u[2] * k.cy[2];
     const float x_max = (float)(tx.W - 1), y_max = (float)(tx.H - 1);
-    const float pos_x = fminf(fmaxf(pu * x_max, 0.0f), x_max), pos_y = fminf(fmaxf(pv * y_max, 0.0f), y_max);
+    pos_x = fminf(fmaxf(pu * x_max, 0.0f), x_max);
+    pos_y = fminf(fmaxf(pv * y_max, 0.0f), y_max);
+}
+
+// the taps of internal pixel q of view b, owned by fn
+__device__ __forceinline__ void uvt_pixel_taps(const AttrMaps& m, const UvTexture& tx, int b, size_t q, int fn, UvtTaps& t) {
+    const float* face = m.faces + ((size_t)b * m.Fp + fn) * 9;
+    const float z[3] = {face[2], face[5], face[8]};
+    UvtCorners k;
+    float pos_x, pos_y;
+    uvt_pixel_position(m, tx, q, fn, z, k, pos_x, pos_y);
     TexelTaps tt;
     bilinear_taps(pos_x, pos_y, tx.H, tx.W, tt);
 #pragma unroll

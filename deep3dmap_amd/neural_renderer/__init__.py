@@ -12,7 +12,7 @@ from .rasterize import (Rasterize, RasterizeFunction, rasterize, rasterize_depth
                         rasterize_silhouettes)
 from .renderer import Renderer
 from .smooth_shading import SHLight, sh_basis, sh_vertex_colors, vertex_normals
-from .uv_texture_images import sample_uv_texture
+from .uv_texture_images import sample_uv_texture, texture_mip_pyramid, uv_texture_lod
 from .uv_textures import UVTextures, textures_from_image
 from .vertex_colors import VertexColors, textures_from_vertex_colors
 

@@ -218,11 +218,12 @@ class Renderer(nn.Module):
         return _attributes.interpolate_vertex_attributes(attributes, fr, background)
 
     def render_uv_texture(self, vertices, faces, image, faces_uv, texture_wrapping='REPEAT', background=None, K=None, R=None,
-                          t=None, dist_coeffs=None, orig_size=None):
+                          t=None, dist_coeffs=None, orig_size=None, mipmap=None, lod_bias=0.0):
         """(images [B,C,s,s], alpha [B,s,s]) of a texture image [H,W,C] or [B,H,W,C] looked up at every pixel's interpolated
-        uv (faces_uv [F,3,2]): fragments() followed by sample_uv_texture, differentiable in the image only."""
+        uv (faces_uv [F,3,2]): fragments() followed by sample_uv_texture, differentiable in the image only.  mipmap, lod_bias:
+        sample_uv_texture's (a trilinear lookup in a box pyramid of the image)."""
         fr = self.fragments(vertices, faces, K, R, t, dist_coeffs, orig_size)
-        return _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background)
+        return _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background, mipmap, lod_bias)
 
     def render_rgb_image_grid(self, vertices, image, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         """render_rgb of the grid mesh of a depth map (vertices [B,h*w,3], one per pixel, row-major) textured by `image`

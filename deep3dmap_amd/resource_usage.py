@@ -24,8 +24,19 @@ def _demangle(names):
 
 def kernel_resource_usage(extra_flags=()):
     """{demangled kernel name: {"vgprs", "sgprs", "agprs", "scratch", "occupancy", "vgpr_spill", "sgpr_spill", "lds"}}
-    for the product build's flags (+ extra_flags)."""
+    for the product build's flags (+ extra_flags).  One compilation per process, compiler, flags and state of the sources."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    sources = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))]
+    key = (hipcc, tuple(HIPCC_FLAGS), tuple(extra_flags), tuple((f, os.path.getmtime(f)) for f in sources))
+    if key not in _tables:
+        _tables[key] = _compile_table(hipcc, extra_flags)
+    return {name: dict(row) for name, row in _tables[key].items()}
+
+
+_tables = {}
+
+
+def _compile_table(hipcc, extra_flags):
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ([hipcc] + HIPCC_FLAGS + list(extra_flags) + ["-Rpass-analysis=kernel-resource-usage"] +
                [os.path.join(CSRC, s) for s in SOURCES] + ["-o", os.path.join(tmp, "lib.so")])

@@ -1084,6 +1084,41 @@ int d3m_uv_texture_images_backward(const d3m_fragments* fragments, const float* 
                                    int image_batch, int image_height, int image_width, int num_channels,
                                    int texture_wrapping, void* scratch, size_t scratch_bytes, float* grad_image,
                                    d3m_stream_t stream);
+/* Mip-mapped per-pixel uv texture images (an addition; csrc/d3m_uv_texture_mip.h states the semantics).  `levels` = L, the
+ * number of levels above level 0, 1 <= L <= 15, image_height and image_width divisible by 2^L; T = sum over l = 0..L of
+ * (H >> l)(W >> l) texels per image.
+ * d3m_texture_mip_pyramid WRITES every element of pyramid [image_batch, T, C]: level 0 is the image, a texel of level l + 1 is
+ * (((a00 + a01) + a10) + a11) * 0.25 of its four children.  One launch (k_texture_mip_tile), two when L > 5
+ * (k_texture_mip_tail).  D3M_ERR_INVALID, before any launch: a NULL or misaligned image / pyramid, image_batch not in
+ * [1, 65535], H or W not in [1, 32768] or not divisible by 2^L, C not in [1, 64], L not in [1, 15]. */
+int d3m_texture_mip_pyramid(const float* image, int image_batch, int image_height, int image_width, int num_channels,
+                            int levels, float* pyramid, d3m_stream_t stream);
+/* The level of detail lambda_c of every internal pixel of the record, lod [B, S, S] in map orientation (S the raster size), 0
+ * where uncovered; every element WRITTEN.  One launch (k_uv_texture_lod).  D3M_ERR_INVALID, before any launch: what
+ * d3m_uv_texture_images refuses of the record, faces_uv, the sizes and the wrapping, what d3m_texture_mip_pyramid refuses of
+ * H, W and L, a lod_bias that is not finite, a NULL or misaligned lod. */
+int d3m_uv_texture_lod(const d3m_fragments* fragments, const float* faces_uv, int image_height, int image_width,
+                       int texture_wrapping, int levels, float lod_bias, float* lod, d3m_stream_t stream);
+/* d3m_uv_texture_images with a trilinear lookup in `pyramid` (d3m_texture_mip_pyramid's, [image_batch, T, C]) at the level
+ * lambda_c.  WRITES every element of images and alpha.  One launch (k_uv_texture_mip_images).  D3M_ERR_INVALID, before any
+ * launch: what d3m_uv_texture_images and d3m_uv_texture_lod refuse. */
+int d3m_uv_texture_mip_images(const d3m_fragments* fragments, const float* faces_uv, const float* pyramid, int image_batch,
+                              int image_height, int image_width, int num_channels, int texture_wrapping, int levels,
+                              float lod_bias, const float* background, float* images, float* alpha, d3m_stream_t stream);
+/* Bytes of scratch the mip-mapped adjoint needs: image_batch T C int64 accumulators (one per element of every level) and
+ * 1024 block maxima.  0 for sizes the adjoint refuses. */
+size_t d3m_uv_texture_mip_images_scratch_bytes(int image_batch, int image_height, int image_width, int num_channels,
+                                               int levels, int batch_size, int raster_size);
+/* The adjoint with respect to the image (level 0): grad_images -> grad_image [image_batch, H, W, C], every element WRITTEN,
+ * the same bits whatever the order of arrival: d3m_uv_texture_images_backward's number format with accumulators on every
+ * level; the conversion gathers an element's accumulator and its ancestors' in level order, in double.  The pyramid is not
+ * read.  Three launches (k_uv_texture_images_clear_max, k_uv_texture_mip_images_scatter, k_uv_texture_mip_images_convert).
+ * D3M_ERR_INVALID, before any launch: what d3m_uv_texture_mip_images refuses, NULL grad_images / scratch / grad_image, a
+ * misaligned scratch, B S S beyond 2^32, scratch_bytes below d3m_uv_texture_mip_images_scratch_bytes(). */
+int d3m_uv_texture_mip_images_backward(const d3m_fragments* fragments, const float* faces_uv, const float* grad_images,
+                                       int image_batch, int image_height, int image_width, int num_channels,
+                                       int texture_wrapping, int levels, float lod_bias, void* scratch, size_t scratch_bytes,
+                                       float* grad_image, d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
