@@ -17,6 +17,7 @@
 #include "d3m_attributes.h"
 #include "d3m_uv_texture.h"
 #include "d3m_uv_texture_mip.h"
+#include "d3m_fragment_geometry.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -2778,6 +2779,96 @@ D3M_EXPORT int d3m_uv_texture_mip_images_backward(const d3m_fragments* fragments
     LAUNCH("k_uv_texture_mip_images_convert", k_uv_texture_mip_images_convert,
            dim3(std::min(blocks_for(n_out, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)acc, mp,
            image_batch, image_height, image_width, num_channels, (const unsigned*)block_max, n_max, frac, grad_image);
+    return check_launch();
+}
+
+// The interior geometry gradient of everything drawn over a coverage record (d3m_fragment_geometry.h).
+// What the entry points refuse of the record; `m`: what the kernels read.  One lane per internal pixel: B S S within 2^32.
+static bool fragment_geometry_ok(const d3m_fragments* fr, int num_vertices, AttrMaps& m) {
+    if (!fragments_ok(fr, 1, num_vertices, 1, m)) return false;
+    return (unsigned long long)m.B * m.S * m.S <= (1ull << 32);
+}
+
+D3M_EXPORT int d3m_fragment_weights(const d3m_fragments* fragments, float* weights, d3m_stream_t stream) {
+    AttrMaps m;
+    if (!weights || misaligned4(weights)) return D3M_ERR_INVALID;
+    if (!fragment_geometry_ok(fragments, 1, m)) return D3M_ERR_INVALID;
+    const long n_px = (long)m.B * m.S * m.S;
+    LAUNCH("k_fragment_weights", k_fragment_weights, dim3(blocks_for(n_px, 256)), dim3(256), (hipStream_t)stream, m, weights);
+    return check_launch();
+}
+
+D3M_EXPORT size_t d3m_fragment_geometry_scratch_floats(int batch_size, int num_faces, int raster_size,
+                                                       const d3m_csr* adjacency, int with_pixel_grads) {
+    if (raster_size < 1 || raster_size > 32768 || (unsigned long long)std::max(batch_size, 0) * raster_size * raster_size > (1ull << 32))
+        return 0;
+    const size_t sums = d3m_vertex_attribute_scratch_floats(batch_size, num_faces, 3, adjacency);
+    if (sums == 0) return 0;
+    return sums + (with_pixel_grads ? (size_t)batch_size * raster_size * raster_size * 3 : 0);
+}
+
+D3M_EXPORT int d3m_vertex_attribute_pixel_grads(const d3m_fragments* fragments, const float* attributes, int attributes_batch,
+                                                int num_vertices, int num_channels, const float* grad_images,
+                                                float* pixel_grads, d3m_stream_t stream) {
+    AttrMaps m;
+    if (!attributes || !grad_images || !pixel_grads) return D3M_ERR_INVALID;
+    if (!fragments_ok(fragments, attributes_batch, num_vertices, num_channels, m)) return D3M_ERR_INVALID;
+    if ((unsigned long long)m.B * m.S * m.S > (1ull << 32)) return D3M_ERR_INVALID;
+    const long n_px = (long)m.B * m.S * m.S;
+    LAUNCH("k_vertex_attribute_pixel_grads", k_vertex_attribute_pixel_grads, dim3(blocks_for(n_px, 256)), dim3(256),
+           (hipStream_t)stream, m, attributes, attributes_batch, num_vertices, num_channels, grad_images, pixel_grads);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_uv_texture_pixel_grads(const d3m_fragments* fragments, const float* faces_uv, const float* image,
+                                          int image_batch, int image_height, int image_width, int num_channels,
+                                          int texture_wrapping, const float* grad_images, float* pixel_grads,
+                                          d3m_stream_t stream) {
+    AttrMaps m;
+    UvTexture tx;
+    if (!image || !grad_images || !pixel_grads) return D3M_ERR_INVALID;
+    if (misaligned4(image) || misaligned4(grad_images) || misaligned4(pixel_grads)) return D3M_ERR_INVALID;
+    if (!uv_texture_ok(fragments, faces_uv, image_batch, image_height, image_width, num_channels, texture_wrapping, m, tx))
+        return D3M_ERR_INVALID;
+    if ((unsigned long long)m.B * m.S * m.S > (1ull << 32)) return D3M_ERR_INVALID;
+    const long n_px = (long)m.B * m.S * m.S;
+    LAUNCH("k_uv_texture_pixel_grads", k_uv_texture_pixel_grads, dim3(blocks_for(n_px, 256)), dim3(256), (hipStream_t)stream, m,
+           tx, image, grad_images, pixel_grads);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_fragment_geometry_backward(const d3m_fragments* fragments, const float* pixel_grads,
+                                              const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
+                                              float* grad_screen_vertices, int num_vertices, d3m_stream_t stream) {
+    AttrMaps m;
+    if (!pixel_grads || !scratch || !grad_screen_vertices) return D3M_ERR_INVALID;
+    if (misaligned4(pixel_grads) || misaligned4(scratch) || misaligned4(grad_screen_vertices)) return D3M_ERR_INVALID;
+    if (!fragment_geometry_ok(fragments, num_vertices, m)) return D3M_ERR_INVALID;
+    if ((long)m.Ft * 3 > 0x7FFFFFFFl) return D3M_ERR_INVALID;          // items are int32
+    const long nf = (long)m.B * m.Fp;
+    if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
+    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if (scratch_floats < d3m_fragment_geometry_scratch_floats(m.B, m.Fp, m.S, adjacency, 0)) return D3M_ERR_WORKSPACE;
+    const CsrRows adj = csr_rows(*adjacency);
+    const int num_chunks = adj.longs.n_chunks;
+    const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
+    float* Gv = scratch;
+    float* partials = Gv + (size_t)nf * 9;
+    hipStream_t st = (hipStream_t)stream;
+    // 1. per visible face: fixed grids striding over the visibility list (its length is only known on the device)
+    const unsigned small_blocks = std::min(blocks_for(nf, FM_FACES_PER_BLOCK), 2048u);
+    LAUNCH("k_fragment_geometry_face_sums", k_fragment_geometry_face_sums, dim3(small_blocks), dim3(256), st, m, pixel_grads,
+           (const int*)vis.list, (const int*)vis.count, Gv);
+    const unsigned large_blocks = std::min(blocks_for(nf, RG_BLOCK), 256u);
+    LAUNCH("k_fragment_geometry_large_face_sums", k_fragment_geometry_large_face_sums, dim3(large_blocks), dim3(RG_BLOCK), st, m,
+           pixel_grads, (const int*)vis.list, (const int*)vis.count, Gv);
+    // 2. per vertex and view, over the adjacency: stage 2 of the attribute adjoint with C = 3 (Gv has G's layout)
+    if (num_chunks > 0)
+        LAUNCH("k_vertex_attribute_adjoint_chunks", k_vertex_attribute_adjoint_chunks, dim3(num_chunks, m.B, 1), dim3(RG_BLOCK),
+               st, adj.items, adj.longs.chunks, num_chunks, (const float*)Gv, (const int*)vis.flags, m.Ft, m.Fp, 3, partials);
+    LAUNCH("k_vertex_attribute_adjoint_rows", k_vertex_attribute_adjoint_rows,
+           dim3(blocks_for((long)num_vertices * 3, 256), m.B), dim3(256), st, adj, (const float*)partials, (const float*)Gv,
+           (const int*)vis.flags, m.B, m.Ft, m.Fp, num_vertices, 3, 0, grad_screen_vertices);
     return check_launch();
 }
 

@@ -2,6 +2,7 @@
 (pnpmodules/neural_renderer/neural_renderer/__init__.py:1-12)."""
 from .attributes import Fragments, interpolate_vertex_attributes, rasterize_fragments
 from .cameras import get_points_from_angles, look, look_at, perspective, projection
+from .fragment_geometry import fragment_weights
 from .mesh_ops import lighting, vertices_to_faces
 from .mesh_regularizers import (MeshRegularizer, edge_length_loss, laplacian_loss, mesh_regularizer, mesh_topology,
                                normal_consistency_loss)

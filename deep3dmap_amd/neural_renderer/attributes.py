@@ -10,7 +10,11 @@ that map with its rows reversed and, with anti-aliasing, 2x2-averaged -- what ra
 The adjoint is a gather in a fixed order (csrc/d3m_attributes.h states it): per visible face the sums over the pixels it owns
 (scan_owned_pixels; a workgroup for a face whose box exceeds 4096 pixels), stored plainly in a per-face scratch, then per
 vertex over the CSR adjacency of the faces (row_gather.vertex_adjacency: the one textures_from_vertex_colors walks), hub
-vertices through the long-row chunks.  No float atomics, nothing cleared, the same bits on every run."""
+vertices through the long-row chunks.  No float atomics, nothing cleared, the same bits on every run.
+
+The record stays a constant, but with `screen_vertices=` the node also returns the INTERIOR geometry gradient -- the
+derivative of the weights u_c with respect to the owner's screen-space corners -- through the shared adjoint of
+csrc/d3m_fragment_geometry.h (fragment_geometry.py); the helpers of that adjoint live here, next to the record."""
 import ctypes
 from typing import NamedTuple
 
@@ -140,6 +144,35 @@ def _checked_background(background, C, attributes):
     return const_tensor([float(x) for x in values], attributes.device)
 
 
+def _attribute_images_launch(fr, attr, background):
+    """(images, alpha) of contiguous attributes: the forward's one launch"""
+    batched = attr.dim() == 3
+    V, C = attr.shape[-2:]
+    B, s = fr.face_index_map.shape[0], int(fr.image_size)
+    images = torch.empty(B, C, s, s, dtype=torch.float32, device=attr.device)
+    alpha = torch.empty(B, s, s, dtype=torch.float32, device=attr.device)
+    c_fr = fr.c_struct()
+    _lib.check(_lib.lib().d3m_vertex_attribute_images(ctypes.byref(c_fr), _lib.ptr(attr), B if batched else 1, V, C,
+                                                      _lib.ptr(background), _lib.ptr(images), _lib.ptr(alpha),
+                                                      _lib.stream_ptr()), "d3m_vertex_attribute_images")
+    return images, alpha
+
+
+def _attribute_images_adjoint(fr, A, g, batched, sizes):
+    """grad_attributes of the contiguous f32 image gradient g: the fixed-order gather"""
+    B, V, C = sizes
+    L = _lib.lib()
+    Fp = fr.faces.shape[1]
+    n = int(L.d3m_vertex_attribute_scratch_floats(B, Fp, C, ctypes.byref(A.csr.c)))
+    scratch = torch.empty(n, dtype=torch.float32, device=g.device)
+    grad = torch.empty((B, V, C) if batched else (V, C), dtype=torch.float32, device=g.device)
+    c_fr = fr.c_struct()
+    _lib.check(L.d3m_vertex_attribute_images_backward(ctypes.byref(c_fr), _lib.ptr(g), ctypes.byref(A.csr.c),
+                                                      _lib.ptr(scratch), n, _lib.ptr(grad), B if batched else 1, V, C,
+                                                      _lib.stream_ptr()), "d3m_vertex_attribute_images_backward")
+    return grad
+
+
 class _VertexAttributeImages(torch.autograd.Function):
     @staticmethod
     def forward(ctx, attributes, fragments, adjacency, background):
@@ -147,14 +180,74 @@ class _VertexAttributeImages(torch.autograd.Function):
         attr = attributes.contiguous()
         batched = attr.dim() == 3
         V, C = attr.shape[-2:]
-        B, s = fr.face_index_map.shape[0], int(fr.image_size)
-        images = torch.empty(B, C, s, s, dtype=torch.float32, device=attr.device)
-        alpha = torch.empty(B, s, s, dtype=torch.float32, device=attr.device)
-        c_fr = fr.c_struct()
-        _lib.check(_lib.lib().d3m_vertex_attribute_images(ctypes.byref(c_fr), _lib.ptr(attr), B if batched else 1, V, C,
-                                                          _lib.ptr(background), _lib.ptr(images), _lib.ptr(alpha),
-                                                          _lib.stream_ptr()), "d3m_vertex_attribute_images")
-        ctx.fragments, ctx.adjacency, ctx.batched, ctx.sizes = fr, adjacency, batched, (B, V, C)
+        images, alpha = _attribute_images_launch(fr, attr, background)
+        ctx.fragments, ctx.adjacency, ctx.batched, ctx.sizes = fr, adjacency, batched, (images.shape[0], V, C)
+        ctx.mark_non_differentiable(alpha)
+        return images, alpha
+
+    @staticmethod
+    def backward(ctx, grad_images, _grad_alpha):
+        g = grad_images.to(torch.float32).contiguous()
+        return _attribute_images_adjoint(ctx.fragments, ctx.adjacency, g, ctx.batched, ctx.sizes), None, None, None
+
+
+# ---- the interior geometry gradient (csrc/d3m_fragment_geometry.h) ----------------------------------------------------------
+MAX_PIXEL_TERMS = 1 << 32  # B S S: one lane per internal pixel
+
+
+def _checked_screen_vertices(screen_vertices, fragments, who):
+    """The screen vertices a node differentiates in: [B,V,3] f32 on the record's device, V the record's.  That they are the
+    vertices the record was rasterised from cannot be checked: the caller's business."""
+    B = fragments.face_index_map.shape[0]
+    if not torch.is_tensor(screen_vertices) or screen_vertices.dim() != 3 or screen_vertices.shape[-1] != 3:
+        raise ValueError(f"{who}: screen_vertices must be [B, num_vertices, 3]")
+    if screen_vertices.dtype != torch.float32:
+        raise ValueError(f"{who}: screen_vertices must be float32")
+    if screen_vertices.shape[0] != B:
+        raise ValueError(f"{who}: screen_vertices must be [{B}, V, 3] for fragments of {B} views")
+    if screen_vertices.shape[1] != fragments.num_vertices:
+        raise ValueError(f"{who}: screen_vertices have {screen_vertices.shape[1]} vertices, the fragments were rasterised "
+                         f"from {fragments.num_vertices}")
+    if screen_vertices.device != fragments.face_index_map.device:
+        raise ValueError(f"{who}: screen_vertices must be on the fragments' device")
+    if B * fragments.raster_size ** 2 > MAX_PIXEL_TERMS:
+        raise ValueError(f"{who}: B S S = {B * fragments.raster_size ** 2} is beyond 2^32")
+
+
+def _geometry_scratch(fr, A, with_pixel_grads):
+    """(pixel_grads [B,S,S,3] or None, the adjoint's scratch): one uninitialised buffer"""
+    B, S, Fp = fr.face_index_map.shape[0], fr.raster_size, fr.faces.shape[1]
+    n = int(_lib.lib().d3m_fragment_geometry_scratch_floats(B, Fp, S, ctypes.byref(A.csr.c), int(with_pixel_grads)))
+    scratch = torch.empty(n, dtype=torch.float32, device=fr.face_index_map.device)
+    if not with_pixel_grads:
+        return None, scratch
+    n_h = B * S * S * 3
+    return scratch[:n_h].view(B, S, S, 3), scratch[n_h:]
+
+
+def _geometry_adjoint(fr, A, pixel_grads, scratch):
+    """grad_screen_vertices [B,V,3] of contiguous f32 pixel_grads [B,S,S,3] = dL/du: the shared fixed-order adjoint"""
+    B, V = fr.face_index_map.shape[0], int(fr.num_vertices)
+    grad = torch.empty(B, V, 3, dtype=torch.float32, device=pixel_grads.device)
+    c_fr = fr.c_struct()
+    _lib.check(_lib.lib().d3m_fragment_geometry_backward(ctypes.byref(c_fr), _lib.ptr(pixel_grads), ctypes.byref(A.csr.c),
+                                                         _lib.ptr(scratch), scratch.numel(), _lib.ptr(grad), V,
+                                                         _lib.stream_ptr()), "d3m_fragment_geometry_backward")
+    return grad
+
+
+class _VertexAttributeImagesGeometry(torch.autograd.Function):
+    """_VertexAttributeImages with the screen vertices as a second differentiable input: the same forward launch and the
+    same adjoint for the attributes; the vertices' gradient through the node's pixel_grads and the shared adjoint."""
+    @staticmethod
+    def forward(ctx, attributes, screen_vertices, fragments, adjacency, background):
+        fr = fragments
+        attr = attributes.contiguous()
+        batched = attr.dim() == 3
+        V, C = attr.shape[-2:]
+        images, alpha = _attribute_images_launch(fr, attr, background)
+        ctx.save_for_backward(attr)
+        ctx.fragments, ctx.adjacency, ctx.batched, ctx.sizes = fr, adjacency, batched, (images.shape[0], V, C)
         ctx.mark_non_differentiable(alpha)
         return images, alpha
 
@@ -162,26 +255,35 @@ class _VertexAttributeImages(torch.autograd.Function):
     def backward(ctx, grad_images, _grad_alpha):
         fr, A = ctx.fragments, ctx.adjacency
         B, V, C = ctx.sizes
-        L = _lib.lib()
+        attr, = ctx.saved_tensors
         g = grad_images.to(torch.float32).contiguous()
-        Fp = fr.faces.shape[1]
-        n = int(L.d3m_vertex_attribute_scratch_floats(B, Fp, C, ctypes.byref(A.csr.c)))
-        scratch = torch.empty(n, dtype=torch.float32, device=g.device)
-        grad = torch.empty((B, V, C) if ctx.batched else (V, C), dtype=torch.float32, device=g.device)
-        c_fr = fr.c_struct()
-        _lib.check(L.d3m_vertex_attribute_images_backward(ctypes.byref(c_fr), _lib.ptr(g), ctypes.byref(A.csr.c),
-                                                          _lib.ptr(scratch), n, _lib.ptr(grad), B if ctx.batched else 1, V, C,
-                                                          _lib.stream_ptr()), "d3m_vertex_attribute_images_backward")
-        return grad, None, None, None
+        grad_attr = _attribute_images_adjoint(fr, A, g, ctx.batched, ctx.sizes) if ctx.needs_input_grad[0] else None
+        grad_sv = None
+        if ctx.needs_input_grad[1]:
+            h, scratch = _geometry_scratch(fr, A, True)
+            c_fr = fr.c_struct()
+            _lib.check(_lib.lib().d3m_vertex_attribute_pixel_grads(ctypes.byref(c_fr), _lib.ptr(attr), B if ctx.batched else 1,
+                                                                   V, C, _lib.ptr(g), _lib.ptr(h), _lib.stream_ptr()),
+                       "d3m_vertex_attribute_pixel_grads")
+            grad_sv = _geometry_adjoint(fr, A, h, scratch)
+        return grad_attr, grad_sv, None, None, None
 
 
-def interpolate_vertex_attributes(attributes, fragments, background=None, cache=None):
+def interpolate_vertex_attributes(attributes, fragments, background=None, cache=None, screen_vertices=None):
     """(images [B,C,s,s], alpha [B,s,s]) of attributes [V,C] (shared by the views) or [B,V,C], f32 on the record's device,
     1 <= C <= 1024, over a Fragments record; background: None (zeros), a float, or [C].  Differentiable in `attributes`
     only; alpha is the coverage (the bits of render_silhouettes), not differentiable.  The first call with the record's tri
     builds the faces' adjacency (outside any stream capture; a ValueError for an index outside [0, V)) and later calls reuse
     it; `cache`: the AdjacencyCache to keep it in (default: row_gather's).  ValueError, before anything is launched, for a
-    wrong rank, dtype, device, V, C, batch or background."""
+    wrong rank, dtype, device, V, C, batch or background.
+
+    screen_vertices None: as above.  screen_vertices [B,V,3] f32 on the record's device -- THE vertices the record was
+    rasterised from, still attached to the graph (their values cannot be checked; shape, dtype, device and V are): the same
+    forward launch and the same bits of images, alpha and the attributes' gradient, and in addition the INTERIOR geometry
+    gradient reaches screen_vertices.grad: the derivative of the weights u_c of every owned pixel with respect to the
+    owner's corners (csrc/d3m_fragment_geometry.h), in a fixed order.  Coverage stays a constant -- no gradient from a
+    pixel changing its owner or from the silhouette, which render_silhouettes / render give.  Vertices that do not require
+    grad launch nothing extra."""
     if not torch.is_tensor(attributes) or attributes.dim() not in (2, 3):
         raise ValueError("attributes must be [num_vertices, C] or [B, num_vertices, C]")
     if attributes.dtype != torch.float32:
@@ -196,8 +298,12 @@ def interpolate_vertex_attributes(attributes, fragments, background=None, cache=
         raise ValueError(f"attributes must be [V, C] or [{B}, V, C] for fragments of {B} views")
     if attributes.device != fragments.face_index_map.device:
         raise ValueError("attributes must be on the fragments' device")
+    if screen_vertices is not None:
+        _checked_screen_vertices(screen_vertices, fragments, "interpolate_vertex_attributes")
     background = _checked_background(background, C, attributes)
     adjacency = vertex_adjacency(fragments.tri, V, cache)          # (where tri's indices are checked against V)
     if not attributes.is_cuda:
         raise ValueError("attributes and fragments must be on one GPU device")
+    if screen_vertices is not None and screen_vertices.requires_grad and torch.is_grad_enabled():
+        return _VertexAttributeImagesGeometry.apply(attributes, screen_vertices, fragments, adjacency, background)
     return _VertexAttributeImages.apply(attributes, fragments, adjacency, background)

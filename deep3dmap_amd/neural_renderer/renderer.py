@@ -211,17 +211,41 @@ class Renderer(nn.Module):
                                                self.far)
 
     def render_attributes(self, vertices, faces, attributes, background=None, K=None, R=None, t=None, dist_coeffs=None,
-                          orig_size=None):
+                          orig_size=None, geometry_grad=False):
         """(images [B,C,s,s], alpha [B,s,s]) of per-vertex attributes [V,C] or [B,V,C]: fragments() followed by
-        interpolate_vertex_attributes, differentiable in the attributes only."""
+        interpolate_vertex_attributes, differentiable in the attributes only.  geometry_grad=True: the screen vertices stay
+        in the graph (the record is made from their detached values) and are passed on as interpolate_vertex_attributes'
+        screen_vertices, so the INTERIOR geometry gradient reaches `vertices` and any learnable camera tensor through the
+        camera operators; coverage stays a constant (the silhouette gradient is render_silhouettes' / render's)."""
+        if geometry_grad:
+            fr, sv = self._fragments_with_vertices(vertices, faces, K, R, t, dist_coeffs, orig_size)
+            return _attributes.interpolate_vertex_attributes(attributes, fr, background, screen_vertices=sv)
         fr = self.fragments(vertices, faces, K, R, t, dist_coeffs, orig_size)
         return _attributes.interpolate_vertex_attributes(attributes, fr, background)
 
+    def _fragments_with_vertices(self, vertices, faces, K, R, t, dist_coeffs, orig_size):
+        """(the coverage record of the detached screen vertices, the screen vertices in the graph)"""
+        sv = self._transform(vertices, K, R, t, dist_coeffs, orig_size)
+        fr = _attributes.rasterize_fragments(sv.detach(), faces, self.image_size, self.anti_aliasing, self.fill_back, self.near,
+                                             self.far)
+        return fr, sv
+
     def render_uv_texture(self, vertices, faces, image, faces_uv, texture_wrapping='REPEAT', background=None, K=None, R=None,
-                          t=None, dist_coeffs=None, orig_size=None, mipmap=None, lod_bias=0.0):
+                          t=None, dist_coeffs=None, orig_size=None, mipmap=None, lod_bias=0.0, geometry_grad=False):
         """(images [B,C,s,s], alpha [B,s,s]) of a texture image [H,W,C] or [B,H,W,C] looked up at every pixel's interpolated
         uv (faces_uv [F,3,2]): fragments() followed by sample_uv_texture, differentiable in the image only.  mipmap, lod_bias:
-        sample_uv_texture's (a trilinear lookup in a box pyramid of the image)."""
+        sample_uv_texture's (a trilinear lookup in a box pyramid of the image).  geometry_grad=True: as in
+        render_attributes -- the interior geometry gradient reaches `vertices` and learnable camera tensors; plain bilinear
+        lookup only (NotImplementedError with mipmap, raised before anything is launched), faces_uv and coverage stay
+        constants."""
+        if geometry_grad:
+            if torch.is_tensor(image) and image.dim() >= 3 and _uv_texture_images.mip_levels(*image.shape[-3:-1], mipmap):
+                # known from the arguments alone: refused before the camera operators and the rasteriser launch
+                raise NotImplementedError("render_uv_texture: no geometry gradient with mipmap (the level of detail depends "
+                                          "on the geometry); pass mipmap=None or geometry_grad=False")
+            fr, sv = self._fragments_with_vertices(vertices, faces, K, R, t, dist_coeffs, orig_size)
+            return _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background, mipmap, lod_bias,
+                                                        screen_vertices=sv)
         fr = self.fragments(vertices, faces, K, R, t, dist_coeffs, orig_size)
         return _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background, mipmap, lod_bias)
 

@@ -26,7 +26,9 @@ import ctypes
 import torch
 
 from .. import _lib
-from .attributes import _checked_background, _checked_fragments
+from .attributes import (_checked_background, _checked_fragments, _checked_screen_vertices, _geometry_adjoint,
+                         _geometry_scratch)
+from .row_gather import vertex_adjacency
 from .uv_textures import _wrapping_code
 
 MAX_CHANNELS = 64          # UVT_MAX_CHANNELS of csrc/d3m_uv_texture.h
@@ -47,39 +49,83 @@ def uv_adjoint_fraction_bits(B, S):
     return 62 - (n - 1).bit_length()
 
 
+def _uv_images_launch(fr, img, faces_uv, wrapping, background):
+    """(images, alpha) of a contiguous image: the plain bilinear forward's one launch"""
+    batched = img.dim() == 4
+    H, W, C = img.shape[-3:]
+    B, s = fr.face_index_map.shape[0], int(fr.image_size)
+    images = torch.empty(B, C, s, s, dtype=torch.float32, device=img.device)
+    alpha = torch.empty(B, s, s, dtype=torch.float32, device=img.device)
+    c_fr = fr.c_struct()
+    _lib.check(_lib.lib().d3m_uv_texture_images(ctypes.byref(c_fr), _lib.ptr(faces_uv), _lib.ptr(img), B if batched else 1,
+                                                H, W, C, wrapping, _lib.ptr(background), _lib.ptr(images), _lib.ptr(alpha),
+                                                _lib.stream_ptr()), "d3m_uv_texture_images")
+    return images, alpha
+
+
+def _uv_images_adjoint(fr, faces_uv, wrapping, g, batched, sizes):
+    """grad_image of the contiguous f32 image gradient g: the fixed-point scatter"""
+    B, H, W, C = sizes
+    L = _lib.lib()
+    ib = B if batched else 1
+    n = int(L.d3m_uv_texture_images_scratch_bytes(ib, H, W, C, B, fr.raster_size))
+    scratch = torch.empty((n + 7) // 8, dtype=torch.int64, device=g.device)
+    grad = torch.empty((B, H, W, C) if batched else (H, W, C), dtype=torch.float32, device=g.device)
+    c_fr = fr.c_struct()
+    _lib.check(L.d3m_uv_texture_images_backward(ctypes.byref(c_fr), _lib.ptr(faces_uv), _lib.ptr(g), ib, H, W, C, wrapping,
+                                                _lib.ptr(scratch), scratch.numel() * 8, _lib.ptr(grad), _lib.stream_ptr()),
+               "d3m_uv_texture_images_backward")
+    return grad
+
+
 class _UvTextureImages(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, faces_uv, fragments, wrapping, background):
-        fr = fragments
         img = image.contiguous()
-        batched = img.dim() == 4
-        H, W, C = img.shape[-3:]
-        B, s = fr.face_index_map.shape[0], int(fr.image_size)
-        images = torch.empty(B, C, s, s, dtype=torch.float32, device=img.device)
-        alpha = torch.empty(B, s, s, dtype=torch.float32, device=img.device)
-        c_fr = fr.c_struct()
-        _lib.check(_lib.lib().d3m_uv_texture_images(ctypes.byref(c_fr), _lib.ptr(faces_uv), _lib.ptr(img), B if batched else 1,
-                                                    H, W, C, wrapping, _lib.ptr(background), _lib.ptr(images), _lib.ptr(alpha),
-                                                    _lib.stream_ptr()), "d3m_uv_texture_images")
-        ctx.fragments, ctx.faces_uv, ctx.wrapping, ctx.batched, ctx.sizes = fr, faces_uv, wrapping, batched, (B, H, W, C)
+        images, alpha = _uv_images_launch(fragments, img, faces_uv, wrapping, background)
+        ctx.fragments, ctx.faces_uv, ctx.wrapping, ctx.batched = fragments, faces_uv, wrapping, img.dim() == 4
+        ctx.sizes = (images.shape[0],) + tuple(img.shape[-3:])
         ctx.mark_non_differentiable(alpha)
         return images, alpha
 
     @staticmethod
     def backward(ctx, grad_images, _grad_alpha):
-        fr = ctx.fragments
-        B, H, W, C = ctx.sizes
-        L = _lib.lib()
         g = grad_images.to(torch.float32).contiguous()
-        ib = B if ctx.batched else 1
-        n = int(L.d3m_uv_texture_images_scratch_bytes(ib, H, W, C, B, fr.raster_size))
-        scratch = torch.empty((n + 7) // 8, dtype=torch.int64, device=g.device)
-        grad = torch.empty((B, H, W, C) if ctx.batched else (H, W, C), dtype=torch.float32, device=g.device)
-        c_fr = fr.c_struct()
-        _lib.check(L.d3m_uv_texture_images_backward(ctypes.byref(c_fr), _lib.ptr(ctx.faces_uv), _lib.ptr(g), ib, H, W, C,
-                                                    ctx.wrapping, _lib.ptr(scratch), scratch.numel() * 8, _lib.ptr(grad),
-                                                    _lib.stream_ptr()), "d3m_uv_texture_images_backward")
-        return grad, None, None, None, None
+        return _uv_images_adjoint(ctx.fragments, ctx.faces_uv, ctx.wrapping, g, ctx.batched, ctx.sizes), None, None, None, None
+
+
+class _UvTextureImagesGeometry(torch.autograd.Function):
+    """_UvTextureImages with the screen vertices as a second differentiable input: the same forward launch and the same
+    adjoint for the image; the vertices' gradient through the node's pixel_grads and the shared interior adjoint
+    (csrc/d3m_fragment_geometry.h)."""
+    @staticmethod
+    def forward(ctx, image, screen_vertices, faces_uv, fragments, adjacency, wrapping, background):
+        img = image.contiguous()
+        images, alpha = _uv_images_launch(fragments, img, faces_uv, wrapping, background)
+        ctx.save_for_backward(img)
+        ctx.fragments, ctx.faces_uv, ctx.wrapping, ctx.batched = fragments, faces_uv, wrapping, img.dim() == 4
+        ctx.adjacency, ctx.sizes = adjacency, (images.shape[0],) + tuple(img.shape[-3:])
+        ctx.mark_non_differentiable(alpha)
+        return images, alpha
+
+    @staticmethod
+    def backward(ctx, grad_images, _grad_alpha):
+        fr, A = ctx.fragments, ctx.adjacency
+        B, H, W, C = ctx.sizes
+        img, = ctx.saved_tensors
+        g = grad_images.to(torch.float32).contiguous()
+        grad_image = None
+        if ctx.needs_input_grad[0]:
+            grad_image = _uv_images_adjoint(fr, ctx.faces_uv, ctx.wrapping, g, ctx.batched, ctx.sizes)
+        grad_sv = None
+        if ctx.needs_input_grad[1]:
+            h, scratch = _geometry_scratch(fr, A, True)
+            c_fr = fr.c_struct()
+            _lib.check(_lib.lib().d3m_uv_texture_pixel_grads(ctypes.byref(c_fr), _lib.ptr(ctx.faces_uv), _lib.ptr(img),
+                                                             B if ctx.batched else 1, H, W, C, ctx.wrapping, _lib.ptr(g),
+                                                             _lib.ptr(h), _lib.stream_ptr()), "d3m_uv_texture_pixel_grads")
+            grad_sv = _geometry_adjoint(fr, A, h, scratch)
+        return grad_image, grad_sv, None, None, None, None, None
 
 
 # ---- mip-mapping (csrc/d3m_uv_texture_mip.h) --------------------------------------------------------------------------------
@@ -175,7 +221,8 @@ class _UvTextureMipImages(torch.autograd.Function):
         return grad, None, None, None, None, None, None
 
 
-def sample_uv_texture(image, faces_uv, fragments, texture_wrapping='REPEAT', background=None, mipmap=None, lod_bias=0.0):
+def sample_uv_texture(image, faces_uv, fragments, texture_wrapping='REPEAT', background=None, mipmap=None, lod_bias=0.0,
+                      screen_vertices=None, cache=None):
     """(images [B,C,s,s], alpha [B,s,s]) of a texture image [H,W,C] (shared by the views) or [B,H,W,C], f32 on the record's
     device, 1 <= C <= 64, texture space as textures_from_image reads it; faces_uv [F,3,2] f32 for the record's F faces, a
     constant; texture_wrapping 'REPEAT', 'MIRRORED_REPEAT' or 'CLAMP_TO_EDGE' (or 0..2), applied to the corners; background:
@@ -188,8 +235,18 @@ def sample_uv_texture(image, faces_uv, fragments, texture_wrapping='REPEAT', bac
     step) + lod_bias, 0, L) -- no aliasing when the texture is minified, and the image's gradient reaches every texel under a
     pixel's footprint instead of four (csrc/d3m_uv_texture_mip.h).  lod_bias: a finite float.
 
+    screen_vertices None: as above.  screen_vertices [B,V,3] f32 on the record's device -- THE vertices the record was
+    rasterised from, still attached to the graph (their values cannot be checked; shape, dtype, device and V are): the same
+    forward launch and the same bits of images, alpha and the image's gradient, and in addition the INTERIOR geometry
+    gradient reaches screen_vertices.grad: the four taps' slope along pos times the derivative of the weights u_c with
+    respect to the owner's corners (csrc/d3m_fragment_geometry.h), in a fixed order.  Coverage stays a constant (the
+    silhouette gradient is render_silhouettes' / render's) and so does faces_uv.  Plain bilinear lookup only: with mipmap
+    the level of detail depends on the geometry, and NotImplementedError is raised.  Vertices that do not require grad
+    launch nothing extra; the first call with the record's tri builds the faces' adjacency (outside any stream capture;
+    `cache`: the AdjacencyCache to keep it in).
+
     ValueError / TypeError, before anything is launched, for a wrong rank, dtype, device, C, F, batch, wrapping, background,
-    mipmap or lod_bias, and for a record with B S S beyond 2^32."""
+    mipmap, lod_bias or screen_vertices, and for a record with B S S beyond 2^32."""
     if not torch.is_tensor(image) or not torch.is_tensor(faces_uv):
         raise TypeError("image and faces_uv must be tensors")
     if image.dtype != torch.float32 or faces_uv.dtype != torch.float32:
@@ -217,9 +274,20 @@ def sample_uv_texture(image, faces_uv, fragments, texture_wrapping='REPEAT', bac
         raise ValueError("image and faces_uv must be on the fragments' device")
     levels = mip_levels(H, W, mipmap)
     lod_bias = _checked_lod_bias(lod_bias)
+    adjacency = None
+    if screen_vertices is not None:
+        _checked_screen_vertices(screen_vertices, fragments, "sample_uv_texture")
+        if levels != 0:
+            raise NotImplementedError("sample_uv_texture: no geometry gradient with mipmap (the level of detail depends on "
+                                      "the geometry); pass mipmap=None or screen_vertices=None")
+        if screen_vertices.requires_grad and torch.is_grad_enabled():
+            adjacency = vertex_adjacency(fragments.tri, fragments.num_vertices, cache)
     background = _checked_background(background, C, image)
     if not image.is_cuda:
         raise ValueError("image and fragments must be on one GPU device")
+    if adjacency is not None:
+        return _UvTextureImagesGeometry.apply(image, screen_vertices, faces_uv.detach().contiguous(), fragments, adjacency,
+                                              wrapping, background)
     if levels == 0:
         return _UvTextureImages.apply(image, faces_uv.detach().contiguous(), fragments, wrapping, background)
     return _UvTextureMipImages.apply(image, faces_uv.detach().contiguous(), fragments, wrapping, background, levels, lod_bias)

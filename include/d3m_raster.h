@@ -1119,6 +1119,46 @@ int d3m_uv_texture_mip_images_backward(const d3m_fragments* fragments, const flo
                                        int image_batch, int image_height, int image_width, int num_channels,
                                        int texture_wrapping, int levels, float lod_bias, void* scratch, size_t scratch_bytes,
                                        float* grad_image, d3m_stream_t stream);
+/* The interior geometry gradient of what is drawn over a coverage record (an addition; csrc/d3m_fragment_geometry.h states the
+ * function that is differentiated and the order of every sum): the derivative of the perspective-correct weights u_c of every
+ * owned pixel with respect to the owner's three screen-space corners.  Coverage is a constant; the silhouette gradient is the
+ * render nodes'.  The record must be the one d3m_forward_face_index_map_mesh made from the vertices the gradient is for.
+ * d3m_fragment_weights WRITES every element of weights [B, S, S, 3] (S the raster size, map orientation): u_c =
+ * weight_map * (depth_map / z_c), +0 where uncovered.  One launch (k_fragment_weights).  D3M_ERR_INVALID, before any launch:
+ * what d3m_vertex_attribute_images refuses of the record, B S S beyond 2^32, a NULL or misaligned weights. */
+int d3m_fragment_weights(const d3m_fragments* fragments, float* weights, d3m_stream_t stream);
+/* Floats of scratch of d3m_fragment_geometry_backward: B F' 9 per-face sums and 3 B num_chunks chunk sums of the adjacency's
+ * long rows; with_pixel_grads != 0: and 3 B S S more, room for a pixel_grads map (raster_size = S).  0 for sizes that are
+ * refused. */
+size_t d3m_fragment_geometry_scratch_floats(int batch_size, int num_faces, int raster_size, const d3m_csr* adjacency,
+                                            int with_pixel_grads);
+/* pixel_grads [B, S, S, 3] = dL/du_c of the attribute images for the image gradient grad_images [B, C, image_size,
+ * image_size]: h_c = sum_k scale g[k] a_c[k], every element WRITTEN (+0 where uncovered).  One launch
+ * (k_vertex_attribute_pixel_grads).  D3M_ERR_INVALID, before any launch: what d3m_vertex_attribute_images refuses of the
+ * record, the attributes and the sizes, B S S beyond 2^32, NULL grad_images / pixel_grads. */
+int d3m_vertex_attribute_pixel_grads(const d3m_fragments* fragments, const float* attributes, int attributes_batch,
+                                     int num_vertices, int num_channels, const float* grad_images, float* pixel_grads,
+                                     d3m_stream_t stream);
+/* pixel_grads [B, S, S, 3] = dL/du_c of the plain bilinear uv texture images (d3m_uv_texture_images; not the mip-mapped
+ * lookup, whose level of detail depends on the geometry): h_c = (W - 1) uv_c.x Dx + (H - 1) uv_c.y Dy, Dx / Dy the image
+ * gradient's derivative along the lookup position from the four taps, 0 where that axis sits at a clamp limit.  faces_uv is a
+ * constant.  Every element WRITTEN.  One launch (k_uv_texture_pixel_grads).  D3M_ERR_INVALID, before any launch: what
+ * d3m_uv_texture_images refuses of the record, faces_uv, the image and the sizes, B S S beyond 2^32, a NULL or misaligned
+ * grad_images / pixel_grads. */
+int d3m_uv_texture_pixel_grads(const d3m_fragments* fragments, const float* faces_uv, const float* image, int image_batch,
+                               int image_height, int image_width, int num_channels, int texture_wrapping,
+                               const float* grad_images, float* pixel_grads, d3m_stream_t stream);
+/* The shared adjoint: pixel_grads [B, S, S, 3] (read at owned pixels only) -> grad_screen_vertices [B, V, 3], every element
+ * WRITTEN (a vertex of no visible face gets +0).  adjacency: the faces' d3m_csr of V rows (item = 3 f + c).  scratch needs no
+ * initialisation.  No float atomics, nothing cleared; three launches (k_fragment_geometry_face_sums,
+ * k_fragment_geometry_large_face_sums, k_vertex_attribute_adjoint_rows) and k_vertex_attribute_adjoint_chunks on a mesh with
+ * long rows.  D3M_ERR_INVALID, before any launch: what d3m_fragment_weights refuses of the record, num_vertices <= 0, a NULL
+ * or too small visibility blob, what d3m_csr lists (num_rows = num_vertices), NULL items, a NULL or misaligned pixel_grads /
+ * scratch / grad_screen_vertices, 3 num_tri beyond 2^31 - 1; D3M_ERR_WORKSPACE: scratch_floats below
+ * d3m_fragment_geometry_scratch_floats(..., 0). */
+int d3m_fragment_geometry_backward(const d3m_fragments* fragments, const float* pixel_grads, const d3m_csr* adjacency,
+                                   float* scratch, size_t scratch_floats, float* grad_screen_vertices, int num_vertices,
+                                   d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
