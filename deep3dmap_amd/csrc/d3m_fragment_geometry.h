@@ -1,5 +1,5 @@
 // d3m_fragment_geometry.h -- the INTERIOR geometry gradient of everything drawn over a coverage record (AttrMaps,
-// d3m_attributes.h): the derivative of the perspective-correct weights u_c of each owned pixel with respect to the owner's
+// d3m_fragments.h): the derivative of the perspective-correct weights u_c of each owned pixel with respect to the owner's
 // three screen-space corners, as ONE adjoint that the attribute images (d3m_attributes.h), the plain bilinear uv texture
 // images (d3m_uv_texture.h) and the weight map itself (k_fragment_weights) share.  Coverage -- which face owns which pixel --
 // is a constant: the silhouette gradient is the business of the render nodes' edge pass, not of this header.
@@ -37,14 +37,8 @@
 //
 // THE ORDER of the adjoint's sums, the same bits on every run (no float atomics anywhere, nothing is cleared):
 //   1. per visible face (b, fn), corner k, coordinate j in {x, y, z}:  Gv[b,fn,k,j] = the sum over the pixels the face owns of
-//      the pixel's term above.  Route and order are those of the attribute adjoint's stage 1 (d3m_attributes.h):
-//      a. a face whose clipped box has at most FM_MAX_BBOX_AREA pixels: FM_LANES lanes share scan_owned_pixels
-//         (d3m_face_major.h): the owned pixels are numbered in ascending box order, lane `sub` adds those of rank sub,
-//         sub + FM_LANES, ... in that order from 0, and the lanes are combined by quad_sum;
-//      b. a larger face: one workgroup of RG_BLOCK lanes; lane t adds the owned pixels among box pixels t, t + RG_BLOCK, ...
-//         (row-major in the box) in that order from 0, and the lanes are combined by rg_block_sum (d3m_row_gather.h, steps 2
-//         and 3).
-//      Gv is stored plainly; entries of faces that own no pixel are never written and never read.
+//      the pixel's term above (fg_add_pixel).  Route and order: stage 1 of d3m_fragments.h (THE ORDER there), with 9
+//      accumulators a face.  Gv [B,F',3,3] is stored plainly; entries of faces that own no pixel are never written or read.
 //   2. per vertex v, view b, coordinate j: stage 2 of the attribute adjoint with C = 3 and a per-view result
 //      (k_vertex_attribute_adjoint_chunks / k_vertex_attribute_adjoint_rows, the SAME kernels: Gv has G's layout [B,F',3,C]):
 //      acc = 0; for the items 3 f + c of the vertex's adjacency row in ascending order: acc += Gv[b,f,c,j] if face f is
@@ -60,15 +54,13 @@ namespace d3m {
 
 // ---- the weight map: one lane per internal pixel; every element of u [B,S,S,3] is written (an uncovered pixel: +0) ----------
 __global__ void __launch_bounds__(256) k_fragment_weights(AttrMaps m, float* __restrict__ u_map) {
-    const long n = (long)m.B * m.S * m.S;
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= n) return;
+    int b, x, y, fn;
+    if (!fr_pixel(m, p, b, x, y, fn)) return;
     float u[3] = {0.0f, 0.0f, 0.0f};
-    const int fn = m.face_index_map[p];
-    if ((unsigned)fn < (unsigned)m.Fp) {
-        const int b = (int)(p / ((long)m.S * m.S));
-        const float* face = m.faces + ((size_t)b * m.Fp + fn) * 9;
-        const float z[3] = {face[2], face[5], face[8]};
+    if (fn >= 0) {
+        float z[3];
+        fr_corner_depths(m, b, fn, z);
         va_weights(m, (size_t)p, z, u);
     }
 #pragma unroll
@@ -122,123 +114,46 @@ __device__ __forceinline__ void fg_add_pixel(const FgFace& f, const float* __res
     }
 }
 
-// 1a: FM_LANES lanes per listed face; a fixed grid strides over the visibility list
+// fr_face_sums / fr_large_face_sums (d3m_fragments.h) with nine accumulators
+struct FgFaceSums {
+    const AttrMaps& m;
+    const float* h;
+    float* Gv;
+    FgFace f;
+    __device__ __forceinline__ void setup(const float* face, int) { fg_face(face, f); }
+    __device__ __forceinline__ void add(int x, int y, size_t q, float* acc) const { fg_add_pixel(f, h, q, x, y, m.S, acc); }
+    __device__ __forceinline__ void store(size_t gi, const float* acc) const {
+#pragma unroll
+        for (int k = 0; k < 9; k++) Gv[gi * 9 + k] = acc[k];
+    }
+};
+
 __global__ void __launch_bounds__(256) k_fragment_geometry_face_sums(AttrMaps m, const float* __restrict__ h,
                                                                     const int* __restrict__ list,
                                                                     const int* __restrict__ n_list, float* __restrict__ Gv) {
-    const int sub = threadIdx.x % FM_LANES;
-    const long n_units = min((long)*n_list, (long)m.B * m.Fp);      // (the list has one entry per face at most)
-    for (long un = (long)blockIdx.x * FM_FACES_PER_BLOCK + threadIdx.x / FM_LANES; un < n_units;
-         un += (long)gridDim.x * FM_FACES_PER_BLOCK) {
-        const long gi = list[un];
-        if (gi < 0 || gi >= (long)m.B * m.Fp) continue;
-        const int bn = (int)(gi / m.Fp), fn = (int)(gi - (long)bn * m.Fp);
-        float face[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) face[k] = m.faces[(size_t)gi * 9 + k];
-        int x0 = 0, x1 = 0, y0 = 0, y1 = 0;
-        const bool boxed = pixel_bbox(face, m.S, x0, x1, y0, y1);
-        const int area = boxed ? (x1 - x0 + 1) * (y1 - y0 + 1) : 0;
-        if (area > FM_MAX_BBOX_AREA) continue;                          // 1b's
-        FgFace f;
-        fg_face(face, f);
-        float acc[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) acc[k] = 0.0f;
-        const size_t base = (size_t)bn * m.S * m.S;
-        if (boxed)
-            scan_owned_pixels<FM_LANES>(m.face_index_map + base, fn, m.S, x0, x1, y0, area, sub, [&](int x, int y) {
-                fg_add_pixel(f, h, base + (size_t)y * m.S + x, x, y, m.S, acc);
-            });
-#pragma unroll
-        for (int k = 0; k < 9; k++) acc[k] = quad_sum(acc[k]);
-        if (sub == 0) {
-#pragma unroll
-            for (int k = 0; k < 9; k++) Gv[(size_t)gi * 9 + k] = acc[k];
-        }
-    }
+    FgFaceSums policy{m, h, Gv};
+    fr_face_sums<9>(m, list, n_list, policy);
 }
 
-// 1b: the listed faces whose box exceeds FM_MAX_BBOX_AREA, a workgroup per face (k_vertex_attribute_large_face_sums' walk:
-// lane t notes entry first + t when it is large, the workgroup then takes the noted faces one after another)
 __global__ void __launch_bounds__(RG_BLOCK) k_fragment_geometry_large_face_sums(AttrMaps m, const float* __restrict__ h,
                                                                                const int* __restrict__ list,
                                                                                const int* __restrict__ n_list,
                                                                                float* __restrict__ Gv) {
-    __shared__ int s_large[RG_BLOCK];
-    const long n_units = min((long)*n_list, (long)m.B * m.Fp);
-    const int t = threadIdx.x;
-    for (long first = (long)blockIdx.x * RG_BLOCK; first < n_units; first += (long)gridDim.x * RG_BLOCK) {
-        int mine = -1;
-        if (first + t < n_units) {
-            const long gi = list[first + t];
-            if (gi >= 0 && gi < (long)m.B * m.Fp) {
-                float face[9];
-#pragma unroll
-                for (int k = 0; k < 9; k++) face[k] = m.faces[(size_t)gi * 9 + k];
-                int x0, x1, y0, y1;
-                if (pixel_bbox(face, m.S, x0, x1, y0, y1) && (x1 - x0 + 1) * (y1 - y0 + 1) > FM_MAX_BBOX_AREA) mine = (int)gi;
-            }
-        }
-        s_large[t] = mine;
-        __syncthreads();
-        for (int j = 0; j < RG_BLOCK; j++) {
-            const int gi = s_large[j];                                  // (the same for every lane)
-            if (gi < 0) continue;
-            const int bn = gi / m.Fp, fn = gi - bn * m.Fp;
-            float face[9];
-#pragma unroll
-            for (int k = 0; k < 9; k++) face[k] = m.faces[(size_t)gi * 9 + k];
-            int x0, x1, y0, y1;
-            pixel_bbox(face, m.S, x0, x1, y0, y1);
-            const int bw = x1 - x0 + 1, area = bw * (y1 - y0 + 1);
-            const size_t base = (size_t)bn * m.S * m.S;
-            FgFace f;
-            fg_face(face, f);
-            float acc[9];
-#pragma unroll
-            for (int k = 0; k < 9; k++) acc[k] = 0.0f;
-            for (int i = t; i < area; i += RG_BLOCK) {
-                const int by = i / bw, x = x0 + (i - by * bw), y = y0 + by;
-                const size_t q = base + (size_t)y * m.S + x;
-                if (m.face_index_map[q] != fn) continue;
-                fg_add_pixel(f, h, q, x, y, m.S, acc);
-            }
-            rg_block_sum(acc);                                          // steps 2 and 3 of d3m_row_gather.h
-            if (t == 0) {
-#pragma unroll
-                for (int k = 0; k < 9; k++) Gv[(size_t)gi * 9 + k] = acc[k];
-            }
-            __syncthreads();                                            // (rg_block_sum's staging array is used again)
-        }
-        __syncthreads();
-    }
+    FgFaceSums policy{m, h, Gv};
+    fr_large_face_sums<9>(m, list, n_list, policy);
 }
 
-// ---- the nodes' h: one lane per internal pixel ------------------------------------------------------------------------------
-// the pixel of lane p: false past the batch; fn < 0 where uncovered
-__device__ __forceinline__ bool fg_pixel(const AttrMaps& m, long p, int& b, int& x, int& y, int& fn) {
-    const long S2 = (long)m.S * m.S;
-    if (p >= (long)m.B * S2) return false;
-    b = (int)(p / S2);
-    const int r = (int)(p - (long)b * S2);
-    y = r / m.S;
-    x = r - y * m.S;
-    fn = m.face_index_map[p];
-    if ((unsigned)fn >= (unsigned)m.Fp) fn = -1;
-    return true;
-}
-
+// ---- the nodes' h: one lane per internal pixel (fr_pixel) --------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_vertex_attribute_pixel_grads(AttrMaps m, const float* __restrict__ attributes,
                                                                      int attr_batch, int V, int C,
                                                                      const float* __restrict__ grad_images,
                                                                      float* __restrict__ h) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     int b, x, y, fn;
-    if (!fg_pixel(m, p, b, x, y, fn)) return;
+    if (!fr_pixel(m, p, b, x, y, fn)) return;
     float acc[3] = {0.0f, 0.0f, 0.0f};
     if (fn >= 0) {
-        const int s = m.aa ? m.S / 2 : m.S;
+        const int s = fr_output_size(m);
         const bool back = fn >= m.Ft;
         const int32_t* t = m.tri + (size_t)(back ? fn - m.Ft : fn) * 3;
         const float* attr = attributes + (size_t)(attr_batch > 1 ? b : 0) * V * C;
@@ -264,12 +179,12 @@ __global__ void __launch_bounds__(256) k_uv_texture_pixel_grads(AttrMaps m, UvTe
                                                                const float* __restrict__ grad_images, float* __restrict__ h) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     int b, x, y, fn;
-    if (!fg_pixel(m, p, b, x, y, fn)) return;
+    if (!fr_pixel(m, p, b, x, y, fn)) return;
     float out[3] = {0.0f, 0.0f, 0.0f};
     if (fn >= 0) {
-        const int s = m.aa ? m.S / 2 : m.S, C = tx.C;
-        const float* face = m.faces + ((size_t)b * m.Fp + fn) * 9;
-        const float z[3] = {face[2], face[5], face[8]};
+        const int s = fr_output_size(m), C = tx.C;
+        float z[3];
+        fr_corner_depths(m, b, fn, z);
         UvtCorners k;
         float pos_x, pos_y;
         uvt_pixel_position(m, tx, (size_t)p, fn, z, k, pos_x, pos_y);

@@ -2560,6 +2560,28 @@ D3M_EXPORT size_t d3m_vertex_attribute_scratch_floats(int batch_size, int num_fa
     return ((size_t)batch_size * num_faces * 3 + (size_t)batch_size * adjacency->num_chunks) * num_channels;
 }
 
+// The two-stage fixed-order adjoint over a coverage record (d3m_fragments.h, d3m_attributes.h): stage 1 -- `stage1(small_blocks,
+// large_blocks, stream)` launches the node's two face-sum kernels on fixed grids striding over the visibility list (its length
+// is only known on the device), which leave G [B,F',3,C] at the front of the scratch -- then stage 2, per vertex over the
+// adjacency: the chunks of the long rows and the rows.  shared: one result over the views, else one per view.
+template <class Stage1>
+static int face_sums_gather(const AttrMaps& m, const VisibilityView& vis, const d3m_csr& adjacency, float* scratch,
+                            int num_vertices, int C, bool shared, float* grad, hipStream_t st, Stage1 stage1) {
+    const CsrRows adj = csr_rows(adjacency);
+    const int num_chunks = adj.longs.n_chunks, c_chunks = (C + VA_CHUNK - 1) / VA_CHUNK;
+    const long nf = (long)m.B * m.Fp;
+    const float* G = scratch;
+    float* partials = scratch + (size_t)nf * 3 * C;
+    stage1(std::min(blocks_for(nf, FM_FACES_PER_BLOCK), 2048u), std::min(blocks_for(nf, RG_BLOCK), 256u), st);
+    if (num_chunks > 0)
+        LAUNCH("k_vertex_attribute_adjoint_chunks", k_vertex_attribute_adjoint_chunks, dim3(num_chunks, m.B, c_chunks),
+               dim3(RG_BLOCK), st, adj.items, adj.longs.chunks, num_chunks, G, (const int*)vis.flags, m.Ft, m.Fp, C, partials);
+    LAUNCH("k_vertex_attribute_adjoint_rows", k_vertex_attribute_adjoint_rows,
+           dim3(blocks_for((long)num_vertices * C, 256), shared ? 1 : m.B), dim3(256), st, adj, (const float*)partials, G,
+           (const int*)vis.flags, m.B, m.Ft, m.Fp, num_vertices, C, shared ? 1 : 0, grad);
+    return check_launch();
+}
+
 D3M_EXPORT int d3m_vertex_attribute_images_backward(const d3m_fragments* fragments, const float* grad_images,
                                                     const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
                                                     float* grad_attributes, int attributes_batch, int num_vertices,
@@ -2572,29 +2594,16 @@ D3M_EXPORT int d3m_vertex_attribute_images_backward(const d3m_fragments* fragmen
     if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
     if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
     if (scratch_floats < d3m_vertex_attribute_scratch_floats(m.B, m.Fp, num_channels, adjacency)) return D3M_ERR_WORKSPACE;
-    const CsrRows adj = csr_rows(*adjacency);
-    const int num_chunks = adj.longs.n_chunks, C = num_channels, c_chunks = (C + VA_CHUNK - 1) / VA_CHUNK;
     const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
-    float* G = scratch;
-    float* partials = G + (size_t)nf * 3 * C;
-    hipStream_t st = (hipStream_t)stream;
-    // 1. per visible face: fixed grids striding over the visibility list (its length is only known on the device)
-    const unsigned small_blocks = std::min(blocks_for(nf, FM_FACES_PER_BLOCK), 2048u);
-    LAUNCH("k_vertex_attribute_face_sums", k_vertex_attribute_face_sums, dim3(small_blocks, c_chunks), dim3(256), st, m,
-           grad_images, C, (const int*)vis.list, (const int*)vis.count, G);
-    const unsigned large_blocks = std::min(blocks_for(nf, RG_BLOCK), 256u);
-    LAUNCH("k_vertex_attribute_large_face_sums", k_vertex_attribute_large_face_sums, dim3(large_blocks, c_chunks),
-           dim3(RG_BLOCK), st, m, grad_images, C, (const int*)vis.list, (const int*)vis.count, G);
-    // 2. per vertex, over the adjacency
-    if (num_chunks > 0)
-        LAUNCH("k_vertex_attribute_adjoint_chunks", k_vertex_attribute_adjoint_chunks, dim3(num_chunks, m.B, c_chunks),
-               dim3(RG_BLOCK), st, adj.items, adj.longs.chunks, num_chunks, (const float*)G, (const int*)vis.flags, m.Ft,
-               m.Fp, C, partials);
-    const int shared = attributes_batch == 1 ? 1 : 0;
-    LAUNCH("k_vertex_attribute_adjoint_rows", k_vertex_attribute_adjoint_rows,
-           dim3(blocks_for((long)num_vertices * C, 256), shared ? 1 : m.B), dim3(256), st, adj, (const float*)partials,
-           (const float*)G, (const int*)vis.flags, m.B, m.Ft, m.Fp, num_vertices, C, shared, grad_attributes);
-    return check_launch();
+    const unsigned c_chunks = (num_channels + VA_CHUNK - 1) / VA_CHUNK;
+    return face_sums_gather(
+        m, vis, *adjacency, scratch, num_vertices, num_channels, attributes_batch == 1, grad_attributes, (hipStream_t)stream,
+        [&](unsigned small_blocks, unsigned large_blocks, hipStream_t st) {
+            LAUNCH("k_vertex_attribute_face_sums", k_vertex_attribute_face_sums, dim3(small_blocks, c_chunks), dim3(256), st, m,
+                   grad_images, num_channels, (const int*)vis.list, (const int*)vis.count, scratch);
+            LAUNCH("k_vertex_attribute_large_face_sums", k_vertex_attribute_large_face_sums, dim3(large_blocks, c_chunks),
+                   dim3(RG_BLOCK), st, m, grad_images, num_channels, (const int*)vis.list, (const int*)vis.count, scratch);
+        });
 }
 
 // Per-pixel uv texture images (d3m_uv_texture.h): a texture image looked up at every pixel's interpolated uv, and the
@@ -2645,6 +2654,29 @@ D3M_EXPORT size_t d3m_uv_texture_images_scratch_bytes(int image_batch, int image
            (size_t)UVT_MAX_BLOCKS * sizeof(unsigned);
 }
 
+// The front of both image adjoints (d3m_uv_texture.h): the fraction bits, the scratch's carve-up -- n_acc accumulators, then the
+// block maxima -- and the launch that clears the accumulators and leaves the block maxima of |scale * g|.
+struct UvAdjoint {
+    unsigned long long* acc;
+    unsigned* block_max;
+    long n_px;
+    int n_max, frac;
+};
+
+static UvAdjoint uv_adjoint_clear_max(const AttrMaps& m, long image_size, int num_channels, const float* grad_images,
+                                      void* scratch, long n_acc, hipStream_t st) {
+    UvAdjoint a;
+    const long n_g = (long)m.B * num_channels * image_size * image_size;
+    a.n_px = (long)m.B * m.S * m.S;
+    a.frac = 62 - ceil_log2((unsigned long long)a.n_px);
+    a.acc = (unsigned long long*)scratch;
+    a.block_max = (unsigned*)(a.acc + n_acc);
+    a.n_max = (int)std::min(blocks_for(std::max(n_acc, n_g), 256), (unsigned)UVT_MAX_BLOCKS);
+    LAUNCH("k_uv_texture_images_clear_max", k_uv_texture_images_clear_max, dim3(a.n_max), dim3(256), st, grad_images, n_g,
+           m.aa ? 0.25f : 1.0f, a.acc, n_acc, a.block_max);
+    return a;
+}
+
 D3M_EXPORT int d3m_uv_texture_images_backward(const d3m_fragments* fragments, const float* faces_uv, const float* grad_images,
                                               int image_batch, int image_height, int image_width, int num_channels,
                                               int texture_wrapping, void* scratch, size_t scratch_bytes, float* grad_image,
@@ -2659,20 +2691,14 @@ D3M_EXPORT int d3m_uv_texture_images_backward(const d3m_fragments* fragments, co
     if (need == 0) return D3M_ERR_INVALID;                              // (B S^2 beyond 2^32)
     if (scratch_bytes < need) return D3M_ERR_WORKSPACE;
     const long n_acc = (long)image_batch * image_height * image_width * num_channels;
-    const long s = fragments->image_size, n_g = (long)m.B * num_channels * s * s, n_px = (long)m.B * m.S * m.S;
-    const int frac = 62 - ceil_log2((unsigned long long)n_px);
-    unsigned long long* acc = (unsigned long long*)scratch;
-    unsigned* block_max = (unsigned*)(acc + n_acc);
     hipStream_t st = (hipStream_t)stream;
-    const int n_max = (int)std::min(blocks_for(std::max(n_acc, n_g), 256), (unsigned)UVT_MAX_BLOCKS);
-    LAUNCH("k_uv_texture_images_clear_max", k_uv_texture_images_clear_max, dim3(n_max), dim3(256), st, grad_images, n_g,
-           m.aa ? 0.25f : 1.0f, acc, n_acc, block_max);
+    const UvAdjoint a = uv_adjoint_clear_max(m, fragments->image_size, num_channels, grad_images, scratch, n_acc, st);
     LAUNCH("k_uv_texture_images_scatter", k_uv_texture_images_scatter,
-           dim3(std::min(blocks_for(n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, m, tx, grad_images,
-           (const unsigned*)block_max, n_max, frac, acc);
+           dim3(std::min(blocks_for(a.n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, m, tx, grad_images,
+           (const unsigned*)a.block_max, a.n_max, a.frac, a.acc);
     LAUNCH("k_uv_texture_images_convert", k_uv_texture_images_convert,
-           dim3(std::min(blocks_for(n_acc, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)acc, n_acc,
-           (const unsigned*)block_max, n_max, frac, grad_image);
+           dim3(std::min(blocks_for(n_acc, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)a.acc, n_acc,
+           (const unsigned*)a.block_max, a.n_max, a.frac, grad_image);
     return check_launch();
 }
 
@@ -2765,20 +2791,14 @@ D3M_EXPORT int d3m_uv_texture_mip_images_backward(const d3m_fragments* fragments
     if (need == 0 || scratch_bytes < need) return D3M_ERR_INVALID;      // (B S^2 beyond 2^32; a scratch that is too small)
     const long n_acc = (long)image_batch * mp.T * num_channels;
     const long n_out = (long)image_batch * image_height * image_width * num_channels;
-    const long s = fragments->image_size, n_g = (long)m.B * num_channels * s * s, n_px = (long)m.B * m.S * m.S;
-    const int frac = 62 - ceil_log2((unsigned long long)n_px);
-    unsigned long long* acc = (unsigned long long*)scratch;
-    unsigned* block_max = (unsigned*)(acc + n_acc);
     hipStream_t st = (hipStream_t)stream;
-    const int n_max = (int)std::min(blocks_for(std::max(n_acc, n_g), 256), (unsigned)UVT_MAX_BLOCKS);
-    LAUNCH("k_uv_texture_images_clear_max", k_uv_texture_images_clear_max, dim3(n_max), dim3(256), st, grad_images, n_g,
-           m.aa ? 0.25f : 1.0f, acc, n_acc, block_max);
+    const UvAdjoint a = uv_adjoint_clear_max(m, fragments->image_size, num_channels, grad_images, scratch, n_acc, st);
     LAUNCH("k_uv_texture_mip_images_scatter", k_uv_texture_mip_images_scatter,
-           dim3(std::min(blocks_for(n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, m, tx, mp, grad_images,
-           (const unsigned*)block_max, n_max, frac, acc);
+           dim3(std::min(blocks_for(a.n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, m, tx, mp, grad_images,
+           (const unsigned*)a.block_max, a.n_max, a.frac, a.acc);
     LAUNCH("k_uv_texture_mip_images_convert", k_uv_texture_mip_images_convert,
-           dim3(std::min(blocks_for(n_out, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)acc, mp,
-           image_batch, image_height, image_width, num_channels, (const unsigned*)block_max, n_max, frac, grad_image);
+           dim3(std::min(blocks_for(n_out, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)a.acc, mp,
+           image_batch, image_height, image_width, num_channels, (const unsigned*)a.block_max, a.n_max, a.frac, grad_image);
     return check_launch();
 }
 
@@ -2849,27 +2869,16 @@ D3M_EXPORT int d3m_fragment_geometry_backward(const d3m_fragments* fragments, co
     if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
     if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
     if (scratch_floats < d3m_fragment_geometry_scratch_floats(m.B, m.Fp, m.S, adjacency, 0)) return D3M_ERR_WORKSPACE;
-    const CsrRows adj = csr_rows(*adjacency);
-    const int num_chunks = adj.longs.n_chunks;
     const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
-    float* Gv = scratch;
-    float* partials = Gv + (size_t)nf * 9;
-    hipStream_t st = (hipStream_t)stream;
-    // 1. per visible face: fixed grids striding over the visibility list (its length is only known on the device)
-    const unsigned small_blocks = std::min(blocks_for(nf, FM_FACES_PER_BLOCK), 2048u);
-    LAUNCH("k_fragment_geometry_face_sums", k_fragment_geometry_face_sums, dim3(small_blocks), dim3(256), st, m, pixel_grads,
-           (const int*)vis.list, (const int*)vis.count, Gv);
-    const unsigned large_blocks = std::min(blocks_for(nf, RG_BLOCK), 256u);
-    LAUNCH("k_fragment_geometry_large_face_sums", k_fragment_geometry_large_face_sums, dim3(large_blocks), dim3(RG_BLOCK), st, m,
-           pixel_grads, (const int*)vis.list, (const int*)vis.count, Gv);
-    // 2. per vertex and view, over the adjacency: stage 2 of the attribute adjoint with C = 3 (Gv has G's layout)
-    if (num_chunks > 0)
-        LAUNCH("k_vertex_attribute_adjoint_chunks", k_vertex_attribute_adjoint_chunks, dim3(num_chunks, m.B, 1), dim3(RG_BLOCK),
-               st, adj.items, adj.longs.chunks, num_chunks, (const float*)Gv, (const int*)vis.flags, m.Ft, m.Fp, 3, partials);
-    LAUNCH("k_vertex_attribute_adjoint_rows", k_vertex_attribute_adjoint_rows,
-           dim3(blocks_for((long)num_vertices * 3, 256), m.B), dim3(256), st, adj, (const float*)partials, (const float*)Gv,
-           (const int*)vis.flags, m.B, m.Ft, m.Fp, num_vertices, 3, 0, grad_screen_vertices);
-    return check_launch();
+    // Gv has G's layout with C = 3, and the result is per view
+    return face_sums_gather(
+        m, vis, *adjacency, scratch, num_vertices, 3, false, grad_screen_vertices, (hipStream_t)stream,
+        [&](unsigned small_blocks, unsigned large_blocks, hipStream_t st) {
+            LAUNCH("k_fragment_geometry_face_sums", k_fragment_geometry_face_sums, dim3(small_blocks), dim3(256), st, m,
+                   pixel_grads, (const int*)vis.list, (const int*)vis.count, scratch);
+            LAUNCH("k_fragment_geometry_large_face_sums", k_fragment_geometry_large_face_sums, dim3(large_blocks),
+                   dim3(RG_BLOCK), st, m, pixel_grads, (const int*)vis.list, (const int*)vis.count, scratch);
+        });
 }
 
 D3M_EXPORT int d3m_create_texture_image(const float* vertices_all, const float* textures, float* image, int num_faces,

@@ -1,11 +1,11 @@
 // d3m_uv_texture.h -- per-pixel uv texture images: a texture image [H, W, C] (channels last) looked up bilinearly at the
-// interpolated uv of every pixel of a coverage record (AttrMaps, d3m_attributes.h) into images [B, C, s, s], and the adjoint
+// interpolated uv of every pixel of a coverage record (AttrMaps, d3m_fragments.h) into images [B, C, s, s], and the adjoint
 // with respect to the texture image.  faces_uv [F, 3, 2], the per-corner uv of load_textures, is a constant.
 //
 // Wrapping is applied to the CORNERS, as load_textures defines it: corner c of face f has uv_c = wrap_uv(faces_uv[f][c])
 // (d3m_textures.h; REPEAT, MIRRORED_REPEAT or CLAMP_TO_EDGE -- CLAMP_TO_BORDER is refused, nearest lookup is not offered); a
 // fill_back copy (fn >= F) reads corners 2 - c, as it reads vertices.  Internal pixel p of view b with owner fn >= 0:
-//   u_c   = va_weights (d3m_attributes.h): weight_map[b,p,c] * (depth_map[b,p] / faces[b,fn,c,2]);
+//   u_c   = va_weights (d3m_fragments.h): weight_map[b,p,c] * (depth_map[b,p] / faces[b,fn,c,2]);
 //   pu    = (u_0 uv_0.x + u_1 uv_1.x) + u_2 uv_2.x, pv likewise with .y;
 //   pos_x = clamp(pu (W - 1), 0, W - 1), pos_y = clamp(pv (H - 1), 0, H - 1) -- the u_c sum to 1 and the wrapped corners lie
 //           in [0, 1], so the clamp only absorbs rounding (and sends a NaN to 0: every tap is inside the image);
@@ -35,12 +35,12 @@
 // sample reaches (and a sum that cancels) is +0.  Everything reads gmax from device memory: nothing goes back to the host.
 // Launches: 1 forward; 3 backward (clear + block maxima, scatter, convert).
 #pragma once
-#include "d3m_attributes.h"
+#include "d3m_fragments.h"
 #include "d3m_textures.h"
 
 namespace d3m {
 
-constexpr int UVT_CHUNK = 8;             // channels a lane of the forward keeps in registers at a time
+constexpr int UVT_CHUNK = VA_CHUNK;      // channels a lane of the forward keeps in registers at a time
 constexpr int UVT_MAX_CHANNELS = 64;
 constexpr int UVT_MAX_SIZE = 32768;      // H, W: W - 1 and every tap index are exact in f32, H W fits an int
 constexpr int UVT_MAX_BLOCKS = 1024;     // workgroups of k_uv_texture_images_clear_max = block maxima in the scratch
@@ -82,8 +82,8 @@ __device__ __forceinline__ void uvt_pixel_position(const AttrMaps& m, const UvTe
 
 // the taps of internal pixel q of view b, owned by fn
 __device__ __forceinline__ void uvt_pixel_taps(const AttrMaps& m, const UvTexture& tx, int b, size_t q, int fn, UvtTaps& t) {
-    const float* face = m.faces + ((size_t)b * m.Fp + fn) * 9;
-    const float z[3] = {face[2], face[5], face[8]};
+    float z[3];
+    fr_corner_depths(m, b, fn, z);
     UvtCorners k;
     float pos_x, pos_y;
     uvt_pixel_position(m, tx, q, fn, z, k, pos_x, pos_y);
@@ -96,62 +96,21 @@ __device__ __forceinline__ void uvt_pixel_taps(const AttrMaps& m, const UvTextur
     }
 }
 
-// ---- forward: one lane per OUTPUT pixel; the 1 or 4 internal pixels' owners, weights and taps are gathered once and the
-// channels walked in chunks of UVT_CHUNK (registers do not grow with C); adjacent lanes store adjacent pixels of one channel
-// plane.  Every element of images and alpha is written.
+// ---- forward: fr_output_pixel_walk (d3m_fragments.h) over the four taps of every internal pixel ----------------------------
 __global__ void __launch_bounds__(256) k_uv_texture_images(AttrMaps m, UvTexture tx, const float* __restrict__ image,
                                                           const float* __restrict__ background, float* __restrict__ images,
                                                           float* __restrict__ alpha) {
-    const int s = m.aa ? m.S / 2 : m.S;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const int b = blockIdx.y;
-    if (i >= (long)s * s) return;
-    const int yo = (int)(i / s), xo = (int)(i - (long)yo * s);
-    const int np = m.aa ? 4 : 1, C = tx.C;
+    const int C = tx.C;
+    const float* img = image + (size_t)(tx.image_batch > 1 ? (int)blockIdx.y : 0) * tx.H * tx.W * C;
     UvtTaps taps[4];
-    bool covered[4];
-    float n_cov = 0.0f;
-    const float* img = image + (size_t)(tx.image_batch > 1 ? b : 0) * tx.H * tx.W * C;
+    fr_output_pixel_walk(
+        m, C, background, images, alpha, [&](int j, int b, size_t q, int fn) { uvt_pixel_taps(m, tx, b, q, fn, taps[j]); },
+        [&](int j, int k) {
+            float v = 0.0f;
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-        covered[j] = false;
-        if (j >= np) continue;
-        const int yi = m.S - 1 - (m.aa ? 2 * yo + (j >> 1) : yo), xi = m.aa ? 2 * xo + (j & 1) : xo;
-        const size_t q = ((size_t)b * m.S + yi) * m.S + xi;
-        const int fn = m.face_index_map[q];
-        if ((unsigned)fn >= (unsigned)m.Fp) continue;                   // uncovered (-1)
-        uvt_pixel_taps(m, tx, b, q, fn, taps[j]);
-        covered[j] = true;
-        n_cov += 1.0f;
-    }
-    const float inv = m.aa ? 0.25f : 1.0f;
-    float* out = images + (size_t)b * C * s * s + i;
-    for (int k0 = 0; k0 < C; k0 += UVT_CHUNK) {
-        float acc[UVT_CHUNK];
-#pragma unroll
-        for (int kk = 0; kk < UVT_CHUNK; kk++) acc[kk] = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (j >= np) continue;
-#pragma unroll
-            for (int kk = 0; kk < UVT_CHUNK; kk++) {
-                const int k = k0 + kk;
-                if (k >= C) continue;
-                if (covered[j]) {
-                    float v = 0.0f;
-#pragma unroll
-                    for (int a = 0; a < 4; a++) v += img[(size_t)taps[j].pix[a] * C + k] * taps[j].w[a];
-                    acc[kk] += v;
-                } else {
-                    acc[kk] += background ? background[k] : 0.0f;
-                }
-            }
-        }
-#pragma unroll
-        for (int kk = 0; kk < UVT_CHUNK; kk++)
-            if (k0 + kk < C) out[(size_t)(k0 + kk) * s * s] = acc[kk] * inv;
-    }
-    alpha[(size_t)b * s * s + i] = n_cov * inv;
+            for (int a = 0; a < 4; a++) v += img[(size_t)taps[j].pix[a] * C + k] * taps[j].w[a];
+            return v;
+        });
 }
 
 // ---- adjoint ------------------------------------------------------------------------------------------------------------
@@ -203,37 +162,55 @@ __global__ void __launch_bounds__(256) k_uv_texture_images_clear_max(const float
     if (threadIdx.x == 0) block_max[blockIdx.x] = v;
 }
 
-// 2. one lane per internal pixel of a fixed grid striding over B S S; the channel loop is innermost, so a lane's adds to one
-// tap are C * 8 contiguous bytes.  A tap of weight 0 adds nothing and is skipped.
-__global__ void __launch_bounds__(256) k_uv_texture_images_scatter(AttrMaps m, UvTexture tx, const float* __restrict__ grad_images,
-                                                                  const unsigned* __restrict__ block_max, int n_max, int frac,
-                                                                  unsigned long long* __restrict__ acc) {
+// 2. one lane per internal pixel of a fixed grid striding over B S S quantises and atomically adds the TAPS taps of every
+// owned pixel: term = w_j * (scale * g), a tap of weight 0 adds nothing and is skipped.  The channel loop is innermost, so a
+// lane's adds to one tap are C * 8 contiguous bytes.  taps(b, p, fn, pix, w): the pixel's tap texels (within one image's
+// per_image / C accumulator texels) and weights; acc holds per_image accumulators an image.
+template <int TAPS, class Taps>
+__device__ __forceinline__ void uvt_scatter_taps(const AttrMaps& m, int C, int image_batch, size_t per_image,
+                                                 const float* __restrict__ grad_images, const unsigned* __restrict__ block_max,
+                                                 int n_max, int frac, unsigned long long* __restrict__ acc, Taps taps) {
     const UvtQuantum qn = uvt_quantum(uvt_gmax_bits(block_max, n_max), frac);
     if (qn.state != UVT_FINITE) return;
-    const int s = m.aa ? m.S / 2 : m.S, C = tx.C;
-    const long S2 = (long)m.S * m.S, n = (long)m.B * S2;
+    const int s = fr_output_size(m);
+    const long n = (long)m.B * m.S * m.S;
     const float scale = m.aa ? 0.25f : 1.0f;
     for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long)gridDim.x * 256) {
-        const int fn = m.face_index_map[p];
-        if ((unsigned)fn >= (unsigned)m.Fp) continue;
-        const int b = (int)(p / S2);
-        const int r = (int)(p - (long)b * S2), y = r / m.S, x = r - y * m.S;
-        UvtTaps t;
-        uvt_pixel_taps(m, tx, b, (size_t)p, fn, t);
-        const int yo = m.aa ? (m.S - 1 - y) >> 1 : m.S - 1 - y, xo = m.aa ? x >> 1 : x;
+        int b, x, y, fn, xo, yo;
+        fr_pixel(m, p, b, x, y, fn);
+        if (fn < 0) continue;
+        int pix[TAPS];
+        float w[TAPS];
+        taps(b, (size_t)p, fn, pix, w);
+        fr_output_pixel(m, x, y, xo, yo);
         const float* g = grad_images + ((size_t)b * C * s + yo) * s + xo;
-        unsigned long long* dst = acc + (size_t)(tx.image_batch > 1 ? b : 0) * tx.H * tx.W * C;
+        unsigned long long* dst = acc + (size_t)(image_batch > 1 ? b : 0) * per_image;
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (t.w[j] == 0.0f) continue;
-            unsigned long long* texel = dst + (size_t)t.pix[j] * C;
+        for (int j = 0; j < TAPS; j++) {
+            if (w[j] == 0.0f) continue;
+            unsigned long long* texel = dst + (size_t)pix[j] * C;
             for (int k = 0; k < C; k++) {
-                const float term = t.w[j] * (scale * g[(size_t)k * s * s]);
+                const float term = w[j] * (scale * g[(size_t)k * s * s]);
                 const long long fixed = __double2ll_rn((double)term * qn.up);
                 __hip_atomic_fetch_add(texel + k, (unsigned long long)fixed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(256) k_uv_texture_images_scatter(AttrMaps m, UvTexture tx, const float* __restrict__ grad_images,
+                                                                  const unsigned* __restrict__ block_max, int n_max, int frac,
+                                                                  unsigned long long* __restrict__ acc) {
+    uvt_scatter_taps<4>(m, tx.C, tx.image_batch, (size_t)tx.H * tx.W * tx.C, grad_images, block_max, n_max, frac, acc,
+                        [&](int b, size_t q, int fn, int* pix, float* w) {
+                            UvtTaps t;
+                            uvt_pixel_taps(m, tx, b, q, fn, t);
+#pragma unroll
+                            for (int j = 0; j < 4; j++) {
+                                pix[j] = t.pix[j];
+                                w[j] = t.w[j];
+                            }
+                        });
 }
 
 // 3. one lane per element of grad_image (a fixed grid striding over them); every element is written

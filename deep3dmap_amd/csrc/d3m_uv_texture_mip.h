@@ -159,11 +159,11 @@ struct UvtMipTaps {
 // the eight taps of internal pixel q of view b, owned by fn; returns lambda_c
 __device__ __forceinline__ float uvt_mip_pixel_taps(const AttrMaps& m, const UvTexture& tx, const UvMip& mp, int b, size_t q,
                                                     int fn, UvtMipTaps& t) {
-    float face[9];
+    float face[9], z[3];
     const float* fp = m.faces + ((size_t)b * m.Fp + fn) * 9;
 #pragma unroll
     for (int i = 0; i < 9; i++) face[i] = fp[i];
-    const float z[3] = {face[2], face[5], face[8]};
+    fr_corner_depths(face, z);
     UvtCorners k;
     float pos_x, pos_y;
     uvt_pixel_position(m, tx, q, fn, z, k, pos_x, pos_y);
@@ -192,111 +192,56 @@ __device__ __forceinline__ float uvt_mip_pixel_taps(const AttrMaps& m, const UvT
 
 // lambda_c [B, S, S] in map orientation, 0 where uncovered: one lane per internal pixel
 __global__ void __launch_bounds__(256) k_uv_texture_lod(AttrMaps m, UvTexture tx, UvMip mp, float* __restrict__ lod) {
-    const long p = (long)blockIdx.x * 256 + threadIdx.x, S2 = (long)m.S * m.S;
-    if (p >= (long)m.B * S2) return;
-    const int fn = m.face_index_map[p];
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    int b, x, y, fn;
+    if (!fr_pixel(m, p, b, x, y, fn)) return;
     float lambda = 0.0f;
-    if ((unsigned)fn < (unsigned)m.Fp) {
+    if (fn >= 0) {
         UvtMipTaps t;
-        lambda = uvt_mip_pixel_taps(m, tx, mp, (int)(p / S2), (size_t)p, fn, t);
+        lambda = uvt_mip_pixel_taps(m, tx, mp, b, (size_t)p, fn, t);
     }
     lod[p] = lambda;
 }
 
-// ---- forward: k_uv_texture_images with eight taps per internal pixel ---------------------------------------------------------
+// ---- forward: fr_output_pixel_walk (d3m_fragments.h) with eight taps per internal pixel -------------------------------------
 __global__ void __launch_bounds__(256) k_uv_texture_mip_images(AttrMaps m, UvTexture tx, UvMip mp,
                                                               const float* __restrict__ pyramid,
                                                               const float* __restrict__ background, float* __restrict__ images,
                                                               float* __restrict__ alpha) {
-    const int s = m.aa ? m.S / 2 : m.S;
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const int b = blockIdx.y;
-    if (i >= (long)s * s) return;
-    const int yo = (int)(i / s), xo = (int)(i - (long)yo * s);
-    const int np = m.aa ? 4 : 1, C = tx.C;
+    const int C = tx.C;
+    const float* img = pyramid + (size_t)(tx.image_batch > 1 ? (int)blockIdx.y : 0) * mp.T * C;
     UvtMipTaps taps[4];
-    bool covered[4];
-    float n_cov = 0.0f;
-    const float* img = pyramid + (size_t)(tx.image_batch > 1 ? b : 0) * mp.T * C;
+    fr_output_pixel_walk(
+        m, C, background, images, alpha,
+        [&](int j, int b, size_t q, int fn) { uvt_mip_pixel_taps(m, tx, mp, b, q, fn, taps[j]); },
+        [&](int j, int k) {
+            float v[2] = {0.0f, 0.0f};
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
-        covered[j] = false;
-        if (j >= np) continue;
-        const int yi = m.S - 1 - (m.aa ? 2 * yo + (j >> 1) : yo), xi = m.aa ? 2 * xo + (j & 1) : xo;
-        const size_t q = ((size_t)b * m.S + yi) * m.S + xi;
-        const int fn = m.face_index_map[q];
-        if ((unsigned)fn >= (unsigned)m.Fp) continue;                   // uncovered (-1)
-        uvt_mip_pixel_taps(m, tx, mp, b, q, fn, taps[j]);
-        covered[j] = true;
-        n_cov += 1.0f;
-    }
-    const float inv = m.aa ? 0.25f : 1.0f;
-    float* out = images + (size_t)b * C * s * s + i;
-    for (int k0 = 0; k0 < C; k0 += UVT_CHUNK) {
-        float acc[UVT_CHUNK];
+            for (int h = 0; h < 2; h++) {
+                if (taps[j].lw[h] == 0.0f) continue;                    // not read
 #pragma unroll
-        for (int kk = 0; kk < UVT_CHUNK; kk++) acc[kk] = 0.0f;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (j >= np) continue;
-#pragma unroll
-            for (int kk = 0; kk < UVT_CHUNK; kk++) {
-                const int k = k0 + kk;
-                if (k >= C) continue;
-                if (covered[j]) {
-                    float v[2] = {0.0f, 0.0f};
-#pragma unroll
-                    for (int h = 0; h < 2; h++) {
-                        if (taps[j].lw[h] == 0.0f) continue;            // not read
-#pragma unroll
-                        for (int a = 0; a < 4; a++) v[h] += img[(size_t)taps[j].pix[4 * h + a] * C + k] * taps[j].w[4 * h + a];
-                    }
-                    acc[kk] += taps[j].lw[0] * v[0] + taps[j].lw[1] * v[1];
-                } else {
-                    acc[kk] += background ? background[k] : 0.0f;
-                }
+                for (int a = 0; a < 4; a++) v[h] += img[(size_t)taps[j].pix[4 * h + a] * C + k] * taps[j].w[4 * h + a];
             }
-        }
-#pragma unroll
-        for (int kk = 0; kk < UVT_CHUNK; kk++)
-            if (k0 + kk < C) out[(size_t)(k0 + kk) * s * s] = acc[kk] * inv;
-    }
-    alpha[(size_t)b * s * s + i] = n_cov * inv;
+            return taps[j].lw[0] * v[0] + taps[j].lw[1] * v[1];
+        });
 }
 
 // ---- adjoint --------------------------------------------------------------------------------------------------------------
-// 2. k_uv_texture_images_scatter with eight taps: a fixed grid striding over B S S, the channel loop innermost
+// 2. uvt_scatter_taps (d3m_uv_texture.h) with eight taps of weight lw * w_j, over the accumulators of every level
 __global__ void __launch_bounds__(256) k_uv_texture_mip_images_scatter(AttrMaps m, UvTexture tx, UvMip mp,
                                                                       const float* __restrict__ grad_images,
                                                                       const unsigned* __restrict__ block_max, int n_max,
                                                                       int frac, unsigned long long* __restrict__ acc) {
-    const UvtQuantum qn = uvt_quantum(uvt_gmax_bits(block_max, n_max), frac);
-    if (qn.state != UVT_FINITE) return;
-    const int s = m.aa ? m.S / 2 : m.S, C = tx.C;
-    const long S2 = (long)m.S * m.S, n = (long)m.B * S2;
-    const float scale = m.aa ? 0.25f : 1.0f;
-    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < n; p += (long)gridDim.x * 256) {
-        const int fn = m.face_index_map[p];
-        if ((unsigned)fn >= (unsigned)m.Fp) continue;
-        const int b = (int)(p / S2);
-        const int r = (int)(p - (long)b * S2), y = r / m.S, x = r - y * m.S;
-        UvtMipTaps t;
-        uvt_mip_pixel_taps(m, tx, mp, b, (size_t)p, fn, t);
-        const int yo = m.aa ? (m.S - 1 - y) >> 1 : m.S - 1 - y, xo = m.aa ? x >> 1 : x;
-        const float* g = grad_images + ((size_t)b * C * s + yo) * s + xo;
-        unsigned long long* dst = acc + (size_t)(tx.image_batch > 1 ? b : 0) * mp.T * C;
+    uvt_scatter_taps<8>(m, tx.C, tx.image_batch, (size_t)mp.T * tx.C, grad_images, block_max, n_max, frac, acc,
+                        [&](int b, size_t q, int fn, int* pix, float* w) {
+                            UvtMipTaps t;
+                            uvt_mip_pixel_taps(m, tx, mp, b, q, fn, t);
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const float w = t.lw[j >> 2] * t.w[j];
-            if (w == 0.0f) continue;
-            unsigned long long* texel = dst + (size_t)t.pix[j] * C;
-            for (int k = 0; k < C; k++) {
-                const float term = w * (scale * g[(size_t)k * s * s]);
-                const long long fixed = __double2ll_rn((double)term * qn.up);
-                __hip_atomic_fetch_add(texel + k, (unsigned long long)fixed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
+                            for (int j = 0; j < 8; j++) {
+                                pix[j] = t.pix[j];
+                                w[j] = t.lw[j >> 2] * t.w[j];
+                            }
+                        });
 }
 
 // 3. one lane per element of grad_image (a fixed grid striding over them): the element's accumulator and its ancestors', in

@@ -173,24 +173,6 @@ def _attribute_images_adjoint(fr, A, g, batched, sizes):
     return grad
 
 
-class _VertexAttributeImages(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, attributes, fragments, adjacency, background):
-        fr = fragments
-        attr = attributes.contiguous()
-        batched = attr.dim() == 3
-        V, C = attr.shape[-2:]
-        images, alpha = _attribute_images_launch(fr, attr, background)
-        ctx.fragments, ctx.adjacency, ctx.batched, ctx.sizes = fr, adjacency, batched, (images.shape[0], V, C)
-        ctx.mark_non_differentiable(alpha)
-        return images, alpha
-
-    @staticmethod
-    def backward(ctx, grad_images, _grad_alpha):
-        g = grad_images.to(torch.float32).contiguous()
-        return _attribute_images_adjoint(ctx.fragments, ctx.adjacency, g, ctx.batched, ctx.sizes), None, None, None
-
-
 # ---- the interior geometry gradient (csrc/d3m_fragment_geometry.h) ----------------------------------------------------------
 MAX_PIXEL_TERMS = 1 << 32  # B S S: one lane per internal pixel
 
@@ -236,18 +218,27 @@ def _geometry_adjoint(fr, A, pixel_grads, scratch):
     return grad
 
 
-class _VertexAttributeImagesGeometry(torch.autograd.Function):
-    """_VertexAttributeImages with the screen vertices as a second differentiable input: the same forward launch and the
-    same adjoint for the attributes; the vertices' gradient through the node's pixel_grads and the shared adjoint."""
+def _node_geometry_adjoint(fr, A, launch_pixel_grads):
+    """grad_screen_vertices of a node: launch_pixel_grads(c_fr, h) writes the node's dL/du into h [B,S,S,3], then the shared
+    adjoint; h and the adjoint's scratch are one uninitialised buffer"""
+    h, scratch = _geometry_scratch(fr, A, True)
+    c_fr = fr.c_struct()
+    launch_pixel_grads(ctypes.byref(c_fr), _lib.ptr(h))
+    return _geometry_adjoint(fr, A, h, scratch)
+
+
+class _VertexAttributeImages(torch.autograd.Function):
+    """screen_vertices: None, or the vertices the record was rasterised from as a second differentiable input -- the same
+    forward launch and the same adjoint for the attributes; the vertices' gradient through the node's pixel_grads and the
+    shared adjoint.  The attributes are kept for the backward only when the vertices need a gradient."""
     @staticmethod
     def forward(ctx, attributes, screen_vertices, fragments, adjacency, background):
-        fr = fragments
         attr = attributes.contiguous()
-        batched = attr.dim() == 3
-        V, C = attr.shape[-2:]
-        images, alpha = _attribute_images_launch(fr, attr, background)
-        ctx.save_for_backward(attr)
-        ctx.fragments, ctx.adjacency, ctx.batched, ctx.sizes = fr, adjacency, batched, (images.shape[0], V, C)
+        images, alpha = _attribute_images_launch(fragments, attr, background)
+        if ctx.needs_input_grad[1]:
+            ctx.save_for_backward(attr)
+        ctx.fragments, ctx.adjacency, ctx.batched = fragments, adjacency, attr.dim() == 3
+        ctx.sizes = (images.shape[0],) + tuple(attr.shape[-2:])
         ctx.mark_non_differentiable(alpha)
         return images, alpha
 
@@ -255,17 +246,14 @@ class _VertexAttributeImagesGeometry(torch.autograd.Function):
     def backward(ctx, grad_images, _grad_alpha):
         fr, A = ctx.fragments, ctx.adjacency
         B, V, C = ctx.sizes
-        attr, = ctx.saved_tensors
         g = grad_images.to(torch.float32).contiguous()
         grad_attr = _attribute_images_adjoint(fr, A, g, ctx.batched, ctx.sizes) if ctx.needs_input_grad[0] else None
         grad_sv = None
         if ctx.needs_input_grad[1]:
-            h, scratch = _geometry_scratch(fr, A, True)
-            c_fr = fr.c_struct()
-            _lib.check(_lib.lib().d3m_vertex_attribute_pixel_grads(ctypes.byref(c_fr), _lib.ptr(attr), B if ctx.batched else 1,
-                                                                   V, C, _lib.ptr(g), _lib.ptr(h), _lib.stream_ptr()),
-                       "d3m_vertex_attribute_pixel_grads")
-            grad_sv = _geometry_adjoint(fr, A, h, scratch)
+            attr, = ctx.saved_tensors
+            grad_sv = _node_geometry_adjoint(fr, A, lambda c_fr, h: _lib.check(_lib.lib().d3m_vertex_attribute_pixel_grads(
+                c_fr, _lib.ptr(attr), B if ctx.batched else 1, V, C, _lib.ptr(g), h, _lib.stream_ptr()),
+                "d3m_vertex_attribute_pixel_grads"))
         return grad_attr, grad_sv, None, None, None
 
 
@@ -304,6 +292,4 @@ def interpolate_vertex_attributes(attributes, fragments, background=None, cache=
     adjacency = vertex_adjacency(fragments.tri, V, cache)          # (where tri's indices are checked against V)
     if not attributes.is_cuda:
         raise ValueError("attributes and fragments must be on one GPU device")
-    if screen_vertices is not None and screen_vertices.requires_grad and torch.is_grad_enabled():
-        return _VertexAttributeImagesGeometry.apply(attributes, screen_vertices, fragments, adjacency, background)
-    return _VertexAttributeImages.apply(attributes, fragments, adjacency, background)
+    return _VertexAttributeImages.apply(attributes, screen_vertices, fragments, adjacency, background)

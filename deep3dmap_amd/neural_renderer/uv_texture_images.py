@@ -26,8 +26,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from .attributes import (_checked_background, _checked_fragments, _checked_screen_vertices, _geometry_adjoint,
-                         _geometry_scratch)
+from .attributes import _checked_background, _checked_fragments, _checked_screen_vertices, _node_geometry_adjoint
 from .row_gather import vertex_adjacency
 from .uv_textures import _wrapping_code
 
@@ -49,60 +48,48 @@ def uv_adjoint_fraction_bits(B, S):
     return 62 - (n - 1).bit_length()
 
 
+def _uv_outputs(fr, img):
+    """(images [B,C,s,s], alpha [B,s,s], the image's batch) of a contiguous image, uninitialised"""
+    B, s = fr.face_index_map.shape[0], int(fr.image_size)
+    images = torch.empty(B, img.shape[-1], s, s, dtype=torch.float32, device=img.device)
+    alpha = torch.empty(B, s, s, dtype=torch.float32, device=img.device)
+    return images, alpha, B if img.dim() == 4 else 1
+
+
 def _uv_images_launch(fr, img, faces_uv, wrapping, background):
     """(images, alpha) of a contiguous image: the plain bilinear forward's one launch"""
-    batched = img.dim() == 4
     H, W, C = img.shape[-3:]
-    B, s = fr.face_index_map.shape[0], int(fr.image_size)
-    images = torch.empty(B, C, s, s, dtype=torch.float32, device=img.device)
-    alpha = torch.empty(B, s, s, dtype=torch.float32, device=img.device)
+    images, alpha, ib = _uv_outputs(fr, img)
     c_fr = fr.c_struct()
-    _lib.check(_lib.lib().d3m_uv_texture_images(ctypes.byref(c_fr), _lib.ptr(faces_uv), _lib.ptr(img), B if batched else 1,
-                                                H, W, C, wrapping, _lib.ptr(background), _lib.ptr(images), _lib.ptr(alpha),
-                                                _lib.stream_ptr()), "d3m_uv_texture_images")
+    _lib.check(_lib.lib().d3m_uv_texture_images(ctypes.byref(c_fr), _lib.ptr(faces_uv), _lib.ptr(img), ib, H, W, C, wrapping,
+                                                _lib.ptr(background), _lib.ptr(images), _lib.ptr(alpha), _lib.stream_ptr()),
+               "d3m_uv_texture_images")
     return images, alpha
 
 
-def _uv_images_adjoint(fr, faces_uv, wrapping, g, batched, sizes):
-    """grad_image of the contiguous f32 image gradient g: the fixed-point scatter"""
+def _uv_images_adjoint(fr, g, batched, sizes, scratch_bytes, backward):
+    """grad_image of the contiguous f32 image gradient g, the fixed-point scatter: backward(c_fr, ib, scratch, bytes, grad)
+    is the plain or the mip-mapped entry point, scratch_bytes its scratch size for the image's batch ib"""
     B, H, W, C = sizes
-    L = _lib.lib()
     ib = B if batched else 1
-    n = int(L.d3m_uv_texture_images_scratch_bytes(ib, H, W, C, B, fr.raster_size))
-    scratch = torch.empty((n + 7) // 8, dtype=torch.int64, device=g.device)
+    scratch = torch.empty((int(scratch_bytes(ib)) + 7) // 8, dtype=torch.int64, device=g.device)
     grad = torch.empty((B, H, W, C) if batched else (H, W, C), dtype=torch.float32, device=g.device)
     c_fr = fr.c_struct()
-    _lib.check(L.d3m_uv_texture_images_backward(ctypes.byref(c_fr), _lib.ptr(faces_uv), _lib.ptr(g), ib, H, W, C, wrapping,
-                                                _lib.ptr(scratch), scratch.numel() * 8, _lib.ptr(grad), _lib.stream_ptr()),
-               "d3m_uv_texture_images_backward")
+    backward(ctypes.byref(c_fr), ib, _lib.ptr(scratch), scratch.numel() * 8, _lib.ptr(grad))
     return grad
 
 
 class _UvTextureImages(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, image, faces_uv, fragments, wrapping, background):
-        img = image.contiguous()
-        images, alpha = _uv_images_launch(fragments, img, faces_uv, wrapping, background)
-        ctx.fragments, ctx.faces_uv, ctx.wrapping, ctx.batched = fragments, faces_uv, wrapping, img.dim() == 4
-        ctx.sizes = (images.shape[0],) + tuple(img.shape[-3:])
-        ctx.mark_non_differentiable(alpha)
-        return images, alpha
-
-    @staticmethod
-    def backward(ctx, grad_images, _grad_alpha):
-        g = grad_images.to(torch.float32).contiguous()
-        return _uv_images_adjoint(ctx.fragments, ctx.faces_uv, ctx.wrapping, g, ctx.batched, ctx.sizes), None, None, None, None
-
-
-class _UvTextureImagesGeometry(torch.autograd.Function):
-    """_UvTextureImages with the screen vertices as a second differentiable input: the same forward launch and the same
-    adjoint for the image; the vertices' gradient through the node's pixel_grads and the shared interior adjoint
-    (csrc/d3m_fragment_geometry.h)."""
+    """screen_vertices: None, or the vertices the record was rasterised from as a second differentiable input -- the same
+    forward launch and the same adjoint for the image; the vertices' gradient through the node's pixel_grads and the shared
+    interior adjoint (csrc/d3m_fragment_geometry.h).  The image is kept for the backward only when the vertices need a
+    gradient."""
     @staticmethod
     def forward(ctx, image, screen_vertices, faces_uv, fragments, adjacency, wrapping, background):
         img = image.contiguous()
         images, alpha = _uv_images_launch(fragments, img, faces_uv, wrapping, background)
-        ctx.save_for_backward(img)
+        if ctx.needs_input_grad[1]:
+            ctx.save_for_backward(img)
         ctx.fragments, ctx.faces_uv, ctx.wrapping, ctx.batched = fragments, faces_uv, wrapping, img.dim() == 4
         ctx.adjacency, ctx.sizes = adjacency, (images.shape[0],) + tuple(img.shape[-3:])
         ctx.mark_non_differentiable(alpha)
@@ -110,21 +97,23 @@ class _UvTextureImagesGeometry(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_images, _grad_alpha):
-        fr, A = ctx.fragments, ctx.adjacency
+        fr, L = ctx.fragments, _lib.lib()
         B, H, W, C = ctx.sizes
-        img, = ctx.saved_tensors
+        uv, wrapping = _lib.ptr(ctx.faces_uv), ctx.wrapping
         g = grad_images.to(torch.float32).contiguous()
         grad_image = None
         if ctx.needs_input_grad[0]:
-            grad_image = _uv_images_adjoint(fr, ctx.faces_uv, ctx.wrapping, g, ctx.batched, ctx.sizes)
+            grad_image = _uv_images_adjoint(
+                fr, g, ctx.batched, ctx.sizes, lambda ib: L.d3m_uv_texture_images_scratch_bytes(ib, H, W, C, B, fr.raster_size),
+                lambda c_fr, ib, scratch, n, grad: _lib.check(L.d3m_uv_texture_images_backward(
+                    c_fr, uv, _lib.ptr(g), ib, H, W, C, wrapping, scratch, n, grad, _lib.stream_ptr()),
+                    "d3m_uv_texture_images_backward"))
         grad_sv = None
         if ctx.needs_input_grad[1]:
-            h, scratch = _geometry_scratch(fr, A, True)
-            c_fr = fr.c_struct()
-            _lib.check(_lib.lib().d3m_uv_texture_pixel_grads(ctypes.byref(c_fr), _lib.ptr(ctx.faces_uv), _lib.ptr(img),
-                                                             B if ctx.batched else 1, H, W, C, ctx.wrapping, _lib.ptr(g),
-                                                             _lib.ptr(h), _lib.stream_ptr()), "d3m_uv_texture_pixel_grads")
-            grad_sv = _geometry_adjoint(fr, A, h, scratch)
+            img, = ctx.saved_tensors
+            grad_sv = _node_geometry_adjoint(fr, ctx.adjacency, lambda c_fr, h: _lib.check(L.d3m_uv_texture_pixel_grads(
+                c_fr, uv, _lib.ptr(img), B if ctx.batched else 1, H, W, C, wrapping, _lib.ptr(g), h, _lib.stream_ptr()),
+                "d3m_uv_texture_pixel_grads"))
         return grad_image, grad_sv, None, None, None, None, None
 
 
@@ -187,37 +176,29 @@ class _UvTextureMipImages(torch.autograd.Function):
     def forward(ctx, image, faces_uv, fragments, wrapping, background, levels, lod_bias):
         fr = fragments
         img = image.contiguous()
-        batched = img.dim() == 4
         H, W, C = img.shape[-3:]
-        B, s = fr.face_index_map.shape[0], int(fr.image_size)
         pyramid = _build_pyramid(img, levels)                         # transient: the backward does not read it
-        images = torch.empty(B, C, s, s, dtype=torch.float32, device=img.device)
-        alpha = torch.empty(B, s, s, dtype=torch.float32, device=img.device)
+        images, alpha, ib = _uv_outputs(fr, img)
         c_fr = fr.c_struct()
-        _lib.check(_lib.lib().d3m_uv_texture_mip_images(ctypes.byref(c_fr), _lib.ptr(faces_uv), _lib.ptr(pyramid),
-                                                        B if batched else 1, H, W, C, wrapping, levels, lod_bias,
-                                                        _lib.ptr(background), _lib.ptr(images), _lib.ptr(alpha),
-                                                        _lib.stream_ptr()), "d3m_uv_texture_mip_images")
-        ctx.fragments, ctx.faces_uv, ctx.wrapping, ctx.batched, ctx.sizes = fr, faces_uv, wrapping, batched, (B, H, W, C)
-        ctx.levels, ctx.lod_bias = levels, lod_bias
+        _lib.check(_lib.lib().d3m_uv_texture_mip_images(ctypes.byref(c_fr), _lib.ptr(faces_uv), _lib.ptr(pyramid), ib, H, W, C,
+                                                        wrapping, levels, lod_bias, _lib.ptr(background), _lib.ptr(images),
+                                                        _lib.ptr(alpha), _lib.stream_ptr()), "d3m_uv_texture_mip_images")
+        ctx.fragments, ctx.faces_uv, ctx.wrapping, ctx.batched = fr, faces_uv, wrapping, img.dim() == 4
+        ctx.sizes, ctx.levels, ctx.lod_bias = (images.shape[0], H, W, C), levels, lod_bias
         ctx.mark_non_differentiable(alpha)
         return images, alpha
 
     @staticmethod
     def backward(ctx, grad_images, _grad_alpha):
-        fr = ctx.fragments
+        fr, L = ctx.fragments, _lib.lib()
         B, H, W, C = ctx.sizes
-        L = _lib.lib()
         g = grad_images.to(torch.float32).contiguous()
-        ib = B if ctx.batched else 1
-        n = int(L.d3m_uv_texture_mip_images_scratch_bytes(ib, H, W, C, ctx.levels, B, fr.raster_size))
-        scratch = torch.empty((n + 7) // 8, dtype=torch.int64, device=g.device)
-        grad = torch.empty((B, H, W, C) if ctx.batched else (H, W, C), dtype=torch.float32, device=g.device)
-        c_fr = fr.c_struct()
-        _lib.check(L.d3m_uv_texture_mip_images_backward(ctypes.byref(c_fr), _lib.ptr(ctx.faces_uv), _lib.ptr(g), ib, H, W, C,
-                                                        ctx.wrapping, ctx.levels, ctx.lod_bias, _lib.ptr(scratch),
-                                                        scratch.numel() * 8, _lib.ptr(grad), _lib.stream_ptr()),
-                   "d3m_uv_texture_mip_images_backward")
+        grad = _uv_images_adjoint(
+            fr, g, ctx.batched, ctx.sizes,
+            lambda ib: L.d3m_uv_texture_mip_images_scratch_bytes(ib, H, W, C, ctx.levels, B, fr.raster_size),
+            lambda c_fr, ib, scratch, n, grad: _lib.check(L.d3m_uv_texture_mip_images_backward(
+                c_fr, _lib.ptr(ctx.faces_uv), _lib.ptr(g), ib, H, W, C, ctx.wrapping, ctx.levels, ctx.lod_bias, scratch, n, grad,
+                _lib.stream_ptr()), "d3m_uv_texture_mip_images_backward"))
         return grad, None, None, None, None, None, None
 
 
@@ -285,11 +266,9 @@ def sample_uv_texture(image, faces_uv, fragments, texture_wrapping='REPEAT', bac
     background = _checked_background(background, C, image)
     if not image.is_cuda:
         raise ValueError("image and fragments must be on one GPU device")
-    if adjacency is not None:
-        return _UvTextureImagesGeometry.apply(image, screen_vertices, faces_uv.detach().contiguous(), fragments, adjacency,
-                                              wrapping, background)
     if levels == 0:
-        return _UvTextureImages.apply(image, faces_uv.detach().contiguous(), fragments, wrapping, background)
+        return _UvTextureImages.apply(image, screen_vertices if adjacency is not None else None, faces_uv.detach().contiguous(),
+                                      fragments, adjacency, wrapping, background)
     return _UvTextureMipImages.apply(image, faces_uv.detach().contiguous(), fragments, wrapping, background, levels, lod_bias)
 
 
