@@ -18,6 +18,7 @@
 #include "d3m_uv_texture.h"
 #include "d3m_uv_texture_mip.h"
 #include "d3m_fragment_geometry.h"
+#include "d3m_antialias.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -2878,6 +2879,77 @@ D3M_EXPORT int d3m_fragment_geometry_backward(const d3m_fragments* fragments, co
                    pixel_grads, (const int*)vis.list, (const int*)vis.count, scratch);
             LAUNCH("k_fragment_geometry_large_face_sums", k_fragment_geometry_large_face_sums, dim3(large_blocks),
                    dim3(RG_BLOCK), st, m, pixel_grads, (const int*)vis.list, (const int*)vis.count, scratch);
+        });
+}
+
+// Analytic edge antialiasing of an image drawn over a coverage record, and its silhouette gradient (d3m_antialias.h).
+// What the entry points refuse of the record and the sizes; `m`, `sc`: what the kernels read.
+static bool antialias_ok(const d3m_fragments* fr, const float* screen_vertices, int num_vertices, const int32_t* side_opposite,
+                         int num_channels, AttrMaps& m, AaScene& sc) {
+    if (!screen_vertices || !side_opposite || misaligned4(screen_vertices) || misaligned4(side_opposite)) return false;
+    if (!fragments_ok(fr, 1, num_vertices, num_channels, m) || m.aa) return false;
+    if ((unsigned long long)m.B * m.S * m.S > (1ull << 32)) return false;
+    sc = AaScene{screen_vertices, side_opposite, num_vertices};
+    return true;
+}
+
+D3M_EXPORT int d3m_antialias_images(const d3m_fragments* fragments, const float* images, int num_channels,
+                                    const float* screen_vertices, int num_vertices, const int32_t* side_opposite,
+                                    float* images_out, d3m_stream_t stream) {
+    AttrMaps m;
+    AaScene sc;
+    if (!images || !images_out || images == images_out || misaligned4(images) || misaligned4(images_out)) return D3M_ERR_INVALID;
+    if (!antialias_ok(fragments, screen_vertices, num_vertices, side_opposite, num_channels, m, sc)) return D3M_ERR_INVALID;
+    const long n_px = (long)m.B * m.S * m.S;
+    LAUNCH("k_antialias_images", k_antialias_images, dim3(blocks_for(n_px, 256)), dim3(256), (hipStream_t)stream, m, sc, images,
+           num_channels, images_out);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_antialias_images_backward(const d3m_fragments* fragments, const float* images, int num_channels,
+                                             const float* screen_vertices, int num_vertices, const int32_t* side_opposite,
+                                             const float* grad_out, float* grad_images, float* pair_grads,
+                                             d3m_stream_t stream) {
+    AttrMaps m;
+    AaScene sc;
+    if (!images || !grad_out || (!grad_images && !pair_grads)) return D3M_ERR_INVALID;
+    if (misaligned4(images) || misaligned4(grad_out) || misaligned4(grad_images) || misaligned4(pair_grads)) return D3M_ERR_INVALID;
+    if (grad_images == images || grad_images == grad_out) return D3M_ERR_INVALID;
+    if (!antialias_ok(fragments, screen_vertices, num_vertices, side_opposite, num_channels, m, sc)) return D3M_ERR_INVALID;
+    const long n_px = (long)m.B * m.S * m.S;
+    LAUNCH("k_antialias_images_backward", k_antialias_images_backward, dim3(blocks_for(n_px, 256)), dim3(256),
+           (hipStream_t)stream, m, sc, images, num_channels, grad_out, grad_images, pair_grads);
+    return check_launch();
+}
+
+D3M_EXPORT size_t d3m_antialias_scratch_floats(int batch_size, int num_faces, int raster_size, const d3m_csr* adjacency,
+                                               int with_pair_grads) {
+    const size_t sums = d3m_fragment_geometry_scratch_floats(batch_size, num_faces, raster_size, adjacency, 0);
+    if (sums == 0) return 0;
+    return sums + (with_pair_grads ? (size_t)batch_size * raster_size * raster_size * 4 : 0);
+}
+
+D3M_EXPORT int d3m_antialias_geometry_backward(const d3m_fragments* fragments, const float* pair_grads,
+                                               const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
+                                               float* grad_screen_vertices, int num_vertices, d3m_stream_t stream) {
+    AttrMaps m;
+    if (!pair_grads || !scratch || !grad_screen_vertices) return D3M_ERR_INVALID;
+    if (misaligned4(pair_grads) || misaligned4(scratch) || misaligned4(grad_screen_vertices)) return D3M_ERR_INVALID;
+    if (!fragment_geometry_ok(fragments, num_vertices, m) || m.aa) return D3M_ERR_INVALID;
+    if ((long)m.Ft * 3 > 0x7FFFFFFFl) return D3M_ERR_INVALID;          // items are int32
+    const long nf = (long)m.B * m.Fp;
+    if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
+    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if (scratch_floats < d3m_antialias_scratch_floats(m.B, m.Fp, m.S, adjacency, 0)) return D3M_ERR_WORKSPACE;
+    const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
+    // Gv has G's layout with C = 3, and the result is per view: stage 2 is d3m_fragment_geometry_backward's
+    return face_sums_gather(
+        m, vis, *adjacency, scratch, num_vertices, 3, false, grad_screen_vertices, (hipStream_t)stream,
+        [&](unsigned small_blocks, unsigned large_blocks, hipStream_t st) {
+            LAUNCH("k_antialias_face_sums", k_antialias_face_sums, dim3(small_blocks), dim3(256), st, m, pair_grads,
+                   (const int*)vis.list, (const int*)vis.count, scratch);
+            LAUNCH("k_antialias_large_face_sums", k_antialias_large_face_sums, dim3(large_blocks), dim3(RG_BLOCK), st, m,
+                   pair_grads, (const int*)vis.list, (const int*)vis.count, scratch);
         });
 }
 

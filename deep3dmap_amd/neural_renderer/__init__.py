@@ -1,5 +1,6 @@
 """MI355X-native mirror of the `neural_renderer` package surface deep3dmap imports
 (pnpmodules/neural_renderer/neural_renderer/__init__.py:1-12)."""
+from .antialias import antialias
 from .attributes import Fragments, interpolate_vertex_attributes, rasterize_fragments
 from .cameras import get_points_from_angles, look, look_at, perspective, projection
 from .fragment_geometry import fragment_weights

@@ -270,8 +270,8 @@ def interpolate_vertex_attributes(attributes, fragments, background=None, cache=
     forward launch and the same bits of images, alpha and the attributes' gradient, and in addition the INTERIOR geometry
     gradient reaches screen_vertices.grad: the derivative of the weights u_c of every owned pixel with respect to the
     owner's corners (csrc/d3m_fragment_geometry.h), in a fixed order.  Coverage stays a constant -- no gradient from a
-    pixel changing its owner or from the silhouette, which render_silhouettes / render give.  Vertices that do not require
-    grad launch nothing extra."""
+    pixel changing its owner or from the silhouette, which render_silhouettes / render give, and antialias (antialias.py)
+    for the drawn image itself.  Vertices that do not require grad launch nothing extra."""
     if not torch.is_tensor(attributes) or attributes.dim() not in (2, 3):
         raise ValueError("attributes must be [num_vertices, C] or [B, num_vertices, C]")
     if attributes.dtype != torch.float32:

@@ -10,7 +10,8 @@ states it and the order of every sum: per visible face over the pixels it owns, 
 no float atomics, nothing cleared, the same bits on every run).
 
 What is NOT differentiated: coverage.  Which face owns which pixel is a constant of the graph, so nothing here sees a pixel
-changing its owner or the silhouette moving: that gradient is render_silhouettes' / render's.  The caller passes the vertices
+changing its owner or the silhouette moving: that gradient is render_silhouettes' / render's, or antialias' (antialias.py)
+over the drawn image.  The caller passes the vertices
 the record was rasterised from; only their shape, dtype, device and V can be checked."""
 import ctypes
 

@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import attributes as _attributes, cameras, mesh_ops, uv_texture_images as _uv_texture_images
+from .antialias import antialias as _antialias_images
 from .rasterize import (light_on_device, rasterize, rasterize_depth, rasterize_lit, rasterize_lit_fit,
                         rasterize_lit_image_grid, rasterize_mesh_modes, rasterize_rgbad, rasterize_silhouettes)
 
@@ -211,17 +212,35 @@ class Renderer(nn.Module):
                                                self.far)
 
     def render_attributes(self, vertices, faces, attributes, background=None, K=None, R=None, t=None, dist_coeffs=None,
-                          orig_size=None, geometry_grad=False):
+                          orig_size=None, geometry_grad=False, antialias=False):
         """(images [B,C,s,s], alpha [B,s,s]) of per-vertex attributes [V,C] or [B,V,C]: fragments() followed by
         interpolate_vertex_attributes, differentiable in the attributes only.  geometry_grad=True: the screen vertices stay
         in the graph (the record is made from their detached values) and are passed on as interpolate_vertex_attributes'
         screen_vertices, so the INTERIOR geometry gradient reaches `vertices` and any learnable camera tensor through the
-        camera operators; coverage stays a constant (the silhouette gradient is render_silhouettes' / render's)."""
-        if geometry_grad:
+        camera operators; coverage stays a constant (the silhouette gradient is render_silhouettes' / render's, or
+        antialias=True's).  antialias=True (a renderer with anti_aliasing=False only: ValueError before any launch
+        otherwise; C + 1 <= 1024): the screen vertices stay in the graph as well and images and alpha -- alpha as channel C of
+        one nr.antialias call -- come back antialiased along the silhouette, so the SILHOUETTE gradient reaches `vertices`
+        through both; with geometry_grad=True the two gradients add in autograd."""
+        self._check_antialias(antialias)
+        if geometry_grad or antialias:
             fr, sv = self._fragments_with_vertices(vertices, faces, K, R, t, dist_coeffs, orig_size)
-            return _attributes.interpolate_vertex_attributes(attributes, fr, background, screen_vertices=sv)
+            images, alpha = _attributes.interpolate_vertex_attributes(attributes, fr, background,
+                                                                      screen_vertices=sv if geometry_grad else None)
+            return self._antialiased(images, alpha, fr, sv) if antialias else (images, alpha)
         fr = self.fragments(vertices, faces, K, R, t, dist_coeffs, orig_size)
         return _attributes.interpolate_vertex_attributes(attributes, fr, background)
+
+    def _check_antialias(self, antialias):
+        if antialias and self.anti_aliasing:
+            raise ValueError("antialias=True needs a renderer with anti_aliasing=False (the 2x2 pooling of anti_aliasing "
+                             "already antialiases; nr.antialias refuses a supersampled record)")
+
+    @staticmethod
+    def _antialiased(images, alpha, fr, sv):
+        """(images, alpha) through ONE nr.antialias call: alpha rides as channel C and is split off again"""
+        out = _antialias_images(torch.cat((images, alpha[:, None]), 1), fr, sv)
+        return out[:, :-1], out[:, -1]
 
     def _fragments_with_vertices(self, vertices, faces, K, R, t, dist_coeffs, orig_size):
         """(the coverage record of the detached screen vertices, the screen vertices in the graph)"""
@@ -231,21 +250,31 @@ class Renderer(nn.Module):
         return fr, sv
 
     def render_uv_texture(self, vertices, faces, image, faces_uv, texture_wrapping='REPEAT', background=None, K=None, R=None,
-                          t=None, dist_coeffs=None, orig_size=None, mipmap=None, lod_bias=0.0, geometry_grad=False):
+                          t=None, dist_coeffs=None, orig_size=None, mipmap=None, lod_bias=0.0, geometry_grad=False,
+                          antialias=False):
         """(images [B,C,s,s], alpha [B,s,s]) of a texture image [H,W,C] or [B,H,W,C] looked up at every pixel's interpolated
         uv (faces_uv [F,3,2]): fragments() followed by sample_uv_texture, differentiable in the image only.  mipmap, lod_bias:
         sample_uv_texture's (a trilinear lookup in a box pyramid of the image).  geometry_grad=True: as in
         render_attributes -- the interior geometry gradient reaches `vertices` and learnable camera tensors; plain bilinear
         lookup only (NotImplementedError with mipmap, raised before anything is launched), faces_uv and coverage stay
-        constants."""
+        constants.  antialias=True: as in render_attributes -- images and alpha antialiased along the silhouette by one
+        nr.antialias call, whose silhouette gradient reaches `vertices`; mipmap is allowed (the lookup itself stays a
+        constant of the vertices unless geometry_grad=True)."""
+        self._check_antialias(antialias)
         if geometry_grad:
             if torch.is_tensor(image) and image.dim() >= 3 and _uv_texture_images.mip_levels(*image.shape[-3:-1], mipmap):
                 # known from the arguments alone: refused before the camera operators and the rasteriser launch
                 raise NotImplementedError("render_uv_texture: no geometry gradient with mipmap (the level of detail depends "
                                           "on the geometry); pass mipmap=None or geometry_grad=False")
+        if geometry_grad or antialias:
             fr, sv = self._fragments_with_vertices(vertices, faces, K, R, t, dist_coeffs, orig_size)
-            return _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background, mipmap, lod_bias,
-                                                        screen_vertices=sv)
+            if geometry_grad:
+                images, alpha = _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background, mipmap,
+                                                                     lod_bias, screen_vertices=sv)
+            else:
+                images, alpha = _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background, mipmap,
+                                                                     lod_bias)
+            return self._antialiased(images, alpha, fr, sv) if antialias else (images, alpha)
         fr = self.fragments(vertices, faces, K, R, t, dist_coeffs, orig_size)
         return _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background, mipmap, lod_bias)
 

@@ -1159,6 +1159,43 @@ int d3m_uv_texture_pixel_grads(const d3m_fragments* fragments, const float* face
 int d3m_fragment_geometry_backward(const d3m_fragments* fragments, const float* pixel_grads, const d3m_csr* adjacency,
                                    float* scratch, size_t scratch_floats, float* grad_screen_vertices, int num_vertices,
                                    d3m_stream_t stream);
+/* Analytic edge antialiasing of an image drawn over a coverage record, and its silhouette gradient (an addition;
+ * csrc/d3m_antialias.h states the function, the pair decision and the order of every sum).  The record must be one without
+ * anti-aliasing (S = image_size) that d3m_forward_face_index_map_mesh made from screen_vertices [B, V, 3];  side_opposite
+ * [num_tri, 3] i32: per side j (corner j to j + 1) of a triangle the third vertex of the one other triangle on that undirected
+ * edge, -1 for a boundary side, -2 for a side the node leaves alone (three or more triangles on it, a triangle that repeats an
+ * index); an entry outside [-1, V) counts as -2.  images [B, C, S, S] in output orientation (row 0 = top).
+ * d3m_antialias_images WRITES every element of images_out [B, C, S, S]: the image with the two pixels on either side of
+ * every silhouette edge blended by the edge's position between their centres; a pixel of no such pair keeps its bits.  One
+ * launch (k_antialias_images).  D3M_ERR_INVALID, before any launch: what d3m_vertex_attribute_images refuses of the record
+ * and of num_vertices / num_channels, a record with anti_aliasing, B S S beyond 2^32, a NULL or misaligned images /
+ * screen_vertices / side_opposite / images_out, images_out == images. */
+int d3m_antialias_images(const d3m_fragments* fragments, const float* images, int num_channels, const float* screen_vertices,
+                         int num_vertices, const int32_t* side_opposite, float* images_out, d3m_stream_t stream);
+/* The adjoint with respect to the image and the derivative with respect to every pair's edge position, for grad_out [B, C,
+ * S, S]: grad_images [B, C, S, S] (NULL: not formed), every element WRITTEN, and pair_grads [B, S, S, 4] in map orientation
+ * (NULL: not formed), every element WRITTEN: slot -x, +x, -y, +y of a pixel holds dL/dt of that pair when the pixel is the
+ * pair's near pixel, else +0.  A gather: no atomics, nothing cleared.  One launch (k_antialias_images_backward).
+ * D3M_ERR_INVALID, before any launch: what d3m_antialias_images refuses (images_out aside), a NULL or misaligned grad_out,
+ * both results NULL, a misaligned result, grad_images == images or grad_out. */
+int d3m_antialias_images_backward(const d3m_fragments* fragments, const float* images, int num_channels,
+                                  const float* screen_vertices, int num_vertices, const int32_t* side_opposite,
+                                  const float* grad_out, float* grad_images, float* pair_grads, d3m_stream_t stream);
+/* Floats of scratch of d3m_antialias_geometry_backward: d3m_fragment_geometry_scratch_floats(..., 0)'s B F' 9 per-face sums
+ * and 3 B num_chunks chunk sums; with_pair_grads != 0: and 4 B S S more, room for a pair_grads map.  0 for sizes that are
+ * refused. */
+size_t d3m_antialias_scratch_floats(int batch_size, int num_faces, int raster_size, const d3m_csr* adjacency,
+                                    int with_pair_grads);
+/* pair_grads [B, S, S, 4] (d3m_antialias_images_backward's) -> grad_screen_vertices [B, V, 3], every element WRITTEN: x and y
+ * of the two end vertices of every silhouette edge a pair chose; the z column, and a vertex on no such edge, get +0.
+ * adjacency: the faces' d3m_csr of V rows (item = 3 f + c).  scratch needs no initialisation.  No float atomics, nothing
+ * cleared; three launches (k_antialias_face_sums, k_antialias_large_face_sums, k_vertex_attribute_adjoint_rows) and
+ * k_vertex_attribute_adjoint_chunks on a mesh with long rows.  D3M_ERR_INVALID, before any launch: what
+ * d3m_fragment_geometry_backward refuses (pair_grads in the place of pixel_grads), a record with anti_aliasing;
+ * D3M_ERR_WORKSPACE: scratch_floats below d3m_antialias_scratch_floats(..., 0). */
+int d3m_antialias_geometry_backward(const d3m_fragments* fragments, const float* pair_grads, const d3m_csr* adjacency,
+                                    float* scratch, size_t scratch_floats, float* grad_screen_vertices, int num_vertices,
+                                    d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
