@@ -274,16 +274,25 @@ __device__ __forceinline__ void sample_pixel_lit(const float* __restrict__ faces
         }
         const float* li = lt.light + 3 * ((size_t)(lt.light_batch > 1 ? bn : 0) * lt.Fp + fi);
         const float l0 = li[0], l1 = li[1], l2 = li[2];
+        // corner pn reads texel isc = rev(pn) (bits 0 and 2 of pn change places) of an original and texel pn = (c,b,a) of
+        // its back copy: the two differ in texels 1 <-> 4 and 3 <-> 6 alone.  The cube is brought into CORNER order here,
+        // once per pixel (12 selects), and the loop indexes it at compile time -- `tex[back ? pn : rev]` is a per-lane
+        // index into registers, which the compiler turned into a 23-way compare / select chain per read: 814 of the 929
+        // instructions this branch had in k_render_lit_fit_records<32> (docs/EXPERIMENTS.md Q)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float t1 = tex[3 + c], t4 = tex[12 + c], t3 = tex[9 + c], t6 = tex[18 + c];
+            tex[3 + c] = back ? t1 : t4; tex[12 + c] = back ? t4 : t1;
+            tex[9 + c] = back ? t3 : t6; tex[18 + c] = back ? t6 : t3;
+        }
 #pragma unroll
         for (int pn = 0; pn < 8; pn++) {
             float w;
             int isc;
             sample_corner(pn, 2, fl, fr, w, isc);
-            const int rev = ((pn & 1) << 2) | (pn & 2) | ((pn >> 2) & 1);      // = isc
-            const int idx = back ? pn : rev;                                    // back copy: texel (c,b,a)
-            px[0] += w * (tex[idx * 3 + 0] * l0);
-            px[1] += w * (tex[idx * 3 + 1] * l1);
-            px[2] += w * (tex[idx * 3 + 2] * l2);
+            px[0] += w * (tex[pn * 3 + 0] * l0);
+            px[1] += w * (tex[pn * 3 + 1] * l1);
+            px[2] += w * (tex[pn * 3 + 2] * l2);
         }
         return;
     }
@@ -540,8 +549,11 @@ __global__ void __launch_bounds__(256) k_fit_target_summary(const float* __restr
     if (threadIdx.x == 0) target_void[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = any ? 0 : 1;
 }
 
-// (4 waves per SIMD: the compiler wants 134 registers, six more than four waves allow; held to 128 the pass -- bound by its
-//  memory round trips, i.e. by how many of them are in flight -- takes 0.198 instead of 0.233 ms alone; 5 waves spill: 0.35)
+// (4 waves per SIMD.  While sample_pixel_lit indexed its texel cube per lane the compiler wanted 134 registers -- most of them
+//  the select chains' live range -- six more than four waves allow; held to 128 the pass took 0.198 instead of 0.233 ms alone,
+//  and 5 waves spilled: 0.35.  With the cube in corner order <32> takes 102 registers and <16> 88 (it runs at 5 waves as it
+//  is); held to the 96 of 5 waves <32> still goes to scratch -- 24 bytes per lane, the epilogue 52 -- so 5 was not timed
+//  again: docs/EXPERIMENTS.md)
 #ifndef D3M_FIT_MINWAVES
 #define D3M_FIT_MINWAVES 4
 #endif
