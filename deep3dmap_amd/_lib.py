@@ -230,6 +230,11 @@ _SIGNATURES = {
     "d3m_vertex_attribute_pixel_grads": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _I, _I, _P, _P, _P]),
     "d3m_uv_texture_pixel_grads": (_I, [ctypes.POINTER(D3MFragments), _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "d3m_fragment_geometry_backward": (_I, [ctypes.POINTER(D3MFragments), _P, ctypes.POINTER(D3MCsr), _P, _SZ, _P, _I, _P]),
+    "d3m_sh_fragment_images": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
+    "d3m_sh_fragment_scratch_floats": (_SZ, [_I, _I, _I, _I, ctypes.POINTER(D3MCsr)]),
+    "d3m_sh_fragment_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _I, _I, _P, ctypes.POINTER(D3MCsr),
+                                             _P, _SZ, _P, _I, _P, _P, _P]),
+    "d3m_sh_fragment_pixel_grads": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _I, _I, _P, _P, _P]),
     "d3m_antialias_images": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _P, _P]),
     "d3m_antialias_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "d3m_antialias_scratch_floats": (_SZ, [_I, _I, _I, ctypes.POINTER(D3MCsr), _I]),

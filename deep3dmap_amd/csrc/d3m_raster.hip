@@ -18,6 +18,7 @@
 #include "d3m_uv_texture.h"
 #include "d3m_uv_texture_mip.h"
 #include "d3m_fragment_geometry.h"
+#include "d3m_sh_fragments.h"
 #include "d3m_antialias.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
@@ -2880,6 +2881,118 @@ D3M_EXPORT int d3m_fragment_geometry_backward(const d3m_fragments* fragments, co
             LAUNCH("k_fragment_geometry_large_face_sums", k_fragment_geometry_large_face_sums, dim3(large_blocks),
                    dim3(RG_BLOCK), st, m, pixel_grads, (const int*)vis.list, (const int*)vis.count, scratch);
         });
+}
+
+// Per-pixel spherical-harmonic shading over a coverage record (d3m_sh_fragments.h).  What the entry points refuse of the record
+// and the inputs; `m`, `in`: what the kernels read.  One lane per internal pixel in the backward: B S S within 2^32.
+static bool sh_fragments_ok(const d3m_fragments* fr, const float* normals, int normals_batch, const float* sh, int sh_batch,
+                            const float* colors, int colors_batch, int num_vertices, AttrMaps& m, ShfInputs& in) {
+    if (!normals || !sh || misaligned4(normals) || misaligned4(sh) || misaligned4(colors)) return false;
+    if (!fragments_ok(fr, normals_batch, num_vertices, 3, m)) return false;
+    if ((sh_batch != 1 && sh_batch != m.B) || (colors_batch != 1 && colors_batch != m.B)) return false;
+    if ((unsigned long long)m.B * m.S * m.S > (1ull << 32)) return false;
+    in = ShfInputs{normals, colors, sh, normals_batch, colors ? colors_batch : 1, sh_batch, num_vertices};
+    return true;
+}
+
+D3M_EXPORT int d3m_sh_fragment_images(const d3m_fragments* fragments, const float* normals, int normals_batch, const float* sh,
+                                      int sh_batch, const float* colors, int colors_batch, int num_vertices,
+                                      const float* background, float* images, float* alpha, d3m_stream_t stream) {
+    AttrMaps m;
+    ShfInputs in;
+    if (!images || !alpha || misaligned4(background) || misaligned4(images) || misaligned4(alpha)) return D3M_ERR_INVALID;
+    if (!sh_fragments_ok(fragments, normals, normals_batch, sh, sh_batch, colors, colors_batch, num_vertices, m, in))
+        return D3M_ERR_INVALID;
+    const long n = (long)fragments->image_size * fragments->image_size;
+    LAUNCH("k_sh_fragment_images", k_sh_fragment_images, dim3(blocks_for(n, 256), m.B), dim3(256), (hipStream_t)stream, m, in,
+           background, images, alpha);
+    return check_launch();
+}
+
+D3M_EXPORT size_t d3m_sh_fragment_scratch_floats(int batch_size, int num_faces, int raster_size, int with_colors,
+                                                 const d3m_csr* adjacency) {
+    if (raster_size < 1 || raster_size > 32768 || (unsigned long long)std::max(batch_size, 0) * raster_size * raster_size > (1ull << 32))
+        return 0;
+    const int C = with_colors ? 6 : 3;
+    const size_t sums = d3m_vertex_attribute_scratch_floats(batch_size, num_faces, C, adjacency);
+    if (sums == 0) return 0;
+    const size_t S2 = (size_t)raster_size * raster_size;
+    return sums + (size_t)batch_size * S2 * C + (size_t)batch_size * shf_parts((long)S2) * SHF_SUMS;
+}
+
+D3M_EXPORT int d3m_sh_fragment_images_backward(const d3m_fragments* fragments, const float* normals, int normals_batch,
+                                               const float* sh, int sh_batch, const float* colors, int colors_batch,
+                                               int num_vertices, const float* grad_images, const d3m_csr* adjacency,
+                                               float* scratch, size_t scratch_floats, float* grad_vertex, int vertex_grads,
+                                               float* grad_sh, float* pixel_grads, d3m_stream_t stream) {
+    AttrMaps m;
+    ShfInputs in;
+    if (!grad_images || !scratch || (!grad_vertex && !grad_sh && !pixel_grads)) return D3M_ERR_INVALID;
+    if (vertex_grads < 0 || vertex_grads > 3 || (vertex_grads != 0) != (grad_vertex != nullptr)) return D3M_ERR_INVALID;
+    if ((vertex_grads & 2) && !colors) return D3M_ERR_INVALID;
+    if (misaligned4(grad_images) || misaligned4(scratch) || misaligned4(grad_vertex) || misaligned4(grad_sh) ||
+        misaligned4(pixel_grads))
+        return D3M_ERR_INVALID;
+    if (!sh_fragments_ok(fragments, normals, normals_batch, sh, sh_batch, colors, colors_batch, num_vertices, m, in))
+        return D3M_ERR_INVALID;
+    if ((long)m.Ft * 3 > 0x7FFFFFFFl) return D3M_ERR_INVALID;          // items are int32
+    const long nf = (long)m.B * m.Fp;
+    if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
+    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if (scratch_floats < d3m_sh_fragment_scratch_floats(m.B, m.Fp, m.S, colors != nullptr, adjacency)) return D3M_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t S2 = (size_t)m.S * m.S;
+    const int parts = shf_parts((long)S2), C = colors ? 6 : 3;
+    const bool want_n = vertex_grads & 1, want_c = vertex_grads & 2;
+    const bool one_gather = want_n && want_c && colors_batch == normals_batch;
+    // the scratch: the gather's own (d3m_vertex_attribute_scratch_floats of C channels), then Q, then the sh partials.  Q: one
+    // gather -- [B,6,S,S]; else a [B,3,S,S] block per wanted gradient, the normals' first
+    float* Q = scratch + d3m_vertex_attribute_scratch_floats(m.B, m.Fp, C, adjacency);
+    float* sh_partial = Q + (size_t)m.B * S2 * C;
+    float* Qn = want_n ? Q : nullptr;
+    float* Qc = want_c ? Q + (one_gather ? 3 * S2 : (want_n ? (size_t)m.B * 3 * S2 : 0)) : nullptr;
+    LAUNCH("k_sh_fragment_backward_pixels", k_sh_fragment_backward_pixels, dim3(parts, m.B), dim3(SET_BLOCK), st, m, in,
+           grad_images, Qn, Qc, one_gather ? 6 * S2 : 3 * S2, pixel_grads, grad_sh ? sh_partial : (float*)nullptr);
+    if (grad_sh)
+        LAUNCH("k_sh_fragment_finish", k_sh_fragment_finish, dim3(blocks_for((long)sh_batch * SHF_SUMS, SET_BLOCK)),
+               dim3(SET_BLOCK), st, (const float*)sh_partial, parts, grad_sh, sh_batch, m.B);
+    if (!grad_vertex) return check_launch();
+    // Q is the image gradient of the record re-labelled image_size = S, anti_aliasing = 0 over the same maps
+    AttrMaps mq = m;
+    mq.aa = 0;
+    const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
+    auto gather = [&](const float* g, int channels, bool shared, float* grad) {
+        const unsigned c_chunks = (channels + VA_CHUNK - 1) / VA_CHUNK;
+        return face_sums_gather(
+            mq, vis, *adjacency, scratch, num_vertices, channels, shared, grad, st,
+            [&](unsigned small_blocks, unsigned large_blocks, hipStream_t s2) {
+                LAUNCH("k_vertex_attribute_face_sums", k_vertex_attribute_face_sums, dim3(small_blocks, c_chunks), dim3(256), s2,
+                       mq, g, channels, (const int*)vis.list, (const int*)vis.count, scratch);
+                LAUNCH("k_vertex_attribute_large_face_sums", k_vertex_attribute_large_face_sums, dim3(large_blocks, c_chunks),
+                       dim3(RG_BLOCK), s2, mq, g, channels, (const int*)vis.list, (const int*)vis.count, scratch);
+            });
+    };
+    if (one_gather) return gather(Q, 6, normals_batch == 1, grad_vertex);
+    int rc = D3M_OK;
+    if (want_n) rc = gather(Qn, 3, normals_batch == 1, grad_vertex);
+    if (rc == D3M_OK && want_c)
+        rc = gather(Qc, 3, colors_batch == 1, grad_vertex + (want_n ? (size_t)normals_batch * num_vertices * 3 : 0));
+    return rc;
+}
+
+D3M_EXPORT int d3m_sh_fragment_pixel_grads(const d3m_fragments* fragments, const float* normals, int normals_batch,
+                                           const float* sh, int sh_batch, const float* colors, int colors_batch,
+                                           int num_vertices, const float* grad_images, float* pixel_grads,
+                                           d3m_stream_t stream) {
+    AttrMaps m;
+    ShfInputs in;
+    if (!grad_images || !pixel_grads || misaligned4(grad_images) || misaligned4(pixel_grads)) return D3M_ERR_INVALID;
+    if (!sh_fragments_ok(fragments, normals, normals_batch, sh, sh_batch, colors, colors_batch, num_vertices, m, in))
+        return D3M_ERR_INVALID;
+    LAUNCH("k_sh_fragment_backward_pixels", k_sh_fragment_backward_pixels, dim3(shf_parts((long)m.S * m.S), m.B),
+           dim3(SET_BLOCK), (hipStream_t)stream, m, in, grad_images, (float*)nullptr, (float*)nullptr, (size_t)0, pixel_grads,
+           (float*)nullptr);
+    return check_launch();
 }
 
 // Analytic edge antialiasing of an image drawn over a coverage record, and its silhouette gradient (d3m_antialias.h).

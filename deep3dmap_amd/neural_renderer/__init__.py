@@ -13,6 +13,7 @@ from .pose import PoseHead, PosedPoints, pose_vertices
 from .rasterize import (Rasterize, RasterizeFunction, rasterize, rasterize_depth, rasterize_rgbad,
                         rasterize_silhouettes)
 from .renderer import Renderer
+from .sh_fragments import shade_fragments
 from .smooth_shading import SHLight, sh_basis, sh_vertex_colors, vertex_normals
 from .uv_texture_images import sample_uv_texture, texture_mip_pyramid, uv_texture_lod
 from .uv_textures import UVTextures, textures_from_image

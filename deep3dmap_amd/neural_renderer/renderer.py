@@ -8,7 +8,8 @@ import numpy
 import torch
 import torch.nn as nn
 
-from . import attributes as _attributes, cameras, mesh_ops, uv_texture_images as _uv_texture_images
+from . import (attributes as _attributes, cameras, mesh_ops, sh_fragments as _sh_fragments, smooth_shading as _smooth_shading,
+               uv_texture_images as _uv_texture_images)
 from .antialias import antialias as _antialias_images
 from .rasterize import (light_on_device, rasterize, rasterize_depth, rasterize_lit, rasterize_lit_fit,
                         rasterize_lit_image_grid, rasterize_mesh_modes, rasterize_rgbad, rasterize_silhouettes)
@@ -277,6 +278,26 @@ class Renderer(nn.Module):
             return self._antialiased(images, alpha, fr, sv) if antialias else (images, alpha)
         fr = self.fragments(vertices, faces, K, R, t, dist_coeffs, orig_size)
         return _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background, mipmap, lod_bias)
+
+    def render_sh_shaded(self, vertices, faces, sh, colors=None, normals=None, background=None, K=None, R=None, t=None,
+                         dist_coeffs=None, orig_size=None, geometry_grad=False, antialias=False):
+        """(images [B,3,s,s], alpha [B,s,s]) of the mesh lit PER PIXEL by the spherical-harmonic light sh [3,9] or [B,3,9]:
+        fragments() followed by shade_fragments (sh_fragments.py), differentiable in sh, colors (per-vertex albedo [V,3] or
+        [B,V,3], or None) and normals.  normals=None takes nr.vertex_normals(vertices, faces) IN THE GRAPH -- the smooth
+        normals in the frame of `vertices`, so the light's gradient reaches the vertices through the normals as well; given
+        normals [V,3] or [B,V,3] are the caller's, in whatever frame the light lives in.  geometry_grad / antialias: as in
+        render_attributes (the interior geometry gradient through shade_fragments' screen_vertices; the silhouette gradient
+        through one nr.antialias call, a renderer with anti_aliasing=False only: ValueError before any launch otherwise)."""
+        self._check_antialias(antialias)
+        if normals is None:
+            normals = _smooth_shading.vertex_normals(vertices, faces)
+        if geometry_grad or antialias:
+            fr, sv = self._fragments_with_vertices(vertices, faces, K, R, t, dist_coeffs, orig_size)
+            images, alpha = _sh_fragments.shade_fragments(normals, sh, fr, colors, background,
+                                                          screen_vertices=sv if geometry_grad else None)
+            return self._antialiased(images, alpha, fr, sv) if antialias else (images, alpha)
+        fr = self.fragments(vertices.detach() if torch.is_tensor(vertices) else vertices, faces, K, R, t, dist_coeffs, orig_size)
+        return _sh_fragments.shade_fragments(normals, sh, fr, colors, background)
 
     def render_rgb_image_grid(self, vertices, image, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         """render_rgb of the grid mesh of a depth map (vertices [B,h*w,3], one per pixel, row-major) textured by `image`

@@ -188,7 +188,8 @@ class SHLight(nn.Module):
     """A spherical-harmonic light as a learnable parameter: `sh` [3,9], or [per_set,3,9] with per_set sets, initialised to
     white ambient (sh[..., 0] = 1 / a0, the rest 0: shaded = colors up to rounding).  forward(vertices, faces, colors) returns
     sh_vertex_colors' shaded colours; the module keeps the adjacency of the faces it last saw itself, so whatever holds the
-    module (a captured step) keeps the adjacency."""
+    module (a captured step) keeps the adjacency.  shade(normals, fragments, colors=None) lights a Fragments record per pixel
+    with the same coefficients (sh_fragments.py)."""
 
     def __init__(self, per_set=None):
         super().__init__()
@@ -201,3 +202,10 @@ class SHLight(nn.Module):
 
     def forward(self, vertices, faces, colors, return_normals=False):
         return sh_vertex_colors(vertices, faces, colors, self.sh, cache=self._adjacency, return_normals=return_normals)
+
+    def shade(self, normals, fragments, colors=None, **kw):
+        """(images [B,3,s,s], alpha [B,s,s]) of this light PER PIXEL over a Fragments record: sh_fragments.shade_fragments
+        with the module's coefficients (per_set must then be None or the record's views); kw: its background, cache and
+        screen_vertices."""
+        from .sh_fragments import shade_fragments
+        return shade_fragments(normals, self.sh, fragments, colors=colors, **kw)

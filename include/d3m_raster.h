@@ -1159,6 +1159,48 @@ int d3m_uv_texture_pixel_grads(const d3m_fragments* fragments, const float* face
 int d3m_fragment_geometry_backward(const d3m_fragments* fragments, const float* pixel_grads, const d3m_csr* adjacency,
                                    float* scratch, size_t scratch_floats, float* grad_screen_vertices, int num_vertices,
                                    d3m_stream_t stream);
+/* Per-pixel spherical-harmonic shading over a coverage record (an addition; csrc/d3m_sh_fragments.h states the function and
+ * the order of every sum): normals [normals_batch, V, 3] and, optionally, colors [colors_batch, V, 3] (NULL: none) are
+ * interpolated at every pixel with the weights of d3m_vertex_attribute_images, the normal is normalised per pixel (m / max(|m|,
+ * 1e-6)) and lit by sh [sh_batch, 3, 9] (channel, basis term; the basis of d3m_smooth_shade_forward): value_k = a_k sum_j
+ * sh[k,j] H_j(n).  Each batch is 1 (shared by the views) or B.  background [3] or NULL (zeros).  WRITES every element of images
+ * [B, 3, image_size, image_size] and alpha [B, image_size, image_size] (alpha: the bits of d3m_vertex_attribute_images').  One
+ * launch (k_sh_fragment_images).  D3M_ERR_INVALID, before any launch: what d3m_vertex_attribute_images refuses of the record,
+ * B S S beyond 2^32, NULL or misaligned normals / sh / images / alpha, misaligned colors / background, a batch neither 1 nor B,
+ * num_vertices <= 0. */
+int d3m_sh_fragment_images(const d3m_fragments* fragments, const float* normals, int normals_batch, const float* sh,
+                           int sh_batch, const float* colors, int colors_batch, int num_vertices, const float* background,
+                           float* images, float* alpha, d3m_stream_t stream);
+/* Floats of scratch of d3m_sh_fragment_images_backward, with C = 6 (with_colors != 0) or 3 and S = raster_size:
+ * d3m_vertex_attribute_scratch_floats(batch_size, num_faces, C, adjacency), then the gradient image B C S S, then the light's
+ * partial sums B * min(ceil(S S / 1024), 256) * 27.  0 for sizes that are refused. */
+size_t d3m_sh_fragment_scratch_floats(int batch_size, int num_faces, int raster_size, int with_colors,
+                                      const d3m_csr* adjacency);
+/* The adjoint: grad_images [B, 3, image_size, image_size] -> grad_sh [sh_batch, 3, 9], grad_vertex and pixel_grads [B, S, S, 3]
+ * (d3m_sh_fragment_pixel_grads' map, written by the same per-pixel launch); each may be NULL (not computed), not all three;
+ * every element of what is given is WRITTEN, the gradient of a shared input summed over the views in ascending order.
+ * vertex_grads says what grad_vertex holds: 0 nothing (grad_vertex NULL), 1 the normals' gradient [normals_batch, V, 3], 2 the
+ * colours' [colors_batch, V, 3], 3 both: with colors of the normals' batch [normals_batch, V, 6] (normals in channels 0..2,
+ * colours in 3..5: one gather), with colors of another batch [normals_batch, V, 3] followed by [colors_batch, V, 3] (two
+ * gathers).  scratch needs no initialisation.  No float atomics, nothing cleared.  Launches: k_sh_fragment_backward_pixels;
+ * k_sh_fragment_finish for grad_sh; per gather k_vertex_attribute_face_sums, k_vertex_attribute_large_face_sums,
+ * k_vertex_attribute_adjoint_rows, and k_vertex_attribute_adjoint_chunks on a mesh with long rows.  D3M_ERR_INVALID, before any
+ * launch: what d3m_sh_fragment_images refuses of the record and the inputs, a NULL or too small visibility blob, what d3m_csr
+ * lists (num_rows = num_vertices), NULL items, a NULL or misaligned grad_images / scratch, all three results NULL, a misaligned
+ * result, vertex_grads outside 0..3, 0 with a grad_vertex or not 0 without, the colours' bit without colors, 3 num_tri beyond
+ * 2^31 - 1; D3M_ERR_WORKSPACE: scratch_floats below d3m_sh_fragment_scratch_floats(). */
+int d3m_sh_fragment_images_backward(const d3m_fragments* fragments, const float* normals, int normals_batch, const float* sh,
+                                    int sh_batch, const float* colors, int colors_batch, int num_vertices,
+                                    const float* grad_images, const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
+                                    float* grad_vertex, int vertex_grads, float* grad_sh, float* pixel_grads,
+                                    d3m_stream_t stream);
+/* pixel_grads [B, S, S, 3] = dL/du_c of the shaded images for d3m_fragment_geometry_backward: h_c = dL/dm . n_c + dL/da . c_c,
+ * every element WRITTEN (+0 where uncovered) -- for a caller who wants nothing else of the adjoint.  One launch
+ * (k_sh_fragment_backward_pixels).  D3M_ERR_INVALID, before any launch:
+ * what d3m_sh_fragment_images refuses of the record and the inputs, a NULL or misaligned grad_images / pixel_grads. */
+int d3m_sh_fragment_pixel_grads(const d3m_fragments* fragments, const float* normals, int normals_batch, const float* sh,
+                                int sh_batch, const float* colors, int colors_batch, int num_vertices,
+                                const float* grad_images, float* pixel_grads, d3m_stream_t stream);
 /* Analytic edge antialiasing of an image drawn over a coverage record, and its silhouette gradient (an addition;
  * csrc/d3m_antialias.h states the function, the pair decision and the order of every sum).  The record must be one without
  * anti-aliasing (S = image_size) that d3m_forward_face_index_map_mesh made from screen_vertices [B, V, 3];  side_opposite
