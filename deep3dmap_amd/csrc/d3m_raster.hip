@@ -20,6 +20,7 @@
 #include "d3m_fragment_geometry.h"
 #include "d3m_sh_fragments.h"
 #include "d3m_antialias.h"
+#include "d3m_uv_bake.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -3063,6 +3064,123 @@ D3M_EXPORT int d3m_antialias_geometry_backward(const d3m_fragments* fragments, c
                    (const int*)vis.list, (const int*)vis.count, scratch);
             LAUNCH("k_antialias_large_face_sums", k_antialias_large_face_sums, dim3(large_blocks), dim3(RG_BLOCK), st, m,
                    pair_grads, (const int*)vis.list, (const int*)vis.count, scratch);
+        });
+}
+
+// View images baked into a uv texture (d3m_uv_bake.h).  What the entry points refuse of the two records, the sizes and the
+// screen vertices; `uv`, `vw`, `bk`: what the kernels read (bk.images is set by the entry points that read the images).
+static bool uv_bake_ok(const d3m_fragments* layout, const d3m_fragments* view, int C, int H, int W, const float* screen_vertices,
+                       int num_vertices, int perspective, float depth_tolerance, AttrMaps& uv, AttrMaps& vw, UbView& view_maps,
+                       UvBake& bk) {
+    if (!screen_vertices || misaligned4(screen_vertices) || !uv_texture_sizes_ok(1, H, W, C)) return false;
+    if (!std::isfinite(depth_tolerance) || depth_tolerance < 0.0f) return false;
+    if (!fragments_ok(layout, 1, 1, C, uv) || !fragments_ok(view, 1, num_vertices, C, vw)) return false;
+    if (uv.B != 1 || uv.aa || uv.Ft != vw.Ft) return false;
+    bk = UvBake{screen_vertices, nullptr, num_vertices, C, H, W, perspective ? 1 : 0, depth_tolerance};
+    view_maps = UbView{vw.face_index_map, vw.depth_map, vw.tri, vw.S, vw.Ft, vw.Fp};
+    return true;
+}
+
+D3M_EXPORT int d3m_uv_bake_texture(const d3m_fragments* layout, const d3m_fragments* view, const float* images,
+                                   int num_channels, int image_height, int image_width, const float* screen_vertices,
+                                   int num_vertices, int perspective, float depth_tolerance, const float* background,
+                                   float* texture, float* mask, d3m_stream_t stream) {
+    AttrMaps uv, vw;
+    UbView vm;
+    UvBake bk;
+    if (!images || !texture || !mask) return D3M_ERR_INVALID;
+    if (misaligned4(images) || misaligned4(background) || misaligned4(texture) || misaligned4(mask)) return D3M_ERR_INVALID;
+    if (!uv_bake_ok(layout, view, num_channels, image_height, image_width, screen_vertices, num_vertices, perspective,
+                    depth_tolerance, uv, vw, vm, bk))
+        return D3M_ERR_INVALID;
+    bk.images = images;
+    LAUNCH("k_uv_bake_texture", k_uv_bake_texture, dim3(blocks_for((long)uv.S * uv.S, 256), vw.B), dim3(256), (hipStream_t)stream,
+           uv, vm, bk, background, texture, mask);
+    return check_launch();
+}
+
+D3M_EXPORT size_t d3m_uv_bake_images_scratch_bytes(int batch_size, int num_channels, int image_height, int image_width) {
+    if (!uv_texture_sizes_ok(batch_size, image_height, image_width, num_channels)) return 0;
+    return (size_t)batch_size * num_channels * image_height * image_width * sizeof(long long) +
+           (size_t)UVT_MAX_BLOCKS * sizeof(unsigned);
+}
+
+D3M_EXPORT int d3m_uv_bake_images_backward(const d3m_fragments* layout, const d3m_fragments* view, int num_channels,
+                                           int image_height, int image_width, const float* screen_vertices, int num_vertices,
+                                           int perspective, float depth_tolerance, const float* grad_texture, void* scratch,
+                                           size_t scratch_bytes, float* grad_images, d3m_stream_t stream) {
+    AttrMaps uv, vw;
+    UbView vm;
+    UvBake bk;
+    if (!grad_texture || !scratch || !grad_images) return D3M_ERR_INVALID;
+    if (misaligned4(grad_texture) || misaligned4(grad_images) || ((uintptr_t)scratch & 7)) return D3M_ERR_INVALID;
+    if (!uv_bake_ok(layout, view, num_channels, image_height, image_width, screen_vertices, num_vertices, perspective,
+                    depth_tolerance, uv, vw, vm, bk))
+        return D3M_ERR_INVALID;
+    const size_t need = d3m_uv_bake_images_scratch_bytes(vw.B, num_channels, image_height, image_width);
+    if (need == 0) return D3M_ERR_INVALID;
+    if (scratch_bytes < need) return D3M_ERR_WORKSPACE;
+    const long T2 = (long)uv.S * uv.S;
+    const long n_acc = (long)vw.B * num_channels * image_height * image_width, n_g = (long)vw.B * T2 * num_channels;
+    const int frac = 62 - ceil_log2((unsigned long long)T2);          // a view's image receives from its own T^2 texels only
+    unsigned long long* acc = (unsigned long long*)scratch;
+    unsigned* block_max = (unsigned*)(acc + n_acc);
+    const int n_max = (int)std::min(blocks_for(std::max(n_acc, n_g), 256), (unsigned)UVT_MAX_BLOCKS);
+    hipStream_t st = (hipStream_t)stream;
+    LAUNCH("k_uv_texture_images_clear_max", k_uv_texture_images_clear_max, dim3(n_max), dim3(256), st, grad_texture, n_g, 1.0f, acc,
+           n_acc, block_max);
+    LAUNCH("k_uv_bake_images_scatter", k_uv_bake_images_scatter,
+           dim3(std::min(blocks_for(T2, 256), (unsigned)UVT_SCATTER_BLOCKS), vw.B), dim3(256), st, uv, vm, bk, grad_texture,
+           (const unsigned*)block_max, n_max, frac, acc);
+    LAUNCH("k_uv_texture_images_convert", k_uv_texture_images_convert,
+           dim3(std::min(blocks_for(n_acc, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)acc, n_acc,
+           (const unsigned*)block_max, n_max, frac, grad_images);
+    return check_launch();
+}
+
+D3M_EXPORT size_t d3m_uv_bake_scratch_floats(int batch_size, int num_layout_faces, const d3m_csr* adjacency) {
+    const size_t sums = d3m_vertex_attribute_scratch_floats(batch_size, num_layout_faces, 3, adjacency);
+    if (sums == 0) return 0;
+    return sums + (size_t)batch_size * num_layout_faces;             // (the per-view flags)
+}
+
+D3M_EXPORT int d3m_uv_bake_vertices_backward(const d3m_fragments* layout, const d3m_fragments* view, const float* images,
+                                             int num_channels, int image_height, int image_width,
+                                             const float* screen_vertices, int num_vertices, int perspective,
+                                             float depth_tolerance, const float* grad_texture, const d3m_csr* adjacency,
+                                             float* scratch, size_t scratch_floats, float* grad_screen_vertices,
+                                             d3m_stream_t stream) {
+    AttrMaps uv, vw;
+    UbView vm;
+    UvBake bk;
+    if (!images || !grad_texture || !scratch || !grad_screen_vertices) return D3M_ERR_INVALID;
+    if (misaligned4(images) || misaligned4(grad_texture) || misaligned4(scratch) || misaligned4(grad_screen_vertices))
+        return D3M_ERR_INVALID;
+    if (!uv_bake_ok(layout, view, num_channels, image_height, image_width, screen_vertices, num_vertices, perspective,
+                    depth_tolerance, uv, vw, vm, bk))
+        return D3M_ERR_INVALID;
+    if ((long)uv.Ft * 3 > 0x7FFFFFFFl || (long)vw.B * uv.Fp > 0x7FFFFFFFl) return D3M_ERR_INVALID;
+    if (!layout->visibility || layout->visibility_size < visibility_bytes(uv.Fp)) return D3M_ERR_INVALID;
+    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if (scratch_floats < d3m_uv_bake_scratch_floats(vw.B, uv.Fp, adjacency)) return D3M_ERR_WORKSPACE;
+    bk.images = images;
+    const VisibilityView layout_vis = visibility_view(const_cast<void*>(layout->visibility), uv.Fp);
+    int* view_flags = (int*)(scratch + d3m_vertex_attribute_scratch_floats(vw.B, uv.Fp, 3, adjacency));
+    VisibilityView vis = layout_vis;
+    vis.flags = view_flags;
+    AttrMaps views = uv;                                                // the gather's sizes: B views of the layout's F' faces
+    views.B = vw.B;
+    return face_sums_gather(
+        views, vis, *adjacency, scratch, num_vertices, 3, false, grad_screen_vertices, (hipStream_t)stream,
+        [&](unsigned, unsigned, hipStream_t st) {
+            const unsigned small_blocks = std::min(blocks_for(uv.Fp, FM_FACES_PER_BLOCK), 2048u);
+            const unsigned large_blocks = std::min(blocks_for(uv.Fp, RG_BLOCK), 256u);
+            LAUNCH("k_uv_bake_view_flags", k_uv_bake_view_flags, dim3(blocks_for(uv.Fp, 256), vw.B), dim3(256), st,
+                   (const int*)layout_vis.flags, uv.Fp, view_flags);
+            LAUNCH("k_uv_bake_face_sums", k_uv_bake_face_sums, dim3(small_blocks, vw.B), dim3(256), st, uv, vm, bk, grad_texture,
+                   (const int*)layout_vis.list, (const int*)layout_vis.count, scratch);
+            LAUNCH("k_uv_bake_large_face_sums", k_uv_bake_large_face_sums, dim3(large_blocks, vw.B), dim3(RG_BLOCK), st, uv, vm,
+                   bk, grad_texture, (const int*)layout_vis.list, (const int*)layout_vis.count, scratch);
         });
 }
 

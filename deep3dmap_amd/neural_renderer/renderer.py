@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import (attributes as _attributes, cameras, mesh_ops, sh_fragments as _sh_fragments, smooth_shading as _smooth_shading,
-               uv_texture_images as _uv_texture_images)
+               uv_bake as _uv_bake, uv_texture_images as _uv_texture_images)
 from .antialias import antialias as _antialias_images
 from .rasterize import (light_on_device, rasterize, rasterize_depth, rasterize_lit, rasterize_lit_fit,
                         rasterize_lit_image_grid, rasterize_mesh_modes, rasterize_rgbad, rasterize_silhouettes)
@@ -278,6 +278,26 @@ class Renderer(nn.Module):
             return self._antialiased(images, alpha, fr, sv) if antialias else (images, alpha)
         fr = self.fragments(vertices, faces, K, R, t, dist_coeffs, orig_size)
         return _uv_texture_images.sample_uv_texture(image, faces_uv, fr, texture_wrapping, background, mipmap, lod_bias)
+
+    def bake_uv_texture(self, vertices, faces, images, faces_uv, texture_size, texture_wrapping='REPEAT', background=None,
+                        depth_tolerance=1e-2, K=None, R=None, t=None, dist_coeffs=None, orig_size=None, geometry_grad=False):
+        """(texture [B,T,T,C], mask [B,T,T]) of images [B,C,H,W] of this renderer's views of the mesh, T = texture_size: the
+        camera transform, fragments(), the layout record of faces_uv [F,3,2] (uv_bake.cached_uv_layout_fragments: built on the
+        first call with this faces_uv tensor and kept in its cache) and nr.bake_uv_texture -- the inverse of
+        render_uv_texture, with the view's z-buffer deciding which texels it sees.  perspective follows the renderer's own
+        attribute (a projection camera: True).  Differentiable in the images; geometry_grad=True: the screen vertices stay
+        in the graph (the record is made from their detached values), so the gradient of the lookup position reaches
+        `vertices` and any learnable camera tensor through the camera operators; visibility stays a constant."""
+        if geometry_grad:
+            fr, sv = self._fragments_with_vertices(vertices, faces, K, R, t, dist_coeffs, orig_size)
+        else:
+            with torch.no_grad():
+                sv = self._transform(vertices, K, R, t, dist_coeffs, orig_size)
+            fr = _attributes.rasterize_fragments(sv, faces, self.image_size, self.anti_aliasing, self.fill_back, self.near,
+                                                 self.far)
+        layout = _uv_bake.cached_uv_layout_fragments(faces_uv, texture_size, texture_wrapping)
+        return _uv_bake.bake_uv_texture(images, layout, fr, sv, bool(getattr(self, "perspective", True)), depth_tolerance,
+                                        background)
 
     def render_sh_shaded(self, vertices, faces, sh, colors=None, normals=None, background=None, K=None, R=None, t=None,
                          dist_coeffs=None, orig_size=None, geometry_grad=False, antialias=False):

@@ -1238,6 +1238,48 @@ size_t d3m_antialias_scratch_floats(int batch_size, int num_faces, int raster_si
 int d3m_antialias_geometry_backward(const d3m_fragments* fragments, const float* pair_grads, const d3m_csr* adjacency,
                                     float* scratch, size_t scratch_floats, float* grad_screen_vertices, int num_vertices,
                                     d3m_stream_t stream);
+/* View images baked into a uv texture, the inverse of d3m_uv_texture_images (an addition; csrc/d3m_uv_bake.h states the
+ * function, the visibility decision and the order of every sum).  layout: the record of the faces_uv layout -- batch_size 1,
+ * no anti-aliasing, raster size T, every vertex at z = 1, so that its weight_map holds a texel's barycentrics in its owner --;
+ * view: the record of B views that d3m_forward_face_index_map_mesh made from screen_vertices [B, V, 3]; both of num_tri
+ * triangles.  images [B, C, H, W] in output orientation (row 0 = top), 1 <= C <= 64, H, W <= 32768.
+ * d3m_uv_bake_texture WRITES every element of texture [B, T, T, C] (a visible texel: the four bilinear taps at its surface
+ * point in the view; else background [C], NULL = zeros) and of mask [B, T, T] (1 or 0).  One launch (k_uv_bake_texture).
+ * D3M_ERR_INVALID, before any launch: what d3m_vertex_attribute_images refuses of either record, a layout record with
+ * batch_size != 1 or with anti_aliasing, records of different num_tri, sizes outside the ranges above, a depth_tolerance
+ * that is negative or not finite, a NULL or misaligned images / screen_vertices / texture / mask, a misaligned background. */
+int d3m_uv_bake_texture(const d3m_fragments* layout, const d3m_fragments* view, const float* images, int num_channels,
+                        int image_height, int image_width, const float* screen_vertices, int num_vertices, int perspective,
+                        float depth_tolerance, const float* background, float* texture, float* mask, d3m_stream_t stream);
+/* Bytes of scratch of d3m_uv_bake_images_backward: B C H W int64 accumulators and 1024 block maxima; 0 for sizes that are
+ * refused. */
+size_t d3m_uv_bake_images_scratch_bytes(int batch_size, int num_channels, int image_height, int image_width);
+/* grad_texture [B, T, T, C] -> grad_images [B, C, H, W], every element WRITTEN: the order-independent fixed-point scatter of
+ * d3m_uv_texture_images_backward (frac = 62 - ceil(log2(T T)); an all-zero gradient gives +0 everywhere, a non-finite one NaN
+ * everywhere).  scratch needs no initialisation.  No float atomics; three launches (k_uv_texture_images_clear_max,
+ * k_uv_bake_images_scatter, k_uv_texture_images_convert).  D3M_ERR_INVALID, before any launch: what d3m_uv_bake_texture
+ * refuses of the records, sizes, tolerance and screen_vertices, a NULL or misaligned grad_texture / grad_images, a NULL
+ * scratch or one not aligned to 8 bytes; D3M_ERR_WORKSPACE: scratch_bytes below d3m_uv_bake_images_scratch_bytes(). */
+int d3m_uv_bake_images_backward(const d3m_fragments* layout, const d3m_fragments* view, int num_channels, int image_height,
+                                int image_width, const float* screen_vertices, int num_vertices, int perspective,
+                                float depth_tolerance, const float* grad_texture, void* scratch, size_t scratch_bytes,
+                                float* grad_images, d3m_stream_t stream);
+/* Floats of scratch of d3m_uv_bake_vertices_backward: d3m_vertex_attribute_scratch_floats(B, F', 3, adjacency) -- the B F' 9
+ * per-face sums and 3 B num_chunks chunk sums, F' = num_layout_faces the layout record's faces with its fill_back copies --
+ * and B F' words of per-view flags.  0 for sizes that are refused. */
+size_t d3m_uv_bake_scratch_floats(int batch_size, int num_layout_faces, const d3m_csr* adjacency);
+/* grad_texture [B, T, T, C] -> grad_screen_vertices [B, V, 3] (x, y and z), every element WRITTEN; visibility and the choice
+ * of taps are constants.  adjacency: the MESH faces' d3m_csr of V rows (item = 3 f + c).  scratch needs no initialisation.
+ * No float atomics, nothing cleared; four launches (k_uv_bake_view_flags, k_uv_bake_face_sums, k_uv_bake_large_face_sums,
+ * k_vertex_attribute_adjoint_rows) and k_vertex_attribute_adjoint_chunks on a mesh with long rows.  D3M_ERR_INVALID, before
+ * any launch: what d3m_uv_bake_texture refuses (texture, mask and background aside), a NULL or misaligned grad_texture /
+ * scratch / grad_screen_vertices, a layout record without a finished visibility blob, a malformed adjacency;
+ * D3M_ERR_WORKSPACE: scratch_floats below d3m_uv_bake_scratch_floats(). */
+int d3m_uv_bake_vertices_backward(const d3m_fragments* layout, const d3m_fragments* view, const float* images,
+                                  int num_channels, int image_height, int image_width, const float* screen_vertices,
+                                  int num_vertices, int perspective, float depth_tolerance, const float* grad_texture,
+                                  const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
+                                  float* grad_screen_vertices, d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
