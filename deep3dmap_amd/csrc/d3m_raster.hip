@@ -21,6 +21,7 @@
 #include "d3m_sh_fragments.h"
 #include "d3m_antialias.h"
 #include "d3m_uv_bake.h"
+#include "d3m_uv_fill.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -3182,6 +3183,110 @@ D3M_EXPORT int d3m_uv_bake_vertices_backward(const d3m_fragments* layout, const 
             LAUNCH("k_uv_bake_large_face_sums", k_uv_bake_large_face_sums, dim3(large_blocks, vw.B), dim3(RG_BLOCK), st, uv, vm,
                    bk, grad_texture, (const int*)layout_vis.list, (const int*)layout_vis.count, scratch);
         });
+}
+
+// Fused view textures with their unseen texels filled by push-pull (d3m_uv_fill.h).  What the entry points refuse of the sizes;
+// `uf`: the levels, as the kernels read them.
+static bool uv_fill_ok(int B, int H, int W, int C, UvFill& uf) {
+    if (!uv_texture_sizes_ok(B, H, W, C)) return false;
+    uf.H = H;
+    uf.W = W;
+    uf.C = C;
+    int L = 0;
+    while (uf_size(H, L) > 1 || uf_size(W, L) > 1) L++;
+    uf.L = L;
+    long T = 0;
+    for (int l = 0; l <= UF_MAX_LEVEL + 1; l++) {
+        uf.offset[l] = T;
+        if (l >= 1 && l <= L) T += (long)uf_size(H, l) * uf_size(W, l);
+    }
+    return true;
+}
+
+static size_t uv_fill_top_texels(const UvFill& uf) {
+    const int lt = std::min(uf.L, UVT_TILE_LEVELS);
+    return lt == 0 ? 1 : (size_t)(uf.offset[uf.L + 1] - uf.offset[lt]);
+}
+
+D3M_EXPORT size_t d3m_uv_fill_pyramid_texels(int image_height, int image_width) {
+    UvFill uf;
+    if (!uv_fill_ok(1, image_height, image_width, 1, uf)) return 0;
+    return (size_t)uf.offset[uf.L + 1];
+}
+
+D3M_EXPORT size_t d3m_uv_fill_scratch_bytes(int image_height, int image_width, int num_channels) {
+    UvFill uf;
+    if (!uv_fill_ok(1, image_height, image_width, num_channels, uf)) return 0;
+    return ((size_t)uf.offset[uf.L + 1] + uv_fill_top_texels(uf)) * num_channels * sizeof(float);
+}
+
+D3M_EXPORT size_t d3m_uv_fill_backward_scratch_bytes(int image_height, int image_width, int num_channels) {
+    UvFill uf;
+    if (!uv_fill_ok(1, image_height, image_width, num_channels, uf)) return 0;
+    return std::max((size_t)uf.offset[uf.L + 1], (size_t)1) * num_channels * sizeof(float);
+}
+
+D3M_EXPORT int d3m_uv_fill_textures(const float* textures, const float* weights, int batch_size, int image_height,
+                                    int image_width, int num_channels, int fill, const float* background, void* scratch,
+                                    size_t scratch_bytes, int32_t* counts, size_t count_texels, float* texture, float* valid,
+                                    d3m_stream_t stream) {
+    UvFill uf;
+    if (!textures || !weights || !texture || !valid) return D3M_ERR_INVALID;
+    if (misaligned4(textures) || misaligned4(weights) || misaligned4(background) || misaligned4(texture) || misaligned4(valid))
+        return D3M_ERR_INVALID;
+    if (!uv_fill_ok(batch_size, image_height, image_width, num_channels, uf)) return D3M_ERR_INVALID;
+    const size_t P = (size_t)uf.offset[uf.L + 1];
+    if (fill) {
+        if (!scratch || misaligned4(scratch) || (P > 0 && (!counts || misaligned4(counts)))) return D3M_ERR_INVALID;
+        if (scratch_bytes < d3m_uv_fill_scratch_bytes(image_height, image_width, num_channels) || count_texels < P)
+            return D3M_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float* sums = (float*)scratch;
+    float* top = sums ? sums + P * num_channels : nullptr;
+    const unsigned tiles = blocks_for(image_width, UVT_TILE) * blocks_for(image_height, UVT_TILE);
+    LAUNCH("k_uv_fill_fuse_tile", k_uv_fill_fuse_tile, dim3(tiles), dim3(256), st, textures, weights, batch_size, uf, fill ? 1 : 0,
+           background, texture, valid, sums, (int*)counts);
+    if (fill) {
+        LAUNCH("k_uv_fill_top", k_uv_fill_top, dim3(1), dim3(UF_TOP_BLOCK), st, uf, background, (const float*)texture,
+               (const float*)valid, sums, (int*)counts, top);
+        LAUNCH("k_uv_fill_push_tile", k_uv_fill_push_tile, dim3(tiles), dim3(256), st, uf, (const float*)valid, (const float*)sums,
+               (const int*)counts, (const float*)top, texture);
+    }
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_uv_fill_textures_backward(const float* weights, const float* valid, const int32_t* counts,
+                                             size_t count_texels, const float* grad_texture, int batch_size, int image_height,
+                                             int image_width, int num_channels, int fill, void* scratch, size_t scratch_bytes,
+                                             float* grad_textures, d3m_stream_t stream) {
+    UvFill uf;
+    if (!weights || !valid || !grad_texture || !grad_textures) return D3M_ERR_INVALID;
+    if (misaligned4(weights) || misaligned4(valid) || misaligned4(grad_texture) || misaligned4(grad_textures))
+        return D3M_ERR_INVALID;
+    if (!uv_fill_ok(batch_size, image_height, image_width, num_channels, uf)) return D3M_ERR_INVALID;
+    const size_t P = (size_t)uf.offset[uf.L + 1];
+    const bool levels = fill && uf.L > 0;
+    if (levels) {
+        if (!scratch || misaligned4(scratch) || !counts || misaligned4(counts)) return D3M_ERR_INVALID;
+        if (scratch_bytes < d3m_uv_fill_backward_scratch_bytes(image_height, image_width, num_channels) || count_texels < P)
+            return D3M_ERR_WORKSPACE;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    float* G = (float*)scratch;
+    for (int base = 0; levels && base < uf.L;) {
+        const int hb = uf_size(image_height, base), wb = uf_size(image_width, base);
+        const bool one_tile = hb <= UVT_TILE && wb <= UVT_TILE;                   // then L - base <= 5
+        const int steps = one_tile ? uf.L - base : UF_ADJ_STEPS;                  // (a larger level is at least 6 below L)
+        LAUNCH("k_uv_fill_adjoint_tile", k_uv_fill_adjoint_tile, dim3(blocks_for(wb, UVT_TILE) * blocks_for(hb, UVT_TILE)),
+               dim3(256), st, uf, base, steps, grad_texture, valid, (const int*)counts, G);
+        base += steps;
+    }
+    const long n = (long)image_height * image_width * num_channels;
+    LAUNCH("k_uv_fill_adjoint_views", k_uv_fill_adjoint_views, dim3(std::min(blocks_for(n, 256), (unsigned)UVT_SCATTER_BLOCKS)),
+           dim3(256), st, uf, batch_size, levels ? uf.L : 0, weights, valid, (const int*)counts, (const float*)G, grad_texture,
+           grad_textures);
+    return check_launch();
 }
 
 D3M_EXPORT int d3m_create_texture_image(const float* vertices_all, const float* textures, float* image, int num_faces,

@@ -16,6 +16,7 @@ from .renderer import Renderer
 from .sh_fragments import shade_fragments
 from .smooth_shading import SHLight, sh_basis, sh_vertex_colors, vertex_normals
 from .uv_bake import bake_uv_texture, uv_layout_fragments
+from .uv_fill import fill_uv_texture, fuse_uv_textures
 from .uv_texture_images import sample_uv_texture, texture_mip_pyramid, uv_texture_lod
 from .uv_textures import UVTextures, textures_from_image
 from .vertex_colors import VertexColors, textures_from_vertex_colors

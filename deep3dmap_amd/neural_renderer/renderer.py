@@ -9,7 +9,7 @@ import torch
 import torch.nn as nn
 
 from . import (attributes as _attributes, cameras, mesh_ops, sh_fragments as _sh_fragments, smooth_shading as _smooth_shading,
-               uv_bake as _uv_bake, uv_texture_images as _uv_texture_images)
+               uv_bake as _uv_bake, uv_fill as _uv_fill, uv_texture_images as _uv_texture_images)
 from .antialias import antialias as _antialias_images
 from .rasterize import (light_on_device, rasterize, rasterize_depth, rasterize_lit, rasterize_lit_fit,
                         rasterize_lit_image_grid, rasterize_mesh_modes, rasterize_rgbad, rasterize_silhouettes)
@@ -298,6 +298,25 @@ class Renderer(nn.Module):
         layout = _uv_bake.cached_uv_layout_fragments(faces_uv, texture_size, texture_wrapping)
         return _uv_bake.bake_uv_texture(images, layout, fr, sv, bool(getattr(self, "perspective", True)), depth_tolerance,
                                         background)
+
+    def bake_fused_uv_texture(self, vertices, faces, images, faces_uv, texture_size, texture_wrapping='REPEAT', background=None,
+                              depth_tolerance=1e-2, K=None, R=None, t=None, dist_coeffs=None, orig_size=None,
+                              geometry_grad=False, view_weights=None, fill=True):
+        """(texture [T,T,C], valid [T,T]): bake_uv_texture of this renderer's B views followed by nr.fuse_uv_textures -- the
+        views fused with their masks as weights and, with fill=True, the texels no view saw filled by push-pull, ready for
+        sample_uv_texture(mipmap=True).  view_weights: None, [B] or [B,T,T] f32 constants multiplied onto the masks (a
+        view-angle weight, say; not > 0 counts as not seen).  The other arguments are bake_uv_texture's; `background` is
+        the value of an unseen texel without the fill, and of every texel when no view saw any."""
+        texture, mask = self.bake_uv_texture(vertices, faces, images, faces_uv, texture_size, texture_wrapping, background,
+                                             depth_tolerance, K, R, t, dist_coeffs, orig_size, geometry_grad)
+        weights = mask
+        if view_weights is not None:
+            if not torch.is_tensor(view_weights) or view_weights.requires_grad or \
+                    tuple(view_weights.shape) not in ((mask.shape[0],), tuple(mask.shape)):
+                raise ValueError("bake_fused_uv_texture: view_weights must be None or a [B] or [B, T, T] tensor that does "
+                                 "not require grad")
+            weights = mask * (view_weights[:, None, None] if view_weights.dim() == 1 else view_weights)
+        return _uv_fill.fuse_uv_textures(texture, weights, fill, background)
 
     def render_sh_shaded(self, vertices, faces, sh, colors=None, normals=None, background=None, K=None, R=None, t=None,
                          dist_coeffs=None, orig_size=None, geometry_grad=False, antialias=False):

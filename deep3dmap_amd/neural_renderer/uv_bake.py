@@ -16,7 +16,7 @@ and in the screen vertices (x, y and z) through the taps' slope and the closed-f
 per layout face in the fixed order of csrc/d3m_fragments.h and gathered over the mesh's vertex adjacency: no float atomics,
 the same bits on every run.  Visibility and the choice of taps are constants of the graph; the mask is not differentiable.
 
-Fusing views is plain torch: (mask[..., None] * texture).sum(0) / mask.sum(0).clamp(min=1)[..., None]."""
+Fusing the views and filling the texels none of them saw: fuse_uv_textures (uv_fill.py)."""
 import ctypes
 import math
 

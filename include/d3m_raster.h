@@ -1280,6 +1280,38 @@ int d3m_uv_bake_vertices_backward(const d3m_fragments* layout, const d3m_fragmen
                                   int num_vertices, int perspective, float depth_tolerance, const float* grad_texture,
                                   const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
                                   float* grad_screen_vertices, d3m_stream_t stream);
+/* Fused view textures with their unseen texels filled by push-pull (an addition; csrc/d3m_uv_fill.h states the fusion, the
+ * pull, the push and the order of every sum).  textures [B, H, W, C] and weights [B, H, W], 1 <= B <= 65535, 1 <= C <= 64,
+ * H, W <= 32768 (any H, W).  The pyramids hold levels 1..L, level l of ceil(H / 2^l) x ceil(W / 2^l) texels, L the 1 x 1
+ * level: d3m_uv_fill_pyramid_texels texels in all (0 for a 1 x 1 image and for sizes that are refused). */
+size_t d3m_uv_fill_pyramid_texels(int image_height, int image_width);
+/* Bytes of scratch of d3m_uv_fill_textures with fill != 0: C floats per pyramid texel (the sums) and per texel of levels
+ * min(L, 5)..L (the pushed values).  0 for sizes that are refused. */
+size_t d3m_uv_fill_scratch_bytes(int image_height, int image_width, int num_channels);
+/* Bytes of scratch of d3m_uv_fill_textures_backward with fill != 0: C floats per pyramid texel.  0 for refused sizes. */
+size_t d3m_uv_fill_backward_scratch_bytes(int image_height, int image_width, int num_channels);
+/* WRITES every element of texture [H, W, C] and of valid [H, W] (1 or 0: some view's weight is > 0).  fill == 0: the weighted
+ * mean of the views at valid texels, background [C] (NULL = zeros) elsewhere; one launch (k_uv_fill_fuse_tile), scratch and
+ * counts unused.  fill != 0: the invalid texels are filled by push-pull; counts [count_texels] int32 receives the valid
+ * texels under every pyramid texel (the backward reads it); three launches (k_uv_fill_fuse_tile, k_uv_fill_top,
+ * k_uv_fill_push_tile).  scratch and counts need no initialisation.  D3M_ERR_INVALID, before any launch: sizes outside the
+ * ranges above, a NULL or misaligned textures / weights / texture / valid, a misaligned background, with fill a NULL or
+ * misaligned scratch or (beyond 1 x 1) counts; D3M_ERR_WORKSPACE: scratch_bytes below d3m_uv_fill_scratch_bytes() or
+ * count_texels below d3m_uv_fill_pyramid_texels(). */
+int d3m_uv_fill_textures(const float* textures, const float* weights, int batch_size, int image_height, int image_width,
+                         int num_channels, int fill, const float* background, void* scratch, size_t scratch_bytes,
+                         int32_t* counts, size_t count_texels, float* texture, float* valid, d3m_stream_t stream);
+/* grad_texture [H, W, C] -> grad_textures [B, H, W, C], every element WRITTEN (exactly +0 where a view does not count);
+ * weights, valid and counts: the forward's.  Gathers in a fixed order: no atomics, nothing cleared.  fill != 0:
+ * k_uv_fill_adjoint_tile once per three levels while a level exceeds 32 x 32 and once for the levels above, then
+ * k_uv_fill_adjoint_views -- 2 launches up to 32 x 32, 3 up to 256 x 256, 4 up to 2048 x 2048 --; fill == 0: one launch,
+ * scratch and counts unused.  D3M_ERR_INVALID, before any launch: refused sizes, a NULL or misaligned weights / valid /
+ * grad_texture / grad_textures, with fill beyond 1 x 1 a NULL or misaligned scratch or counts; D3M_ERR_WORKSPACE:
+ * scratch_bytes below d3m_uv_fill_backward_scratch_bytes() or count_texels below d3m_uv_fill_pyramid_texels(). */
+int d3m_uv_fill_textures_backward(const float* weights, const float* valid, const int32_t* counts, size_t count_texels,
+                                  const float* grad_texture, int batch_size, int image_height, int image_width,
+                                  int num_channels, int fill, void* scratch, size_t scratch_bytes, float* grad_textures,
+                                  d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
