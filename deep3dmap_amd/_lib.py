@@ -235,6 +235,12 @@ _SIGNATURES = {
     "d3m_sh_fragment_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _I, _I, _P, ctypes.POINTER(D3MCsr),
                                              _P, _SZ, _P, _I, _P, _P, _P]),
     "d3m_sh_fragment_pixel_grads": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _I, _I, _P, _P, _P]),
+    "d3m_sh_uv_fragment_images": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "d3m_sh_uv_fragment_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(D3MCsr)]),
+    "d3m_sh_uv_fragment_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P,
+                                                ctypes.POINTER(D3MCsr), _P, _SZ, _P, _P, _P, _P, _P]),
+    "d3m_sh_uv_fragment_pixel_grads": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P,
+                                            _P]),
     "d3m_antialias_images": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _P, _P]),
     "d3m_antialias_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _P, _P, _P, _P]),
     "d3m_antialias_scratch_floats": (_SZ, [_I, _I, _I, ctypes.POINTER(D3MCsr), _I]),

@@ -33,6 +33,8 @@
 //                maps: the slope of the very patch the forward evaluated), fx = pos_x - xi, fy = pos_y - yi; Dx (Dy) = 0 where
 //                pos_x (pos_y) sits at a clamp limit (<= 0 or >= size - 1); h_c = (W - 1) cx_c Dx + (H - 1) cy_c Dy with the
 //                wrapped corner uv of uvt_pixel_position (a fill_back copy: corners 2 - c).  faces_uv is a constant.
+//                FgUvSlopes below is the one statement of Dx, Dy and this h_c; the SH-shaded uv albedo
+//                (d3m_sh_uv_fragments.h) calls it with dL/da_k in the place of sg[k] and adds its normals' term.
 // Going through h costs 12 B a pixel each way -- small beside reading g for C channels -- and keeps one shared adjoint.
 //
 // THE ORDER of the adjoint's sums, the same bits on every run (no float atomics anywhere, nothing is cleared):
@@ -175,6 +177,44 @@ __global__ void __launch_bounds__(256) k_vertex_attribute_pixel_grads(AttrMaps m
     for (int c = 0; c < 3; c++) h[3 * (size_t)p + c] = acc[c];
 }
 
+// The bilinear lookup's slopes along pos, stated once for the two nodes that differentiate it (this header's uv texture node
+// and d3m_sh_uv_fragments.h).  fg_uv_slopes: the four taps bilinear_taps chose at (pos_x, pos_y) of one image [H,W,C] and the
+// fractions.  add(c, g, dx, dy): dx += g * (channel c's slope along pos_x), dy likewise.  finish(k, dx, dy, h): the derivative
+// of the clamp is 0 AT a limit; h_c = (W - 1) cx_c dx + (H - 1) cy_c dy.
+struct FgUvSlopes {
+    const float *t00, *t10, *t01, *t11;
+    float fx, fy, x_max, y_max;
+    bool inside_x, inside_y;
+    __device__ __forceinline__ void add(int c, float g, float& dx, float& dy) const {
+        const float a00 = t00[c], a10 = t10[c], a01 = t01[c], a11 = t11[c];
+        dx += g * ((1.0f - fy) * (a01 - a00) + fy * (a11 - a10));
+        dy += g * ((1.0f - fx) * (a10 - a00) + fx * (a11 - a01));
+    }
+    __device__ __forceinline__ void finish(const UvtCorners& k, float dx, float dy, float* h) const {
+        if (!inside_x) dx = 0.0f;
+        if (!inside_y) dy = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; c++) h[c] = x_max * k.cx[c] * dx + y_max * k.cy[c] * dy;
+    }
+};
+
+__device__ __forceinline__ FgUvSlopes fg_uv_slopes(const UvTexture& tx, const float* __restrict__ img, float pos_x, float pos_y) {
+    TexelTaps tt;
+    bilinear_taps(pos_x, pos_y, tx.H, tx.W, tt);
+    FgUvSlopes s;
+    s.t00 = img + (size_t)tt.pix[0] * tx.C;
+    s.t10 = img + (size_t)tt.pix[1] * tx.C;
+    s.t01 = img + (size_t)tt.pix[2] * tx.C;
+    s.t11 = img + (size_t)tt.pix[3] * tx.C;
+    s.fx = pos_x - (float)(int)pos_x;
+    s.fy = pos_y - (float)(int)pos_y;
+    s.x_max = (float)(tx.W - 1);
+    s.y_max = (float)(tx.H - 1);
+    s.inside_x = pos_x > 0.0f && pos_x < s.x_max;
+    s.inside_y = pos_y > 0.0f && pos_y < s.y_max;
+    return s;
+}
+
 __global__ void __launch_bounds__(256) k_uv_texture_pixel_grads(AttrMaps m, UvTexture tx, const float* __restrict__ image,
                                                                const float* __restrict__ grad_images, float* __restrict__ h) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
@@ -188,15 +228,7 @@ __global__ void __launch_bounds__(256) k_uv_texture_pixel_grads(AttrMaps m, UvTe
         UvtCorners k;
         float pos_x, pos_y;
         uvt_pixel_position(m, tx, (size_t)p, fn, z, k, pos_x, pos_y);
-        TexelTaps tt;
-        bilinear_taps(pos_x, pos_y, tx.H, tx.W, tt);
-        const float fx = pos_x - (float)(int)pos_x, fy = pos_y - (float)(int)pos_y;
-        const float x_max = (float)(tx.W - 1), y_max = (float)(tx.H - 1);
-        const float* img = image + (size_t)(tx.image_batch > 1 ? b : 0) * tx.H * tx.W * C;
-        const float* t00 = img + (size_t)tt.pix[0] * C;
-        const float* t10 = img + (size_t)tt.pix[1] * C;
-        const float* t01 = img + (size_t)tt.pix[2] * C;
-        const float* t11 = img + (size_t)tt.pix[3] * C;
+        const FgUvSlopes sl = fg_uv_slopes(tx, image + (size_t)(tx.image_batch > 1 ? b : 0) * tx.H * tx.W * C, pos_x, pos_y);
         const float* g_view = grad_images + (size_t)b * C * s * s;
         float dx = 0.0f, dy = 0.0f;
         for (int k0 = 0; k0 < C; k0 += UVT_CHUNK) {
@@ -207,15 +239,10 @@ __global__ void __launch_bounds__(256) k_uv_texture_pixel_grads(AttrMaps m, UvTe
             for (int kk = 0; kk < VA_CHUNK; kk++) {
                 const int c = k0 + kk;
                 if (c >= C) continue;
-                const float a00 = t00[c], a10 = t10[c], a01 = t01[c], a11 = t11[c];
-                dx += gs[kk] * ((1.0f - fy) * (a01 - a00) + fy * (a11 - a10));
-                dy += gs[kk] * ((1.0f - fx) * (a10 - a00) + fx * (a11 - a01));
+                sl.add(c, gs[kk], dx, dy);
             }
         }
-        if (!(pos_x > 0.0f && pos_x < x_max)) dx = 0.0f;
-        if (!(pos_y > 0.0f && pos_y < y_max)) dy = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 3; c++) out[c] = x_max * k.cx[c] * dx + y_max * k.cy[c] * dy;
+        sl.finish(k, dx, dy, out);
     }
 #pragma unroll
     for (int c = 0; c < 3; c++) h[3 * (size_t)p + c] = out[c];

@@ -19,6 +19,7 @@
 #include "d3m_uv_texture_mip.h"
 #include "d3m_fragment_geometry.h"
 #include "d3m_sh_fragments.h"
+#include "d3m_sh_uv_fragments.h"
 #include "d3m_antialias.h"
 #include "d3m_uv_bake.h"
 #include "d3m_uv_fill.h"
@@ -2993,6 +2994,129 @@ D3M_EXPORT int d3m_sh_fragment_pixel_grads(const d3m_fragments* fragments, const
         return D3M_ERR_INVALID;
     LAUNCH("k_sh_fragment_backward_pixels", k_sh_fragment_backward_pixels, dim3(shf_parts((long)m.S * m.S), m.B),
            dim3(SET_BLOCK), (hipStream_t)stream, m, in, grad_images, (float*)nullptr, (float*)nullptr, (size_t)0, pixel_grads,
+           (float*)nullptr);
+    return check_launch();
+}
+
+// Per-pixel spherical-harmonic shading of a UV albedo texture over a coverage record (d3m_sh_uv_fragments.h).  What the entry
+// points refuse: what the two nodes it joins refuse; `m`, `in`, `tx`: what the kernels read.
+static bool sh_uv_fragments_ok(const d3m_fragments* fr, const float* normals, int normals_batch, const float* sh, int sh_batch,
+                               int num_vertices, const float* faces_uv, const float* image, int image_batch, int H, int W,
+                               int wrapping, AttrMaps& m, ShfInputs& in, UvTexture& tx) {
+    AttrMaps m_uv;
+    if (!image || misaligned4(image)) return false;
+    if (!uv_texture_ok(fr, faces_uv, image_batch, H, W, 3, wrapping, m_uv, tx)) return false;
+    return sh_fragments_ok(fr, normals, normals_batch, sh, sh_batch, nullptr, 1, num_vertices, m, in);
+}
+
+D3M_EXPORT int d3m_sh_uv_fragment_images(const d3m_fragments* fragments, const float* normals, int normals_batch,
+                                         const float* sh, int sh_batch, int num_vertices, const float* faces_uv,
+                                         const float* image, int image_batch, int image_height, int image_width,
+                                         int texture_wrapping, const float* background, float* images, float* alpha,
+                                         d3m_stream_t stream) {
+    AttrMaps m;
+    ShfInputs in;
+    UvTexture tx;
+    if (!images || !alpha || misaligned4(background) || misaligned4(images) || misaligned4(alpha)) return D3M_ERR_INVALID;
+    if (!sh_uv_fragments_ok(fragments, normals, normals_batch, sh, sh_batch, num_vertices, faces_uv, image, image_batch,
+                            image_height, image_width, texture_wrapping, m, in, tx))
+        return D3M_ERR_INVALID;
+    const long n = (long)fragments->image_size * fragments->image_size;
+    LAUNCH("k_sh_uv_fragment_images", k_sh_uv_fragment_images, dim3(blocks_for(n, 256), m.B), dim3(256), (hipStream_t)stream, m,
+           in, tx, image, background, images, alpha);
+    return check_launch();
+}
+
+// The scratch's carve-up: the image adjoint's accumulators and block maxima (d3m_uv_texture_images_scratch_bytes, rounded up
+// to 8 bytes) come first, then floats: the gather's own, Qn, Qa, the sh partials.
+static size_t sh_uv_fixed_point_bytes(int image_batch, int H, int W, int batch_size, int raster_size) {
+    return (d3m_uv_texture_images_scratch_bytes(image_batch, H, W, 3, batch_size, raster_size) + 7) & ~(size_t)7;
+}
+
+D3M_EXPORT size_t d3m_sh_uv_fragment_scratch_bytes(int batch_size, int num_faces, int raster_size, int image_batch,
+                                                   int image_height, int image_width, const d3m_csr* adjacency) {
+    const size_t fixed = sh_uv_fixed_point_bytes(image_batch, image_height, image_width, batch_size, raster_size);
+    const size_t sums = d3m_vertex_attribute_scratch_floats(batch_size, num_faces, 3, adjacency);
+    if (fixed == 0 || sums == 0) return 0;
+    const size_t S2 = (size_t)raster_size * raster_size;
+    return fixed + (sums + (size_t)batch_size * S2 * 6 + (size_t)batch_size * shf_parts((long)S2) * SHF_SUMS) * sizeof(float);
+}
+
+D3M_EXPORT int d3m_sh_uv_fragment_images_backward(const d3m_fragments* fragments, const float* normals, int normals_batch,
+                                                  const float* sh, int sh_batch, int num_vertices, const float* faces_uv,
+                                                  const float* image, int image_batch, int image_height, int image_width,
+                                                  int texture_wrapping, const float* grad_images, const d3m_csr* adjacency,
+                                                  void* scratch, size_t scratch_bytes, float* grad_normals, float* grad_sh,
+                                                  float* grad_image, float* pixel_grads, d3m_stream_t stream) {
+    AttrMaps m;
+    ShfInputs in;
+    UvTexture tx;
+    if (!grad_images || !scratch || (!grad_normals && !grad_sh && !grad_image && !pixel_grads)) return D3M_ERR_INVALID;
+    if (misaligned4(grad_images) || ((uintptr_t)scratch & 7) || misaligned4(grad_normals) || misaligned4(grad_sh) ||
+        misaligned4(grad_image) || misaligned4(pixel_grads))
+        return D3M_ERR_INVALID;
+    if (!sh_uv_fragments_ok(fragments, normals, normals_batch, sh, sh_batch, num_vertices, faces_uv, image, image_batch,
+                            image_height, image_width, texture_wrapping, m, in, tx))
+        return D3M_ERR_INVALID;
+    if ((long)m.Ft * 3 > 0x7FFFFFFFl) return D3M_ERR_INVALID;          // items are int32
+    const long nf = (long)m.B * m.Fp;
+    if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
+    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    const size_t need = d3m_sh_uv_fragment_scratch_bytes(m.B, m.Fp, m.S, image_batch, image_height, image_width, adjacency);
+    if (need == 0) return D3M_ERR_INVALID;
+    if (scratch_bytes < need) return D3M_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t S2 = (size_t)m.S * m.S;
+    const int parts = shf_parts((long)S2);
+    float* gather_scratch = (float*)((char*)scratch + sh_uv_fixed_point_bytes(image_batch, image_height, image_width, m.B, m.S));
+    float* Qn = gather_scratch + d3m_vertex_attribute_scratch_floats(m.B, m.Fp, 3, adjacency);
+    float* Qa = Qn + (size_t)m.B * 3 * S2;
+    float* sh_partial = Qa + (size_t)m.B * 3 * S2;
+    LAUNCH("k_sh_uv_fragment_backward_pixels", k_sh_uv_fragment_backward_pixels, dim3(parts, m.B), dim3(SET_BLOCK), st, m, in, tx,
+           image, grad_images, grad_normals ? Qn : (float*)nullptr, grad_image ? Qa : (float*)nullptr, pixel_grads,
+           grad_sh ? sh_partial : (float*)nullptr);
+    if (grad_sh)
+        LAUNCH("k_sh_fragment_finish", k_sh_fragment_finish, dim3(blocks_for((long)sh_batch * SHF_SUMS, SET_BLOCK)),
+               dim3(SET_BLOCK), st, (const float*)sh_partial, parts, grad_sh, sh_batch, m.B);
+    // Qn and Qa are image gradients of the record re-labelled image_size = S, anti_aliasing = 0 over the same maps
+    AttrMaps mq = m;
+    mq.aa = 0;
+    if (grad_image) {
+        const long n_acc = (long)image_batch * image_height * image_width * 3;
+        const UvAdjoint a = uv_adjoint_clear_max(mq, m.S, 3, Qa, scratch, n_acc, st);
+        LAUNCH("k_uv_texture_images_scatter", k_uv_texture_images_scatter,
+               dim3(std::min(blocks_for(a.n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, mq, tx, (const float*)Qa,
+               (const unsigned*)a.block_max, a.n_max, a.frac, a.acc);
+        LAUNCH("k_uv_texture_images_convert", k_uv_texture_images_convert,
+               dim3(std::min(blocks_for(n_acc, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)a.acc, n_acc,
+               (const unsigned*)a.block_max, a.n_max, a.frac, grad_image);
+    }
+    if (!grad_normals) return check_launch();
+    const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
+    return face_sums_gather(
+        mq, vis, *adjacency, gather_scratch, num_vertices, 3, normals_batch == 1, grad_normals, st,
+        [&](unsigned small_blocks, unsigned large_blocks, hipStream_t s2) {
+            LAUNCH("k_vertex_attribute_face_sums", k_vertex_attribute_face_sums, dim3(small_blocks, 1), dim3(256), s2, mq,
+                   (const float*)Qn, 3, (const int*)vis.list, (const int*)vis.count, gather_scratch);
+            LAUNCH("k_vertex_attribute_large_face_sums", k_vertex_attribute_large_face_sums, dim3(large_blocks, 1),
+                   dim3(RG_BLOCK), s2, mq, (const float*)Qn, 3, (const int*)vis.list, (const int*)vis.count, gather_scratch);
+        });
+}
+
+D3M_EXPORT int d3m_sh_uv_fragment_pixel_grads(const d3m_fragments* fragments, const float* normals, int normals_batch,
+                                              const float* sh, int sh_batch, int num_vertices, const float* faces_uv,
+                                              const float* image, int image_batch, int image_height, int image_width,
+                                              int texture_wrapping, const float* grad_images, float* pixel_grads,
+                                              d3m_stream_t stream) {
+    AttrMaps m;
+    ShfInputs in;
+    UvTexture tx;
+    if (!grad_images || !pixel_grads || misaligned4(grad_images) || misaligned4(pixel_grads)) return D3M_ERR_INVALID;
+    if (!sh_uv_fragments_ok(fragments, normals, normals_batch, sh, sh_batch, num_vertices, faces_uv, image, image_batch,
+                            image_height, image_width, texture_wrapping, m, in, tx))
+        return D3M_ERR_INVALID;
+    LAUNCH("k_sh_uv_fragment_backward_pixels", k_sh_uv_fragment_backward_pixels, dim3(shf_parts((long)m.S * m.S), m.B),
+           dim3(SET_BLOCK), (hipStream_t)stream, m, in, tx, image, grad_images, (float*)nullptr, (float*)nullptr, pixel_grads,
            (float*)nullptr);
     return check_launch();
 }

@@ -107,6 +107,18 @@ __device__ __forceinline__ void shf_pixel(const AttrMaps& m, const ShfInputs& in
     }
 }
 
+// gm = dL/dm of the pixel from gn = dL/dn (THE ADJOINT above; d3m_sh_uv_fragments.h calls it too)
+__device__ __forceinline__ void shf_normal_gradient(const ShfPixel& px, const float* gn, float* gm) {
+    if (px.r >= SS_EPS) {
+        const float dot = (px.n[0] * gn[0] + px.n[1] * gn[1]) + px.n[2] * gn[2];
+#pragma unroll
+        for (int k = 0; k < 3; k++) gm[k] = (gn[k] - px.n[k] * dot) / px.r;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++) gm[k] = gn[k] / SS_EPS;
+    }
+}
+
 // ---- forward: fr_output_pixel_walk (d3m_fragments.h) with C = 3; a covered pixel's three values are formed in the gather -----
 __global__ void __launch_bounds__(256) k_sh_fragment_images(AttrMaps m, ShfInputs in, const float* __restrict__ background,
                                                            float* __restrict__ images, float* __restrict__ alpha) {
@@ -166,14 +178,7 @@ __global__ void __launch_bounds__(SET_BLOCK) k_sh_fragment_backward_pixels(AttrM
                 gn[0] += gs * d[0]; gn[1] += gs * d[1]; gn[2] += gs * d[2];
             }
             float gm[3];
-            if (px.r >= SS_EPS) {
-                const float dot = (px.n[0] * gn[0] + px.n[1] * gn[1]) + px.n[2] * gn[2];
-#pragma unroll
-                for (int k = 0; k < 3; k++) gm[k] = (gn[k] - px.n[k] * dot) / px.r;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 3; k++) gm[k] = gn[k] / SS_EPS;
-            }
+            shf_normal_gradient(px, gn, gm);
             const size_t at = (size_t)b * q_view + (size_t)(S - 1 - y) * S + x;       // output orientation: rows reversed
             if (Qn) {
 #pragma unroll

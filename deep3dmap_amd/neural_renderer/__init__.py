@@ -14,6 +14,7 @@ from .rasterize import (Rasterize, RasterizeFunction, rasterize, rasterize_depth
                         rasterize_silhouettes)
 from .renderer import Renderer
 from .sh_fragments import shade_fragments
+from .sh_uv_fragments import shade_uv_texture
 from .smooth_shading import SHLight, sh_basis, sh_vertex_colors, vertex_normals
 from .uv_bake import bake_uv_texture, uv_layout_fragments
 from .uv_fill import fill_uv_texture, fuse_uv_textures

@@ -8,8 +8,9 @@ import numpy
 import torch
 import torch.nn as nn
 
-from . import (attributes as _attributes, cameras, mesh_ops, sh_fragments as _sh_fragments, smooth_shading as _smooth_shading,
-               uv_bake as _uv_bake, uv_fill as _uv_fill, uv_texture_images as _uv_texture_images)
+from . import (attributes as _attributes, cameras, mesh_ops, sh_fragments as _sh_fragments,
+               sh_uv_fragments as _sh_uv_fragments, smooth_shading as _smooth_shading, uv_bake as _uv_bake, uv_fill as _uv_fill,
+               uv_texture_images as _uv_texture_images)
 from .antialias import antialias as _antialias_images
 from .rasterize import (light_on_device, rasterize, rasterize_depth, rasterize_lit, rasterize_lit_fit,
                         rasterize_lit_image_grid, rasterize_mesh_modes, rasterize_rgbad, rasterize_silhouettes)
@@ -337,6 +338,26 @@ class Renderer(nn.Module):
             return self._antialiased(images, alpha, fr, sv) if antialias else (images, alpha)
         fr = self.fragments(vertices.detach() if torch.is_tensor(vertices) else vertices, faces, K, R, t, dist_coeffs, orig_size)
         return _sh_fragments.shade_fragments(normals, sh, fr, colors, background)
+
+    def render_uv_shaded(self, vertices, faces, sh, image, faces_uv, normals=None, texture_wrapping='REPEAT', background=None,
+                         K=None, R=None, t=None, dist_coeffs=None, orig_size=None, geometry_grad=False, antialias=False):
+        """(images [B,3,s,s], alpha [B,s,s]) of the mesh textured by the UV albedo `image` [H,W,3] or [B,H,W,3] through
+        faces_uv [F,3,2] and lit PER PIXEL by the spherical-harmonic light sh [3,9] or [B,3,9]: fragments() followed by
+        shade_uv_texture (sh_uv_fragments.py), differentiable in image, sh and normals; the product is formed at every
+        internal pixel, before the pooling of a supersampling renderer.  normals=None takes nr.vertex_normals(vertices,
+        faces) IN THE GRAPH, as render_sh_shaded does.  geometry_grad / antialias: as in render_sh_shaded (the interior
+        geometry gradient through shade_uv_texture's screen_vertices; the silhouette gradient through one nr.antialias
+        call, a renderer with anti_aliasing=False only: ValueError before any launch otherwise)."""
+        self._check_antialias(antialias)
+        if normals is None:
+            normals = _smooth_shading.vertex_normals(vertices, faces)
+        if geometry_grad or antialias:
+            fr, sv = self._fragments_with_vertices(vertices, faces, K, R, t, dist_coeffs, orig_size)
+            images, alpha = _sh_uv_fragments.shade_uv_texture(image, faces_uv, normals, sh, fr, texture_wrapping, background,
+                                                              screen_vertices=sv if geometry_grad else None)
+            return self._antialiased(images, alpha, fr, sv) if antialias else (images, alpha)
+        fr = self.fragments(vertices.detach() if torch.is_tensor(vertices) else vertices, faces, K, R, t, dist_coeffs, orig_size)
+        return _sh_uv_fragments.shade_uv_texture(image, faces_uv, normals, sh, fr, texture_wrapping, background)
 
     def render_rgb_image_grid(self, vertices, image, K=None, R=None, t=None, dist_coeffs=None, orig_size=None):
         """render_rgb of the grid mesh of a depth map (vertices [B,h*w,3], one per pixel, row-major) textured by `image`

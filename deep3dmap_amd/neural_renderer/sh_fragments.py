@@ -121,8 +121,9 @@ def shade_fragments(normals, sh, fragments, colors=None, background=None, cache=
     normalised per pixel and lit by `sh` f32 [3,9] or [B,3,9] (channel, basis term: sh_vertex_colors' layout, SH_A's
     constants); `colors` None or per-vertex albedo f32 [V,3] / [B,V,3] interpolated alike and multiplied in.  background: None
     (zeros), a float or [3], as interpolate_vertex_attributes takes it; an uncovered pixel takes it.  With a supersampled
-    record the shading is evaluated at every internal pixel and then pooled 2x2.  A caller who fits a uv albedo calls this
-    with colors=None and background=1.0 and multiplies the result with sample_uv_texture's picture.
+    record the shading is evaluated at every internal pixel and then pooled 2x2.  A caller who fits a uv albedo calls
+    shade_uv_texture (sh_uv_fragments.py), which multiplies the looked-up albedo in at every internal pixel: this node's picture
+    times sample_uv_texture's is that product only without supersampling and away from the silhouette.
 
     One autograd node, differentiable in normals, sh and colors; alpha has the bits of interpolate_vertex_attributes' alpha
     and is not differentiable.  Every sum of the backward has a fixed order, no float atomics are used, nothing is cleared

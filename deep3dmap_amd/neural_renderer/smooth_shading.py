@@ -209,3 +209,10 @@ class SHLight(nn.Module):
         screen_vertices."""
         from .sh_fragments import shade_fragments
         return shade_fragments(normals, self.sh, fragments, colors=colors, **kw)
+
+    def shade_uv_texture(self, image, faces_uv, normals, fragments, **kw):
+        """(images [B,3,s,s], alpha [B,s,s]) of this light PER PIXEL on the UV albedo `image` over a Fragments record:
+        sh_uv_fragments.shade_uv_texture with the module's coefficients (per_set must then be None or the record's views);
+        kw: its texture_wrapping, background, cache and screen_vertices."""
+        from .sh_uv_fragments import shade_uv_texture
+        return shade_uv_texture(image, faces_uv, normals, self.sh, fragments, **kw)

@@ -1201,6 +1201,52 @@ int d3m_sh_fragment_images_backward(const d3m_fragments* fragments, const float*
 int d3m_sh_fragment_pixel_grads(const d3m_fragments* fragments, const float* normals, int normals_batch, const float* sh,
                                 int sh_batch, const float* colors, int colors_batch, int num_vertices,
                                 const float* grad_images, float* pixel_grads, d3m_stream_t stream);
+/* Per-pixel spherical-harmonic shading of a UV albedo texture over a coverage record (an addition;
+ * csrc/d3m_sh_uv_fragments.h states the function and the order of every sum): image [image_batch, H, W, 3] is looked up at
+ * every internal pixel as d3m_uv_texture_images looks it up (faces_uv [num_tri, 3, 2], wrapped per corner by texture_wrapping:
+ * REPEAT, MIRRORED_REPEAT or CLAMP_TO_EDGE) and multiplied THERE, before the pooling of a supersampled record, with the light
+ * of d3m_sh_fragment_images (normals [normals_batch, V, 3], sh [sh_batch, 3, 9], no per-vertex colours): value_k = a_k sum_j
+ * sh[k,j] H_j(n).  Each batch is 1 (shared by the views) or B.  background [3] or NULL (zeros).  WRITES every element of images
+ * [B, 3, image_size, image_size] and alpha [B, image_size, image_size] (alpha: the bits of d3m_vertex_attribute_images').  One
+ * launch (k_sh_uv_fragment_images).  D3M_ERR_INVALID, before any launch: what d3m_sh_fragment_images refuses of the record,
+ * normals, sh and num_vertices; what d3m_uv_texture_images refuses of faces_uv, the image's sizes and batch (with three
+ * channels) and the wrapping; a NULL or misaligned image / images / alpha, a misaligned background. */
+int d3m_sh_uv_fragment_images(const d3m_fragments* fragments, const float* normals, int normals_batch, const float* sh,
+                              int sh_batch, int num_vertices, const float* faces_uv, const float* image, int image_batch,
+                              int image_height, int image_width, int texture_wrapping, const float* background, float* images,
+                              float* alpha, d3m_stream_t stream);
+/* Bytes of scratch of d3m_sh_uv_fragment_images_backward, with S = raster_size: d3m_uv_texture_images_scratch_bytes(image_batch,
+ * H, W, 3, batch_size, S) rounded up to 8, then floats: d3m_vertex_attribute_scratch_floats(batch_size, num_faces, 3,
+ * adjacency), the two gradient images 2 B 3 S S, the light's partial sums B * min(ceil(S S / 1024), 256) * 27.  0 for sizes
+ * that are refused. */
+size_t d3m_sh_uv_fragment_scratch_bytes(int batch_size, int num_faces, int raster_size, int image_batch, int image_height,
+                                        int image_width, const d3m_csr* adjacency);
+/* The adjoint: grad_images [B, 3, image_size, image_size] -> grad_normals [normals_batch, V, 3], grad_sh [sh_batch, 3, 9],
+ * grad_image [image_batch, H, W, 3] and pixel_grads [B, S, S, 3] (d3m_sh_uv_fragment_pixel_grads' map, written by the same
+ * per-pixel launch); each may be NULL (not computed), not all four; every element of what is given is WRITTEN, the gradient of
+ * a shared input summed over the views (normals, sh: in ascending order; the image: in 64-bit fixed point, independent of
+ * order, with d3m_uv_texture_images_backward's rules for a zero, an Inf or a NaN gradient and an untouched texel).  scratch (8-byte
+ * aligned) needs no initialisation.  No float atomics.  Launches: k_sh_uv_fragment_backward_pixels; k_sh_fragment_finish for
+ * grad_sh; for grad_image k_uv_texture_images_clear_max, k_uv_texture_images_scatter, k_uv_texture_images_convert; for
+ * grad_normals k_vertex_attribute_face_sums, k_vertex_attribute_large_face_sums, k_vertex_attribute_adjoint_rows, and
+ * k_vertex_attribute_adjoint_chunks on a mesh with long rows.  D3M_ERR_INVALID, before any launch: what
+ * d3m_sh_uv_fragment_images refuses of the record and the inputs, a NULL or too small visibility blob, what d3m_csr lists
+ * (num_rows = num_vertices), NULL items, a NULL or misaligned grad_images / scratch, all four results NULL, a misaligned
+ * result, 3 num_tri beyond 2^31 - 1; D3M_ERR_WORKSPACE: scratch_bytes below d3m_sh_uv_fragment_scratch_bytes(). */
+int d3m_sh_uv_fragment_images_backward(const d3m_fragments* fragments, const float* normals, int normals_batch, const float* sh,
+                                       int sh_batch, int num_vertices, const float* faces_uv, const float* image,
+                                       int image_batch, int image_height, int image_width, int texture_wrapping,
+                                       const float* grad_images, const d3m_csr* adjacency, void* scratch, size_t scratch_bytes,
+                                       float* grad_normals, float* grad_sh, float* grad_image, float* pixel_grads,
+                                       d3m_stream_t stream);
+/* pixel_grads [B, S, S, 3] = dL/du_c of the shaded images for d3m_fragment_geometry_backward: h_c = dL/dm . n_c + the lookup's
+ * slopes along pos times the corner's wrapped uv, every element WRITTEN (+0 where uncovered) -- for a caller who wants nothing
+ * else of the adjoint.  One launch (k_sh_uv_fragment_backward_pixels).  D3M_ERR_INVALID, before any launch: what
+ * d3m_sh_uv_fragment_images refuses of the record and the inputs, a NULL or misaligned grad_images / pixel_grads. */
+int d3m_sh_uv_fragment_pixel_grads(const d3m_fragments* fragments, const float* normals, int normals_batch, const float* sh,
+                                   int sh_batch, int num_vertices, const float* faces_uv, const float* image, int image_batch,
+                                   int image_height, int image_width, int texture_wrapping, const float* grad_images,
+                                   float* pixel_grads, d3m_stream_t stream);
 /* Analytic edge antialiasing of an image drawn over a coverage record, and its silhouette gradient (an addition;
  * csrc/d3m_antialias.h states the function, the pair decision and the order of every sum).  The record must be one without
  * anti-aliasing (S = image_size) that d3m_forward_face_index_map_mesh made from screen_vertices [B, V, 3];  side_opposite
