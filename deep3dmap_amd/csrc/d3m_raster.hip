@@ -23,6 +23,7 @@
 #include "d3m_antialias.h"
 #include "d3m_uv_bake.h"
 #include "d3m_uv_fill.h"
+#include "d3m_uv_texture_reg.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -3411,6 +3412,140 @@ D3M_EXPORT int d3m_uv_fill_textures_backward(const float* weights, const float* 
            dim3(256), st, uf, batch_size, levels ? uf.L : 0, weights, valid, (const int*)counts, (const float*)G, grad_texture,
            grad_textures);
     return check_launch();
+}
+
+// Regularisers of a UV texture (d3m_uv_texture_reg.h).  What the entry points refuse of the sizes, weights and inputs; `a`: the
+// arguments as the kernels read them.
+static bool uv_texture_reg_ok(const float* texture, int B, int H, int W, int C, const float* mask, int mask_batch, float w_smooth,
+                              float smooth_eps, float w_sym, float w_flat, float w_anchor, const float* reference,
+                              int reference_batch, const float* reference_weights, int rw_batch, UvTextureReg& a) {
+    if (!texture || B < 1 || B > 65535 || H < 1 || H > UVT_MAX_SIZE || W < 1 || W > UVT_MAX_SIZE || C < 1 || C > UVR_MAX_CHANNELS)
+        return false;
+    const float w[4] = {w_smooth, w_sym, w_flat, w_anchor};
+    for (float v : w)
+        if (!(v >= 0.f) || std::isinf(v)) return false;                           // (NaN fails too)
+    if (!(w_smooth > 0.f || w_sym > 0.f || w_flat > 0.f || w_anchor > 0.f)) return false;
+    if (smooth_eps != UVR_NO_EPS && (!(smooth_eps > 0.f) || std::isinf(smooth_eps))) return false;
+    const uintptr_t texel_align = C == 4 ? 15 : (C == 2 ? 7 : 3);
+    if (((uintptr_t)texture & texel_align) || misaligned4(mask) || misaligned4(reference_weights)) return false;
+    if (mask && mask_batch != 1 && mask_batch != B) return false;
+    if (w_anchor > 0.f) {
+        if (!reference || ((uintptr_t)reference & texel_align)) return false;
+        if (reference_batch != 1 && reference_batch != B) return false;
+        if (reference_weights && rw_batch != 1 && rw_batch != B) return false;
+    }
+    const bool anchor = w_anchor > 0.f;
+    a = UvTextureReg{texture, mask, anchor ? reference : nullptr, anchor ? reference_weights : nullptr, B, H, W,
+                     mask ? mask_batch : 0, anchor ? reference_batch : 0, anchor && reference_weights ? rw_batch : 0,
+                     w_smooth, w_sym, w_flat, w_anchor, smooth_eps};
+    return true;
+}
+
+// the scratch, in 4-byte words: the statistics' float partials, their counts, the value's partials, the statistics
+struct UvTextureRegScratch {
+    size_t stat_partial, count_partial, value_partial, stats, words;
+};
+static UvTextureRegScratch uv_texture_reg_scratch(int B, int H, int W) {
+    const size_t rows = (size_t)B * uvr_parts((long)H * W);
+    UvTextureRegScratch s;
+    s.stat_partial = 0;
+    s.count_partial = s.stat_partial + rows * UVR_STAT_SUMS;
+    s.value_partial = s.count_partial + rows * UVR_COUNTS;
+    s.stats = s.value_partial + rows * UVR_VALUE_SUMS;
+    s.words = s.stats + (size_t)B * (UVR_STATS + UVR_MAX_CHANNELS);
+    return s;
+}
+
+D3M_EXPORT size_t d3m_uv_texture_regularizer_scratch_bytes(int batch_size, int image_height, int image_width) {
+    if (batch_size < 1 || batch_size > 65535 || image_height < 1 || image_height > UVT_MAX_SIZE || image_width < 1 ||
+        image_width > UVT_MAX_SIZE)
+        return 0;
+    return uv_texture_reg_scratch(batch_size, image_height, image_width).words * sizeof(float);
+}
+
+#define UVR_BY_CHANNELS(C, CALL)    \
+    do {                            \
+        if ((C) == 1) { CALL(1); }  \
+        else if ((C) == 2) { CALL(2); } \
+        else if ((C) == 3) { CALL(3); } \
+        else { CALL(4); }           \
+    } while (0)
+
+// stats == NULL: the statistics passes run first, into scratch
+static int uv_texture_reg_run(const UvTextureReg& a, int C, const float* stats, float* stats_out, const float* grad_scale,
+                              void* scratch, size_t scratch_bytes, float* value, float* grad, hipStream_t st) {
+    const UvTextureRegScratch lay = uv_texture_reg_scratch(a.B, a.H, a.W);
+    const bool need_scratch = !stats || value;
+    if (need_scratch) {
+        if (!scratch || misaligned4(scratch)) return D3M_ERR_INVALID;
+        if (scratch_bytes < lay.words * sizeof(float)) return D3M_ERR_WORKSPACE;
+    }
+    float* words = (float*)scratch;
+    const int parts = uvr_parts((long)a.H * a.W);
+    const dim3 grid(parts, a.B), finish_grid(a.B);
+    if (!stats) {
+        float* stat_partial = words + lay.stat_partial;
+        int* count_partial = (int*)(words + lay.count_partial);
+        if (!stats_out) stats_out = words + lay.stats;
+#define UVR_STATS_CALL(NC)                                                                                                  \
+    LAUNCH("k_uv_texture_reg_stats", k_uv_texture_reg_stats<NC>, grid, dim3(SET_BLOCK), st, a, stat_partial, count_partial)
+        UVR_BY_CHANNELS(C, UVR_STATS_CALL);
+#undef UVR_STATS_CALL
+        LAUNCH("k_uv_texture_reg_stats_finish", k_uv_texture_reg_stats_finish, finish_grid, dim3(SET_BLOCK), st, a, C,
+               (const float*)stat_partial, (const int*)count_partial, parts, stats_out);
+        stats = stats_out;
+    }
+    float* value_partial = value ? words + lay.value_partial : nullptr;
+#define UVR_TERMS_CALL(NC)                                                                                                  \
+    do {                                                                                                                    \
+        if (a.eps == UVR_NO_EPS)                                                                                            \
+            LAUNCH("k_uv_texture_reg_terms", (k_uv_texture_reg_terms<NC, false>), grid, dim3(SET_BLOCK), st, a, stats,      \
+                   grad_scale, value_partial, grad);                                                                        \
+        else                                                                                                                \
+            LAUNCH("k_uv_texture_reg_terms", (k_uv_texture_reg_terms<NC, true>), grid, dim3(SET_BLOCK), st, a, stats,       \
+                   grad_scale, value_partial, grad);                                                                        \
+    } while (0)
+    UVR_BY_CHANNELS(C, UVR_TERMS_CALL);
+#undef UVR_TERMS_CALL
+    if (value)
+        LAUNCH("k_uv_texture_reg_value_finish", k_uv_texture_reg_value_finish, finish_grid, dim3(SET_BLOCK), st, a, C, stats,
+               (const float*)value_partial, parts, value);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_uv_texture_regularizer(const float* texture, int batch_size, int image_height, int image_width,
+                                          int num_channels, const float* mask, int mask_batch, float w_smooth, float smooth_eps,
+                                          float w_symmetry, float w_flat, float w_anchor, const float* reference,
+                                          int reference_batch, const float* reference_weights, int reference_weights_batch,
+                                          void* scratch, size_t scratch_bytes, float* stats, float* value, d3m_stream_t stream) {
+    UvTextureReg a;
+    if (!uv_texture_reg_ok(texture, batch_size, image_height, image_width, num_channels, mask, mask_batch, w_smooth, smooth_eps,
+                           w_symmetry, w_flat, w_anchor, reference, reference_batch, reference_weights, reference_weights_batch,
+                           a))
+        return D3M_ERR_INVALID;
+    if (!stats || !value || misaligned4(stats) || misaligned4(value)) return D3M_ERR_INVALID;
+    return uv_texture_reg_run(a, num_channels, nullptr, stats, nullptr, scratch, scratch_bytes, value, nullptr,
+                              (hipStream_t)stream);
+}
+
+D3M_EXPORT int d3m_uv_texture_regularizer_grad(const float* texture, int batch_size, int image_height, int image_width,
+                                               int num_channels, const float* mask, int mask_batch, float w_smooth,
+                                               float smooth_eps, float w_symmetry, float w_flat, float w_anchor,
+                                               const float* reference, int reference_batch, const float* reference_weights,
+                                               int reference_weights_batch, const float* stats, const float* grad_scale,
+                                               void* scratch, size_t scratch_bytes, float* value, float* grad_texture,
+                                               d3m_stream_t stream) {
+    UvTextureReg a;
+    if (!uv_texture_reg_ok(texture, batch_size, image_height, image_width, num_channels, mask, mask_batch, w_smooth, smooth_eps,
+                           w_symmetry, w_flat, w_anchor, reference, reference_batch, reference_weights, reference_weights_batch,
+                           a))
+        return D3M_ERR_INVALID;
+    if (!value && !grad_texture) return D3M_ERR_INVALID;
+    const uintptr_t texel_align = num_channels == 4 ? 15 : (num_channels == 2 ? 7 : 3);
+    if (((uintptr_t)grad_texture & texel_align) || misaligned4(stats) || misaligned4(grad_scale) || misaligned4(value))
+        return D3M_ERR_INVALID;
+    return uv_texture_reg_run(a, num_channels, stats, nullptr, grad_scale, scratch, scratch_bytes, value, grad_texture,
+                              (hipStream_t)stream);
 }
 
 D3M_EXPORT int d3m_create_texture_image(const float* vertices_all, const float* textures, float* image, int num_faces,

@@ -18,6 +18,8 @@ from .sh_uv_fragments import shade_uv_texture
 from .smooth_shading import SHLight, sh_basis, sh_vertex_colors, vertex_normals
 from .uv_bake import bake_uv_texture, uv_layout_fragments
 from .uv_fill import fill_uv_texture, fuse_uv_textures
+from .uv_texture_regularizers import (UvTextureRegularizer, uv_layout_mask, uv_texture_anchor, uv_texture_flatness,
+                                      uv_texture_regularizer, uv_texture_smoothness, uv_texture_symmetry)
 from .uv_texture_images import sample_uv_texture, texture_mip_pyramid, uv_texture_lod
 from .uv_textures import UVTextures, textures_from_image
 from .vertex_colors import VertexColors, textures_from_vertex_colors

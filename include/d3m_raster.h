@@ -1358,6 +1358,44 @@ int d3m_uv_fill_textures_backward(const float* weights, const float* valid, cons
                                   const float* grad_texture, int batch_size, int image_height, int image_width,
                                   int num_channels, int fill, void* scratch, size_t scratch_bytes, float* grad_textures,
                                   d3m_stream_t stream);
+/* Regularisers of a UV texture (an addition; csrc/d3m_uv_texture_reg.h states the four terms, their counts and the order of
+ * every sum): smoothness over the 4-neighbour pairs, left-right symmetry (u -> 1 - u), flatness and an anchor to a reference
+ * texture, per image.  texture [B, H, W, C], 1 <= B <= 65535, 1 <= C <= 4, H, W <= 32768 (any H, W); mask [mask_batch, H, W],
+ * mask_batch 1 or B, or NULL (every texel active; mask_batch ignored): a texel is active iff its mask is > 0; reference
+ * [reference_batch, H, W, C], reference_batch 1 or B; reference_weights [reference_weights_batch, H, W], batch 1 or B, or NULL
+ * (1).  w_* >= 0, not all 0; a term of weight 0 is not evaluated and its inputs are not read (reference and
+ * reference_weights may be NULL with w_anchor == 0).  smooth_eps: D3M_UV_TEXTURE_REG_NO_EPS for the squared difference, else
+ * > 0 (Charbonnier).  What every entry point refuses with D3M_ERR_INVALID before any launch: sizes, batches or C outside these
+ * ranges, a negative or NaN weight, all weights 0, another smooth_eps <= 0 or NaN, w_anchor > 0 without a reference, a NULL
+ * texture, a texture / reference / gradient not aligned to 16 bytes with C = 4, 8 with C = 2 and 4 otherwise, another
+ * misaligned pointer. */
+#define D3M_UV_TEXTURE_REG_NO_EPS (-1.0f)
+/* Bytes of scratch of the two entry points below; 0 for sizes that are refused. */
+size_t d3m_uv_texture_regularizer_scratch_bytes(int batch_size, int image_height, int image_width);
+/* WRITES value [B] and stats [B, 4 + C]: the per-image coefficients weight / (count C) of the four terms (0 where the
+ * count is 0) and the C channel means of the active texels, which d3m_uv_texture_regularizer_grad reads.  The counts are
+ * taken on the device on every call.  Four launches (k_uv_texture_reg_stats, k_uv_texture_reg_stats_finish,
+ * k_uv_texture_reg_terms, k_uv_texture_reg_value_finish), whatever B, H, W, C and the weights.  scratch needs no
+ * initialisation.  D3M_ERR_INVALID also for a NULL value or stats, a NULL or misaligned scratch; D3M_ERR_WORKSPACE:
+ * scratch_bytes below d3m_uv_texture_regularizer_scratch_bytes(). */
+int d3m_uv_texture_regularizer(const float* texture, int batch_size, int image_height, int image_width, int num_channels,
+                               const float* mask, int mask_batch, float w_smooth, float smooth_eps, float w_symmetry,
+                               float w_flat, float w_anchor, const float* reference, int reference_batch,
+                               const float* reference_weights, int reference_weights_batch, void* scratch, size_t scratch_bytes,
+                               float* stats, float* value, d3m_stream_t stream);
+/* Value and gradient.  grad_texture [B, H, W, C] (NULL: not wanted): every element WRITTEN, the gradient of image b times
+ * grad_scale[b] (device memory; NULL: 1); exactly +0 at inactive texels and where grad_scale[b] == 0.  value [B] (NULL: not
+ * wanted).  stats: the forward's [B, 4 + C], or NULL: they are computed here into scratch.  A gather per texel: no float
+ * atomics, nothing cleared.  Launches: k_uv_texture_reg_terms alone with stats and without value; + k_uv_texture_reg_value_finish
+ * with value; + k_uv_texture_reg_stats and k_uv_texture_reg_stats_finish without stats: at most four.  D3M_ERR_INVALID also
+ * for value and grad_texture both NULL, a NULL or misaligned scratch where one is needed (without stats, with value);
+ * D3M_ERR_WORKSPACE as above. */
+int d3m_uv_texture_regularizer_grad(const float* texture, int batch_size, int image_height, int image_width, int num_channels,
+                                    const float* mask, int mask_batch, float w_smooth, float smooth_eps, float w_symmetry,
+                                    float w_flat, float w_anchor, const float* reference, int reference_batch,
+                                    const float* reference_weights, int reference_weights_batch, const float* stats,
+                                    const float* grad_scale, void* scratch, size_t scratch_bytes, float* value,
+                                    float* grad_texture, d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
