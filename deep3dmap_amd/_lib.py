@@ -262,6 +262,13 @@ _SIGNATURES = {
     "d3m_uv_texture_regularizer": (_I, [_P, _I, _I, _I, _I, _P, _I, _F, _F, _F, _F, _F, _P, _I, _P, _I, _P, _SZ, _P, _P, _P]),
     "d3m_uv_texture_regularizer_grad": (_I, [_P, _I, _I, _I, _I, _P, _I, _F, _F, _F, _F, _F, _P, _I, _P, _I, _P, _P, _P, _SZ, _P,
                                              _P, _P]),
+    "d3m_chamfer_distance_scratch_bytes": (_SZ, [_I, _I, _I]),
+    "d3m_point_set_tile": (_I, []),
+    "d3m_point_set_queries_per_lane": (_I, []),
+    "d3m_point_set_splits": (_I, [_I, _I, _I]),
+    "d3m_nearest_points": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _SZ, _P, _P, _P]),
+    "d3m_chamfer_distance": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _F, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P]),
+    "d3m_chamfer_distance_backward": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _SZ, _P, _P, _P]),
     "d3m_mesh_regularizer_scratch_floats": (_SZ, [_I, ctypes.POINTER(D3MMeshTopology)]),
     "d3m_mesh_regularizer": (_I, [_P, _I, ctypes.POINTER(D3MMeshTopology), _F, _F, _F, _F, _P, _SZ, _P, _P, _P, _I, _P]),
     "d3m_morphable_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -24,6 +24,7 @@
 #include "d3m_uv_bake.h"
 #include "d3m_uv_fill.h"
 #include "d3m_uv_texture_reg.h"
+#include "d3m_point_sets.h"
 #include "d3m_mesh.h"
 #include "d3m_uv.h"
 #include "d3m_backward.h"
@@ -3546,6 +3547,191 @@ D3M_EXPORT int d3m_uv_texture_regularizer_grad(const float* texture, int batch_s
         return D3M_ERR_INVALID;
     return uv_texture_reg_run(a, num_channels, stats, nullptr, grad_scale, scratch, scratch_bytes, value, grad_texture,
                               (hipStream_t)stream);
+}
+
+// Nearest points and chamfer distances between point sets (d3m_point_sets.h).  The scratch, in bytes from its start: the keys of
+// both directions (forward), or the accumulators of both sets and the block maxima (backward); then the value's partial sums.
+struct PointSetScratch {
+    size_t keys_ab, keys_ba, partial_ab, partial_ba, acc_a, acc_b, block_max, bytes;
+};
+static bool point_set_sizes_ok(int B, int N, int M) {
+    return B >= 1 && B <= 65535 && N >= 1 && N <= PSET_MAX_POINTS && M >= 1 && M <= PSET_MAX_POINTS;
+}
+static PointSetScratch point_set_scratch(int B, int N, int M) {
+    PointSetScratch s;
+    const size_t na = (size_t)B * N, nb = (size_t)B * M;
+    s.keys_ab = 0;
+    s.keys_ba = s.keys_ab + na * 8;
+    s.partial_ab = s.keys_ba + nb * 8;
+    s.partial_ba = s.partial_ab + (size_t)B * pset_parts(N) * 4;
+    const size_t forward = s.partial_ba + (size_t)B * pset_parts(M) * 4;
+    s.acc_a = 0;
+    s.acc_b = s.acc_a + na * 3 * 8;
+    s.block_max = s.acc_b + nb * 3 * 8;
+    const size_t backward = s.block_max + (size_t)PSET_FILL_BLOCKS * 4;
+    s.bytes = forward > backward ? forward : backward;
+    return s;
+}
+
+D3M_EXPORT size_t d3m_chamfer_distance_scratch_bytes(int batch_size, int num_points_a, int num_points_b) {
+    if (!point_set_sizes_ok(batch_size, num_points_a, num_points_b)) return 0;
+    return point_set_scratch(batch_size, num_points_a, num_points_b).bytes;
+}
+
+D3M_EXPORT int d3m_point_set_tile(void) { return PSET_TILE; }
+D3M_EXPORT int d3m_point_set_queries_per_lane(void) { return PSET_Q; }
+D3M_EXPORT int d3m_point_set_splits(int batch_size, int num_queries, int num_targets) {
+    if (!point_set_sizes_ok(batch_size, num_queries, num_targets)) return 0;
+    return pset_auto_splits(batch_size, num_queries, num_targets);
+}
+
+static inline bool misaligned8(const void* p) { return ((uintptr_t)p & 7) != 0; }
+static unsigned point_set_fill_blocks(size_t items) {
+    const size_t blocks = (items + 255) / 256;
+    return (unsigned)(blocks < 1 ? 1 : (blocks > PSET_FILL_BLOCKS ? PSET_FILL_BLOCKS : blocks));
+}
+
+static PsetDir point_set_dir(const float* q, const float* t, const int* len_q, const int* len_t, int B, int N, int M, int splits,
+                           char* scratch, size_t keys, size_t partial, int* index, float* dist2, bool want_value, bool on) {
+    PsetDir d{};
+    d.on = on ? 1 : 0;
+    d.N = N;
+    d.M = M;
+    d.parts = pset_parts(N);
+    d.splits = d.tiles_per_split = 1;
+    if (!on) return d;
+    d.q = q;
+    d.t = t;
+    d.len_q = len_q;
+    d.len_t = len_t;
+    d.keys = (unsigned long long*)(scratch + keys);
+    d.index = index;
+    d.dist2 = dist2;
+    d.partial = want_value ? (float*)(scratch + partial) : nullptr;
+    const int tiles = pset_tiles(M);
+    int sp = splits > 0 ? splits : pset_auto_splits(B, N, M);
+    const int most = (1 << 30) / pset_query_blocks(N);                     // query blocks x splits is the grid's x
+    if (sp > most) sp = most;
+    if (sp > tiles) sp = tiles;
+    d.tiles_per_split = (tiles + sp - 1) / sp;
+    d.splits = (tiles + d.tiles_per_split - 1) / d.tiles_per_split;       // no split without a tile
+    return d;
+}
+
+// the three launches that the two forward entry points share
+static void point_set_search(const PsetSearch& s, int squared, float tau2, hipStream_t st) {
+    const int n_ab = s.ab.on ? s.ab.N : 0, n_ba = s.ba.on ? s.ba.N : 0;
+    LAUNCH("k_pset_init", k_pset_init, dim3(point_set_fill_blocks((size_t)s.B * (n_ab > n_ba ? n_ab : n_ba))), dim3(256), st, s);
+    const unsigned dirs = s.ba.on ? 2 : 1;
+    unsigned units = 1, parts = 1;
+    if (s.ab.on) {
+        units = (unsigned)pset_query_blocks(s.ab.N) * (unsigned)s.ab.splits;
+        parts = (unsigned)s.ab.parts;
+    }
+    if (s.ba.on) {
+        const unsigned u = (unsigned)pset_query_blocks(s.ba.N) * (unsigned)s.ba.splits;
+        units = u > units ? u : units;
+        parts = (unsigned)s.ba.parts > parts ? (unsigned)s.ba.parts : parts;
+    }
+    LAUNCH("k_pset_nearest", k_pset_nearest, dim3(units, s.B, dirs), dim3(256), st, s);
+    LAUNCH("k_pset_resolve", k_pset_resolve, dim3(parts, s.B, dirs), dim3(SET_BLOCK), st, s, squared, tau2);
+}
+
+static bool point_set_inputs_ok(const float* a, const float* b, int B, int N, int M, const int* lengths_a, const int* lengths_b,
+                                int splits, const void* scratch) {
+    if (!point_set_sizes_ok(B, N, M) || !a || !b || !scratch || splits < 0) return false;
+    return !(misaligned4(a) || misaligned4(b) || misaligned4(lengths_a) || misaligned4(lengths_b) || misaligned8(scratch));
+}
+
+D3M_EXPORT int d3m_nearest_points(const float* points, const float* targets, int batch_size, int num_points, int num_targets,
+                                  const int* lengths, const int* target_lengths, int splits, void* scratch, size_t scratch_bytes,
+                                  int* index, float* dist2, d3m_stream_t stream) {
+    if (!point_set_inputs_ok(points, targets, batch_size, num_points, num_targets, lengths, target_lengths, splits, scratch))
+        return D3M_ERR_INVALID;
+    if (!index || !dist2 || misaligned4(index) || misaligned4(dist2)) return D3M_ERR_INVALID;
+    const PointSetScratch lay = point_set_scratch(batch_size, num_points, num_targets);
+    if (scratch_bytes < lay.bytes) return D3M_ERR_WORKSPACE;
+    PsetSearch s{};
+    s.B = batch_size;
+    s.ab = point_set_dir(points, targets, lengths, target_lengths, batch_size, num_points, num_targets, splits, (char*)scratch,
+                         lay.keys_ab, lay.partial_ab, index, dist2, false, true);
+    s.ba = point_set_dir(nullptr, nullptr, nullptr, nullptr, batch_size, num_targets, num_points, 0, nullptr, 0, 0, nullptr, nullptr,
+                         false, false);
+    point_set_search(s, 1, -1.f, (hipStream_t)stream);
+    return check_launch();
+}
+
+// truncate < 0: no truncation
+static bool point_set_options_ok(float truncate, float weight_ab, float weight_ba) {
+    if (std::isnan(truncate) || std::isinf(truncate)) return false;
+    if (!(weight_ab >= 0.f) || !(weight_ba >= 0.f) || std::isinf(weight_ab) || std::isinf(weight_ba)) return false;
+    return weight_ab > 0.f || weight_ba > 0.f;
+}
+
+D3M_EXPORT int d3m_chamfer_distance(const float* a, const float* b, int batch_size, int num_points_a, int num_points_b,
+                                    const int* lengths_a, const int* lengths_b, int squared, float truncate, float weight_ab,
+                                    float weight_ba, int splits, void* scratch, size_t scratch_bytes, int* index_ab, float* dist2_ab,
+                                    int* index_ba, float* dist2_ba, float* coef, float* value, d3m_stream_t stream) {
+    const int B = batch_size, N = num_points_a, M = num_points_b;
+    if (!point_set_inputs_ok(a, b, B, N, M, lengths_a, lengths_b, splits, scratch)) return D3M_ERR_INVALID;
+    if (!point_set_options_ok(truncate, weight_ab, weight_ba)) return D3M_ERR_INVALID;
+    const bool ab = weight_ab > 0.f, ba = weight_ba > 0.f;
+    if ((ab && (!index_ab || !dist2_ab)) || (ba && (!index_ba || !dist2_ba)) || !coef || !value) return D3M_ERR_INVALID;
+    if (misaligned4(index_ab) || misaligned4(dist2_ab) || misaligned4(index_ba) || misaligned4(dist2_ba) || misaligned4(coef) ||
+        misaligned4(value))
+        return D3M_ERR_INVALID;
+    const PointSetScratch lay = point_set_scratch(B, N, M);
+    if (scratch_bytes < lay.bytes) return D3M_ERR_WORKSPACE;
+    PsetSearch s{};
+    s.B = B;
+    s.ab = point_set_dir(a, b, lengths_a, lengths_b, B, N, M, splits, (char*)scratch, lay.keys_ab, lay.partial_ab, index_ab, dist2_ab,
+                         true, ab);
+    s.ba = point_set_dir(b, a, lengths_b, lengths_a, B, M, N, splits, (char*)scratch, lay.keys_ba, lay.partial_ba, index_ba, dist2_ba,
+                         true, ba);
+    const hipStream_t st = (hipStream_t)stream;
+    point_set_search(s, squared != 0, truncate >= 0.f ? truncate * truncate : -1.f, st);
+    LAUNCH("k_pset_value_finish", k_pset_value_finish, dim3(B), dim3(SET_BLOCK), st, s, weight_ab, weight_ba, coef, value);
+    return check_launch();
+}
+
+D3M_EXPORT int d3m_chamfer_distance_backward(const float* a, const float* b, int batch_size, int num_points_a, int num_points_b,
+                                             const int* lengths_a, const int* lengths_b, const int* index_ab, const float* dist2_ab,
+                                             const int* index_ba, const float* dist2_ba, const float* coef, const float* upstream,
+                                             int upstream_per_query, int squared, float truncate, void* scratch,
+                                             size_t scratch_bytes, float* grad_a, float* grad_b, d3m_stream_t stream) {
+    const int B = batch_size, N = num_points_a, M = num_points_b;
+    if (!point_set_inputs_ok(a, b, B, N, M, lengths_a, lengths_b, 0, scratch)) return D3M_ERR_INVALID;
+    if (std::isnan(truncate) || std::isinf(truncate)) return D3M_ERR_INVALID;
+    if (!upstream || !grad_a || !grad_b || (!index_ab && !index_ba) || (index_ab && !dist2_ab) || (index_ba && !dist2_ba))
+        return D3M_ERR_INVALID;
+    if (upstream_per_query ? (coef || !index_ab || index_ba) : !coef) return D3M_ERR_INVALID;
+    if (misaligned4(index_ab) || misaligned4(dist2_ab) || misaligned4(index_ba) || misaligned4(dist2_ba) || misaligned4(coef) ||
+        misaligned4(upstream) || misaligned4(grad_a) || misaligned4(grad_b))
+        return D3M_ERR_INVALID;
+    const PointSetScratch lay = point_set_scratch(B, N, M);
+    if (scratch_bytes < lay.bytes) return D3M_ERR_WORKSPACE;
+    long long* acc_a = (long long*)((char*)scratch + lay.acc_a);
+    long long* acc_b = (long long*)((char*)scratch + lay.acc_b);
+    unsigned* block_max = (unsigned*)((char*)scratch + lay.block_max);
+    PsetAdjoint adj{};
+    adj.ab = PsetAdjDir{a, b, lengths_a, lengths_b, index_ab, dist2_ab, grad_a, acc_a, acc_b, N, M, 0};
+    adj.ba = PsetAdjDir{b, a, lengths_b, lengths_a, index_ba, dist2_ba, grad_b, acc_b, acc_a, M, N, 1};
+    adj.coef = coef;
+    adj.upstream = upstream;
+    adj.B = B;
+    adj.per_query = upstream_per_query != 0;
+    adj.squared = squared != 0;
+    adj.tau2 = truncate >= 0.f ? truncate * truncate : -1.f;
+    const int most = N > M ? N : M;
+    int log2_most = 0;
+    while ((1L << log2_most) < (long)most) log2_most++;
+    const int frac = 62 - log2_most;
+    const unsigned blocks = point_set_fill_blocks((size_t)B * most);
+    const hipStream_t st = (hipStream_t)stream;
+    LAUNCH("k_pset_direct", k_pset_direct, dim3(blocks), dim3(256), st, adj, block_max);
+    LAUNCH("k_pset_scatter", k_pset_scatter, dim3(blocks), dim3(256), st, adj, (const unsigned*)block_max, (int)blocks, frac);
+    LAUNCH("k_pset_convert", k_pset_convert, dim3(blocks), dim3(256), st, adj, (const unsigned*)block_max, (int)blocks, frac);
+    return check_launch();
 }
 
 D3M_EXPORT int d3m_create_texture_image(const float* vertices_all, const float* textures, float* image, int num_faces,

@@ -9,6 +9,7 @@ from .mesh_regularizers import (MeshRegularizer, edge_length_loss, laplacian_los
                                normal_consistency_loss)
 from .morphable import MorphableModel, morphable_vertices
 from .obj_io import Mesh, load_obj, save_obj
+from .point_sets import ChamferTarget, chamfer_distance, nearest_points
 from .pose import PoseHead, PosedPoints, pose_vertices
 from .rasterize import (Rasterize, RasterizeFunction, rasterize, rasterize_depth, rasterize_rgbad,
                         rasterize_silhouettes)

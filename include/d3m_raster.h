@@ -1396,6 +1396,48 @@ int d3m_uv_texture_regularizer_grad(const float* texture, int batch_size, int im
                                     const float* reference_weights, int reference_weights_batch, const float* stats,
                                     const float* grad_scale, void* scratch, size_t scratch_bytes, float* value,
                                     float* grad_texture, d3m_stream_t stream);
+/* Nearest points and chamfer distances between point sets (an addition; csrc/d3m_point_sets.h states the distance, the tie
+ * rule, the order of every sum and the fixed-point scatter of the adjoint).  a [B, N, 3] and b [B, M, 3] in f32, 1 <= B <= 65535,
+ * 1 <= N, M <= 2^30; lengths_a [B], lengths_b [B]: int32 in device memory, the ragged set sizes (clamped to 0 .. N and 0 .. M), or
+ * NULL: N and M.  splits: the number of workgroups the targets' tiles of d3m_point_set_tile() points are split over per query
+ * block, 0: d3m_point_set_splits() of the shapes; no result depends on it by a bit.  scratch: d3m_chamfer_distance_scratch_bytes()
+ * bytes aligned to 8, no initialisation needed.  What every entry point refuses with D3M_ERR_INVALID before any launch: sizes
+ * outside these ranges, a NULL a, b or scratch, a negative splits, a misaligned pointer, a NULL output that it writes;
+ * D3M_ERR_WORKSPACE: scratch_bytes below the query's answer. */
+/* Bytes of scratch of the three entry points below; 0 for sizes that are refused. */
+size_t d3m_chamfer_distance_scratch_bytes(int batch_size, int num_points_a, int num_points_b);
+/* The kernel's tile of targets, its queries per lane (a workgroup takes 256 times as many), and the split count it chooses for
+ * B sets of num_queries queries against num_targets targets (0 for sizes that are refused). */
+int d3m_point_set_tile(void);
+int d3m_point_set_queries_per_lane(void);
+int d3m_point_set_splits(int batch_size, int num_queries, int num_targets);
+/* WRITES every element of index [B, N] (int32) and dist2 [B, N]: for every point its nearest target (the lowest index among equal
+ * f32 distances) and the squared distance; -1 and +0 for a point at or beyond its set's length and for every point of an element
+ * without targets; -1 and NaN where every candidate distance is NaN.  Three launches (k_pset_init, k_pset_nearest, k_pset_resolve). */
+int d3m_nearest_points(const float* points, const float* targets, int batch_size, int num_points, int num_targets,
+                       const int* lengths, const int* target_lengths, int splits, void* scratch, size_t scratch_bytes, int* index,
+                       float* dist2, d3m_stream_t stream);
+/* WRITES value [B] = weight_ab L_ab + weight_ba L_ba, L_ab the mean over a's points of rho(dist2 to the nearest point of b), rho
+ * the identity (squared != 0) or the square root; truncate >= 0: a term with dist2 > truncate^2 contributes rho(truncate^2),
+ * truncate < 0: none.  Also WRITES the searches' index_ab, dist2_ab [B, N] and index_ba, dist2_ba [B, M] and coef [B, 2] =
+ * weight / set length (0 for an empty set), which d3m_chamfer_distance_backward reads.  A direction of weight 0 is not evaluated:
+ * its index and dist2 may be NULL and are not written.  Four launches (k_pset_init, k_pset_nearest, k_pset_resolve,
+ * k_pset_value_finish).  D3M_ERR_INVALID also for a negative or non-finite weight, both weights 0, a non-finite truncate. */
+int d3m_chamfer_distance(const float* a, const float* b, int batch_size, int num_points_a, int num_points_b, const int* lengths_a,
+                         const int* lengths_b, int squared, float truncate, float weight_ab, float weight_ba, int splits,
+                         void* scratch, size_t scratch_bytes, int* index_ab, float* dist2_ab, int* index_ba, float* dist2_ba,
+                         float* coef, float* value, d3m_stream_t stream);
+/* WRITES every element of grad_a [B, N, 3] and grad_b [B, M, 3], the argmin held constant: a point's direct term as a query plus
+ * minus the terms of the points whose nearest neighbour it is, summed in 64-bit fixed point (no float atomics; the same bits on
+ * every run).  index_* / dist2_* / coef: the forward's; a direction whose index is NULL is off.  upstream [B] in device memory,
+ * the gradient of value; or, with upstream_per_query != 0, upstream [B, N], the gradient of d3m_nearest_points' dist2 (coef and
+ * index_ba NULL).  Exactly +0 at truncated terms' direct gradients, beyond the sets' lengths and everywhere when every term is
+ * 0; NaN everywhere when a term is not finite.  Three launches (k_pset_direct, k_pset_scatter, k_pset_convert). */
+int d3m_chamfer_distance_backward(const float* a, const float* b, int batch_size, int num_points_a, int num_points_b,
+                                  const int* lengths_a, const int* lengths_b, const int* index_ab, const float* dist2_ab,
+                                  const int* index_ba, const float* dist2_ba, const float* coef, const float* upstream,
+                                  int upstream_per_query, int squared, float truncate, void* scratch, size_t scratch_bytes,
+                                  float* grad_a, float* grad_b, d3m_stream_t stream);
 /* Replaces create_texture_image_cuda (NR/cuda/create_texture_image_cuda.cpp:6-30, kernels
  * create_texture_image_cuda_kernel.cu:10-115, both launches in one pass): renders textures
  * [F, tsi, tsi, tsi, 3] into the atlas image [image_height, image_width, 3] of tile_width tiles per row
