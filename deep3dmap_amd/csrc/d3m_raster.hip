@@ -2548,6 +2548,22 @@ static bool fragments_ok(const d3m_fragments* fr, int attributes_batch, int num_
     return true;
 }
 
+// What a node with one lane per internal pixel refuses of a record's sizes, and its scratch sizes with it: B S S beyond 2^32.
+static bool pixel_lanes_ok(int B, int S) { return B > 0 && S > 0 && (unsigned long long)B * S * S <= (1ull << 32); }
+
+// What every gathering backward refuses after its node's own checks, before it asks for its scratch: a topology whose items
+// (Ft * 3) pass int32; no visibility blob in `fr`, the record whose list is walked, or one shorter than the nf entries of that
+// list need; an adjacency that is not a CSR of num_vertices rows with its items (`partials`: where the chunk sums of its long
+// rows go, csr_ok).  `vis`: the blob as the kernels read it.
+static bool gather_ok(const d3m_fragments* fr, long nf, int Ft, const d3m_csr* adjacency, int num_vertices,
+                      const void* partials, VisibilityView& vis) {
+    if ((long)Ft * 3 > 0x7FFFFFFFl) return false;                       // items are int32
+    if (!fr->visibility || fr->visibility_size < visibility_bytes(nf)) return false;
+    if (!csr_ok(adjacency, num_vertices, partials) || !adjacency->items) return false;
+    vis = visibility_view(const_cast<void*>(fr->visibility), nf);
+    return true;
+}
+
 D3M_EXPORT int d3m_vertex_attribute_images(const d3m_fragments* fragments, const float* attributes, int attributes_batch,
                                            int num_vertices, int num_channels, const float* background, float* images,
                                            float* alpha, d3m_stream_t stream) {
@@ -2589,28 +2605,34 @@ static int face_sums_gather(const AttrMaps& m, const VisibilityView& vis, const 
     return check_launch();
 }
 
+// face_sums_gather with the attribute node's stage 1 (d3m_attributes.h): the two face-sum kernels over the channel chunks of
+// an image gradient g [B,C,s,s] of the record `m` -- the attribute images' own, and the per-pixel gradient images of the SH
+// nodes, which are read as attribute images at the raster size.
+static int attribute_face_sums_gather(const AttrMaps& m, const VisibilityView& vis, const d3m_csr& adjacency, float* scratch,
+                                      const float* g, int num_vertices, int C, bool shared, float* grad, hipStream_t st) {
+    const unsigned c_chunks = (C + VA_CHUNK - 1) / VA_CHUNK;
+    return face_sums_gather(
+        m, vis, adjacency, scratch, num_vertices, C, shared, grad, st,
+        [&](unsigned small_blocks, unsigned large_blocks, hipStream_t s2) {
+            LAUNCH("k_vertex_attribute_face_sums", k_vertex_attribute_face_sums, dim3(small_blocks, c_chunks), dim3(256), s2, m,
+                   g, C, (const int*)vis.list, (const int*)vis.count, scratch);
+            LAUNCH("k_vertex_attribute_large_face_sums", k_vertex_attribute_large_face_sums, dim3(large_blocks, c_chunks),
+                   dim3(RG_BLOCK), s2, m, g, C, (const int*)vis.list, (const int*)vis.count, scratch);
+        });
+}
+
 D3M_EXPORT int d3m_vertex_attribute_images_backward(const d3m_fragments* fragments, const float* grad_images,
                                                     const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
                                                     float* grad_attributes, int attributes_batch, int num_vertices,
                                                     int num_channels, d3m_stream_t stream) {
     AttrMaps m;
+    VisibilityView vis;
     if (!grad_images || !scratch || !grad_attributes) return D3M_ERR_INVALID;
     if (!fragments_ok(fragments, attributes_batch, num_vertices, num_channels, m)) return D3M_ERR_INVALID;
-    if ((long)m.Ft * 3 > 0x7FFFFFFFl) return D3M_ERR_INVALID;          // items are int32
-    const long nf = (long)m.B * m.Fp;
-    if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
-    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if (!gather_ok(fragments, (long)m.B * m.Fp, m.Ft, adjacency, num_vertices, scratch, vis)) return D3M_ERR_INVALID;
     if (scratch_floats < d3m_vertex_attribute_scratch_floats(m.B, m.Fp, num_channels, adjacency)) return D3M_ERR_WORKSPACE;
-    const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
-    const unsigned c_chunks = (num_channels + VA_CHUNK - 1) / VA_CHUNK;
-    return face_sums_gather(
-        m, vis, *adjacency, scratch, num_vertices, num_channels, attributes_batch == 1, grad_attributes, (hipStream_t)stream,
-        [&](unsigned small_blocks, unsigned large_blocks, hipStream_t st) {
-            LAUNCH("k_vertex_attribute_face_sums", k_vertex_attribute_face_sums, dim3(small_blocks, c_chunks), dim3(256), st, m,
-                   grad_images, num_channels, (const int*)vis.list, (const int*)vis.count, scratch);
-            LAUNCH("k_vertex_attribute_large_face_sums", k_vertex_attribute_large_face_sums, dim3(large_blocks, c_chunks),
-                   dim3(RG_BLOCK), st, m, grad_images, num_channels, (const int*)vis.list, (const int*)vis.count, scratch);
-        });
+    return attribute_face_sums_gather(m, vis, *adjacency, scratch, grad_images, num_vertices, num_channels,
+                                      attributes_batch == 1, grad_attributes, (hipStream_t)stream);
 }
 
 // Per-pixel uv texture images (d3m_uv_texture.h): a texture image looked up at every pixel's interpolated uv, and the
@@ -2656,32 +2678,38 @@ D3M_EXPORT size_t d3m_uv_texture_images_scratch_bytes(int image_batch, int image
     if (!uv_texture_sizes_ok(image_batch, image_height, image_width, num_channels)) return 0;
     if (batch_size < 1 || batch_size > 65535 || raster_size < 1 || raster_size > 32768) return 0;
     if (image_batch != 1 && image_batch != batch_size) return 0;
-    if ((unsigned long long)batch_size * raster_size * raster_size > (1ull << 32)) return 0;
+    if (!pixel_lanes_ok(batch_size, raster_size)) return 0;
     return (size_t)image_batch * image_height * image_width * num_channels * sizeof(long long) +
            (size_t)UVT_MAX_BLOCKS * sizeof(unsigned);
 }
 
-// The front of both image adjoints (d3m_uv_texture.h): the fraction bits, the scratch's carve-up -- n_acc accumulators, then the
-// block maxima -- and the launch that clears the accumulators and leaves the block maxima of |scale * g|.
+// The fixed-point adjoint around a node's own scatter (d3m_uv_texture.h).  The scratch's carve-up: n_acc int64 accumulators,
+// then the block maxima.  uv_adjoint_clear_max launches the kernel that clears the accumulators and leaves the block maxima of
+// |scale * g| over the n_g elements of the gradient g (scale: 0.25 where g is pooled 2x2, else 1); frac: the fraction bits a
+// term keeps, 62 - ceil_log2 of the most terms an accumulator can receive.  uv_adjoint_convert launches the plain conversion
+// of the n_acc accumulators into grad.
 struct UvAdjoint {
     unsigned long long* acc;
     unsigned* block_max;
-    long n_px;
     int n_max, frac;
 };
 
-static UvAdjoint uv_adjoint_clear_max(const AttrMaps& m, long image_size, int num_channels, const float* grad_images,
-                                      void* scratch, long n_acc, hipStream_t st) {
+static UvAdjoint uv_adjoint_clear_max(const float* g, long n_g, float scale, int frac, void* scratch, long n_acc,
+                                      hipStream_t st) {
     UvAdjoint a;
-    const long n_g = (long)m.B * num_channels * image_size * image_size;
-    a.n_px = (long)m.B * m.S * m.S;
-    a.frac = 62 - ceil_log2((unsigned long long)a.n_px);
+    a.frac = frac;
     a.acc = (unsigned long long*)scratch;
     a.block_max = (unsigned*)(a.acc + n_acc);
     a.n_max = (int)std::min(blocks_for(std::max(n_acc, n_g), 256), (unsigned)UVT_MAX_BLOCKS);
-    LAUNCH("k_uv_texture_images_clear_max", k_uv_texture_images_clear_max, dim3(a.n_max), dim3(256), st, grad_images, n_g,
-           m.aa ? 0.25f : 1.0f, a.acc, n_acc, a.block_max);
+    LAUNCH("k_uv_texture_images_clear_max", k_uv_texture_images_clear_max, dim3(a.n_max), dim3(256), st, g, n_g, scale, a.acc,
+           n_acc, a.block_max);
     return a;
+}
+
+static void uv_adjoint_convert(const UvAdjoint& a, long n_acc, float* grad, hipStream_t st) {
+    LAUNCH("k_uv_texture_images_convert", k_uv_texture_images_convert,
+           dim3(std::min(blocks_for(n_acc, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)a.acc, n_acc,
+           (const unsigned*)a.block_max, a.n_max, a.frac, grad);
 }
 
 D3M_EXPORT int d3m_uv_texture_images_backward(const d3m_fragments* fragments, const float* faces_uv, const float* grad_images,
@@ -2698,14 +2726,14 @@ D3M_EXPORT int d3m_uv_texture_images_backward(const d3m_fragments* fragments, co
     if (need == 0) return D3M_ERR_INVALID;                              // (B S^2 beyond 2^32)
     if (scratch_bytes < need) return D3M_ERR_WORKSPACE;
     const long n_acc = (long)image_batch * image_height * image_width * num_channels;
+    const long n_g = (long)m.B * num_channels * fragments->image_size * fragments->image_size, n_px = (long)m.B * m.S * m.S;
     hipStream_t st = (hipStream_t)stream;
-    const UvAdjoint a = uv_adjoint_clear_max(m, fragments->image_size, num_channels, grad_images, scratch, n_acc, st);
+    const UvAdjoint a = uv_adjoint_clear_max(grad_images, n_g, m.aa ? 0.25f : 1.0f, 62 - ceil_log2((unsigned long long)n_px),
+                                             scratch, n_acc, st);
     LAUNCH("k_uv_texture_images_scatter", k_uv_texture_images_scatter,
-           dim3(std::min(blocks_for(a.n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, m, tx, grad_images,
+           dim3(std::min(blocks_for(n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, m, tx, grad_images,
            (const unsigned*)a.block_max, a.n_max, a.frac, a.acc);
-    LAUNCH("k_uv_texture_images_convert", k_uv_texture_images_convert,
-           dim3(std::min(blocks_for(n_acc, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)a.acc, n_acc,
-           (const unsigned*)a.block_max, a.n_max, a.frac, grad_image);
+    uv_adjoint_convert(a, n_acc, grad_image, st);
     return check_launch();
 }
 
@@ -2795,13 +2823,18 @@ D3M_EXPORT int d3m_uv_texture_mip_images_backward(const d3m_fragments* fragments
     if (!uv_mip_ok(image_height, image_width, levels, lod_bias, mp)) return D3M_ERR_INVALID;
     const size_t need = d3m_uv_texture_mip_images_scratch_bytes(image_batch, image_height, image_width, num_channels, levels,
                                                                 m.B, m.S);
-    if (need == 0 || scratch_bytes < need) return D3M_ERR_INVALID;      // (B S^2 beyond 2^32; a scratch that is too small)
+    // (B S^2 beyond 2^32, or a scratch that is too small: D3M_ERR_INVALID for both here, where the siblings answer the second
+    // with D3M_ERR_WORKSPACE; kept as the ABI has answered so far)
+    if (need == 0 || scratch_bytes < need) return D3M_ERR_INVALID;
     const long n_acc = (long)image_batch * mp.T * num_channels;
     const long n_out = (long)image_batch * image_height * image_width * num_channels;
+    const long n_g = (long)m.B * num_channels * fragments->image_size * fragments->image_size, n_px = (long)m.B * m.S * m.S;
     hipStream_t st = (hipStream_t)stream;
-    const UvAdjoint a = uv_adjoint_clear_max(m, fragments->image_size, num_channels, grad_images, scratch, n_acc, st);
+    const UvAdjoint a = uv_adjoint_clear_max(grad_images, n_g, m.aa ? 0.25f : 1.0f, 62 - ceil_log2((unsigned long long)n_px),
+                                             scratch, n_acc, st);
+    // (the mip node's own conversion gathers the levels back down the pyramid: no uv_adjoint_convert)
     LAUNCH("k_uv_texture_mip_images_scatter", k_uv_texture_mip_images_scatter,
-           dim3(std::min(blocks_for(a.n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, m, tx, mp, grad_images,
+           dim3(std::min(blocks_for(n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, m, tx, mp, grad_images,
            (const unsigned*)a.block_max, a.n_max, a.frac, a.acc);
     LAUNCH("k_uv_texture_mip_images_convert", k_uv_texture_mip_images_convert,
            dim3(std::min(blocks_for(n_out, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)a.acc, mp,
@@ -2812,8 +2845,7 @@ D3M_EXPORT int d3m_uv_texture_mip_images_backward(const d3m_fragments* fragments
 // The interior geometry gradient of everything drawn over a coverage record (d3m_fragment_geometry.h).
 // What the entry points refuse of the record; `m`: what the kernels read.  One lane per internal pixel: B S S within 2^32.
 static bool fragment_geometry_ok(const d3m_fragments* fr, int num_vertices, AttrMaps& m) {
-    if (!fragments_ok(fr, 1, num_vertices, 1, m)) return false;
-    return (unsigned long long)m.B * m.S * m.S <= (1ull << 32);
+    return fragments_ok(fr, 1, num_vertices, 1, m) && pixel_lanes_ok(m.B, m.S);
 }
 
 D3M_EXPORT int d3m_fragment_weights(const d3m_fragments* fragments, float* weights, d3m_stream_t stream) {
@@ -2827,8 +2859,7 @@ D3M_EXPORT int d3m_fragment_weights(const d3m_fragments* fragments, float* weigh
 
 D3M_EXPORT size_t d3m_fragment_geometry_scratch_floats(int batch_size, int num_faces, int raster_size,
                                                        const d3m_csr* adjacency, int with_pixel_grads) {
-    if (raster_size < 1 || raster_size > 32768 || (unsigned long long)std::max(batch_size, 0) * raster_size * raster_size > (1ull << 32))
-        return 0;
+    if (raster_size > 32768 || !pixel_lanes_ok(batch_size, raster_size)) return 0;
     const size_t sums = d3m_vertex_attribute_scratch_floats(batch_size, num_faces, 3, adjacency);
     if (sums == 0) return 0;
     return sums + (with_pixel_grads ? (size_t)batch_size * raster_size * raster_size * 3 : 0);
@@ -2840,7 +2871,7 @@ D3M_EXPORT int d3m_vertex_attribute_pixel_grads(const d3m_fragments* fragments, 
     AttrMaps m;
     if (!attributes || !grad_images || !pixel_grads) return D3M_ERR_INVALID;
     if (!fragments_ok(fragments, attributes_batch, num_vertices, num_channels, m)) return D3M_ERR_INVALID;
-    if ((unsigned long long)m.B * m.S * m.S > (1ull << 32)) return D3M_ERR_INVALID;
+    if (!pixel_lanes_ok(m.B, m.S)) return D3M_ERR_INVALID;
     const long n_px = (long)m.B * m.S * m.S;
     LAUNCH("k_vertex_attribute_pixel_grads", k_vertex_attribute_pixel_grads, dim3(blocks_for(n_px, 256)), dim3(256),
            (hipStream_t)stream, m, attributes, attributes_batch, num_vertices, num_channels, grad_images, pixel_grads);
@@ -2857,7 +2888,7 @@ D3M_EXPORT int d3m_uv_texture_pixel_grads(const d3m_fragments* fragments, const 
     if (misaligned4(image) || misaligned4(grad_images) || misaligned4(pixel_grads)) return D3M_ERR_INVALID;
     if (!uv_texture_ok(fragments, faces_uv, image_batch, image_height, image_width, num_channels, texture_wrapping, m, tx))
         return D3M_ERR_INVALID;
-    if ((unsigned long long)m.B * m.S * m.S > (1ull << 32)) return D3M_ERR_INVALID;
+    if (!pixel_lanes_ok(m.B, m.S)) return D3M_ERR_INVALID;
     const long n_px = (long)m.B * m.S * m.S;
     LAUNCH("k_uv_texture_pixel_grads", k_uv_texture_pixel_grads, dim3(blocks_for(n_px, 256)), dim3(256), (hipStream_t)stream, m,
            tx, image, grad_images, pixel_grads);
@@ -2868,15 +2899,12 @@ D3M_EXPORT int d3m_fragment_geometry_backward(const d3m_fragments* fragments, co
                                               const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
                                               float* grad_screen_vertices, int num_vertices, d3m_stream_t stream) {
     AttrMaps m;
+    VisibilityView vis;
     if (!pixel_grads || !scratch || !grad_screen_vertices) return D3M_ERR_INVALID;
     if (misaligned4(pixel_grads) || misaligned4(scratch) || misaligned4(grad_screen_vertices)) return D3M_ERR_INVALID;
     if (!fragment_geometry_ok(fragments, num_vertices, m)) return D3M_ERR_INVALID;
-    if ((long)m.Ft * 3 > 0x7FFFFFFFl) return D3M_ERR_INVALID;          // items are int32
-    const long nf = (long)m.B * m.Fp;
-    if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
-    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if (!gather_ok(fragments, (long)m.B * m.Fp, m.Ft, adjacency, num_vertices, scratch, vis)) return D3M_ERR_INVALID;
     if (scratch_floats < d3m_fragment_geometry_scratch_floats(m.B, m.Fp, m.S, adjacency, 0)) return D3M_ERR_WORKSPACE;
-    const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
     // Gv has G's layout with C = 3, and the result is per view
     return face_sums_gather(
         m, vis, *adjacency, scratch, num_vertices, 3, false, grad_screen_vertices, (hipStream_t)stream,
@@ -2895,7 +2923,7 @@ static bool sh_fragments_ok(const d3m_fragments* fr, const float* normals, int n
     if (!normals || !sh || misaligned4(normals) || misaligned4(sh) || misaligned4(colors)) return false;
     if (!fragments_ok(fr, normals_batch, num_vertices, 3, m)) return false;
     if ((sh_batch != 1 && sh_batch != m.B) || (colors_batch != 1 && colors_batch != m.B)) return false;
-    if ((unsigned long long)m.B * m.S * m.S > (1ull << 32)) return false;
+    if (!pixel_lanes_ok(m.B, m.S)) return false;
     in = ShfInputs{normals, colors, sh, normals_batch, colors ? colors_batch : 1, sh_batch, num_vertices};
     return true;
 }
@@ -2916,8 +2944,7 @@ D3M_EXPORT int d3m_sh_fragment_images(const d3m_fragments* fragments, const floa
 
 D3M_EXPORT size_t d3m_sh_fragment_scratch_floats(int batch_size, int num_faces, int raster_size, int with_colors,
                                                  const d3m_csr* adjacency) {
-    if (raster_size < 1 || raster_size > 32768 || (unsigned long long)std::max(batch_size, 0) * raster_size * raster_size > (1ull << 32))
-        return 0;
+    if (raster_size > 32768 || !pixel_lanes_ok(batch_size, raster_size)) return 0;
     const int C = with_colors ? 6 : 3;
     const size_t sums = d3m_vertex_attribute_scratch_floats(batch_size, num_faces, C, adjacency);
     if (sums == 0) return 0;
@@ -2932,6 +2959,7 @@ D3M_EXPORT int d3m_sh_fragment_images_backward(const d3m_fragments* fragments, c
                                                float* grad_sh, float* pixel_grads, d3m_stream_t stream) {
     AttrMaps m;
     ShfInputs in;
+    VisibilityView vis;
     if (!grad_images || !scratch || (!grad_vertex && !grad_sh && !pixel_grads)) return D3M_ERR_INVALID;
     if (vertex_grads < 0 || vertex_grads > 3 || (vertex_grads != 0) != (grad_vertex != nullptr)) return D3M_ERR_INVALID;
     if ((vertex_grads & 2) && !colors) return D3M_ERR_INVALID;
@@ -2940,10 +2968,7 @@ D3M_EXPORT int d3m_sh_fragment_images_backward(const d3m_fragments* fragments, c
         return D3M_ERR_INVALID;
     if (!sh_fragments_ok(fragments, normals, normals_batch, sh, sh_batch, colors, colors_batch, num_vertices, m, in))
         return D3M_ERR_INVALID;
-    if ((long)m.Ft * 3 > 0x7FFFFFFFl) return D3M_ERR_INVALID;          // items are int32
-    const long nf = (long)m.B * m.Fp;
-    if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
-    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if (!gather_ok(fragments, (long)m.B * m.Fp, m.Ft, adjacency, num_vertices, scratch, vis)) return D3M_ERR_INVALID;
     if (scratch_floats < d3m_sh_fragment_scratch_floats(m.B, m.Fp, m.S, colors != nullptr, adjacency)) return D3M_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const size_t S2 = (size_t)m.S * m.S;
@@ -2965,17 +2990,8 @@ D3M_EXPORT int d3m_sh_fragment_images_backward(const d3m_fragments* fragments, c
     // Q is the image gradient of the record re-labelled image_size = S, anti_aliasing = 0 over the same maps
     AttrMaps mq = m;
     mq.aa = 0;
-    const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
     auto gather = [&](const float* g, int channels, bool shared, float* grad) {
-        const unsigned c_chunks = (channels + VA_CHUNK - 1) / VA_CHUNK;
-        return face_sums_gather(
-            mq, vis, *adjacency, scratch, num_vertices, channels, shared, grad, st,
-            [&](unsigned small_blocks, unsigned large_blocks, hipStream_t s2) {
-                LAUNCH("k_vertex_attribute_face_sums", k_vertex_attribute_face_sums, dim3(small_blocks, c_chunks), dim3(256), s2,
-                       mq, g, channels, (const int*)vis.list, (const int*)vis.count, scratch);
-                LAUNCH("k_vertex_attribute_large_face_sums", k_vertex_attribute_large_face_sums, dim3(large_blocks, c_chunks),
-                       dim3(RG_BLOCK), s2, mq, g, channels, (const int*)vis.list, (const int*)vis.count, scratch);
-            });
+        return attribute_face_sums_gather(mq, vis, *adjacency, scratch, g, num_vertices, channels, shared, grad, st);
     };
     if (one_gather) return gather(Q, 6, normals_batch == 1, grad_vertex);
     int rc = D3M_OK;
@@ -3053,6 +3069,7 @@ D3M_EXPORT int d3m_sh_uv_fragment_images_backward(const d3m_fragments* fragments
     AttrMaps m;
     ShfInputs in;
     UvTexture tx;
+    VisibilityView vis;
     if (!grad_images || !scratch || (!grad_normals && !grad_sh && !grad_image && !pixel_grads)) return D3M_ERR_INVALID;
     if (misaligned4(grad_images) || ((uintptr_t)scratch & 7) || misaligned4(grad_normals) || misaligned4(grad_sh) ||
         misaligned4(grad_image) || misaligned4(pixel_grads))
@@ -3060,10 +3077,7 @@ D3M_EXPORT int d3m_sh_uv_fragment_images_backward(const d3m_fragments* fragments
     if (!sh_uv_fragments_ok(fragments, normals, normals_batch, sh, sh_batch, num_vertices, faces_uv, image, image_batch,
                             image_height, image_width, texture_wrapping, m, in, tx))
         return D3M_ERR_INVALID;
-    if ((long)m.Ft * 3 > 0x7FFFFFFFl) return D3M_ERR_INVALID;          // items are int32
-    const long nf = (long)m.B * m.Fp;
-    if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
-    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if (!gather_ok(fragments, (long)m.B * m.Fp, m.Ft, adjacency, num_vertices, scratch, vis)) return D3M_ERR_INVALID;
     const size_t need = d3m_sh_uv_fragment_scratch_bytes(m.B, m.Fp, m.S, image_batch, image_height, image_width, adjacency);
     if (need == 0) return D3M_ERR_INVALID;
     if (scratch_bytes < need) return D3M_ERR_WORKSPACE;
@@ -3084,25 +3098,16 @@ D3M_EXPORT int d3m_sh_uv_fragment_images_backward(const d3m_fragments* fragments
     AttrMaps mq = m;
     mq.aa = 0;
     if (grad_image) {
-        const long n_acc = (long)image_batch * image_height * image_width * 3;
-        const UvAdjoint a = uv_adjoint_clear_max(mq, m.S, 3, Qa, scratch, n_acc, st);
+        const long n_acc = (long)image_batch * image_height * image_width * 3, n_px = (long)m.B * S2;
+        const UvAdjoint a = uv_adjoint_clear_max(Qa, n_px * 3, 1.0f, 62 - ceil_log2((unsigned long long)n_px), scratch, n_acc, st);
         LAUNCH("k_uv_texture_images_scatter", k_uv_texture_images_scatter,
-               dim3(std::min(blocks_for(a.n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, mq, tx, (const float*)Qa,
+               dim3(std::min(blocks_for(n_px, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, mq, tx, (const float*)Qa,
                (const unsigned*)a.block_max, a.n_max, a.frac, a.acc);
-        LAUNCH("k_uv_texture_images_convert", k_uv_texture_images_convert,
-               dim3(std::min(blocks_for(n_acc, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)a.acc, n_acc,
-               (const unsigned*)a.block_max, a.n_max, a.frac, grad_image);
+        uv_adjoint_convert(a, n_acc, grad_image, st);
     }
     if (!grad_normals) return check_launch();
-    const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
-    return face_sums_gather(
-        mq, vis, *adjacency, gather_scratch, num_vertices, 3, normals_batch == 1, grad_normals, st,
-        [&](unsigned small_blocks, unsigned large_blocks, hipStream_t s2) {
-            LAUNCH("k_vertex_attribute_face_sums", k_vertex_attribute_face_sums, dim3(small_blocks, 1), dim3(256), s2, mq,
-                   (const float*)Qn, 3, (const int*)vis.list, (const int*)vis.count, gather_scratch);
-            LAUNCH("k_vertex_attribute_large_face_sums", k_vertex_attribute_large_face_sums, dim3(large_blocks, 1),
-                   dim3(RG_BLOCK), s2, mq, (const float*)Qn, 3, (const int*)vis.list, (const int*)vis.count, gather_scratch);
-        });
+    return attribute_face_sums_gather(mq, vis, *adjacency, gather_scratch, Qn, num_vertices, 3, normals_batch == 1,
+                                      grad_normals, st);
 }
 
 D3M_EXPORT int d3m_sh_uv_fragment_pixel_grads(const d3m_fragments* fragments, const float* normals, int normals_batch,
@@ -3128,8 +3133,7 @@ D3M_EXPORT int d3m_sh_uv_fragment_pixel_grads(const d3m_fragments* fragments, co
 static bool antialias_ok(const d3m_fragments* fr, const float* screen_vertices, int num_vertices, const int32_t* side_opposite,
                          int num_channels, AttrMaps& m, AaScene& sc) {
     if (!screen_vertices || !side_opposite || misaligned4(screen_vertices) || misaligned4(side_opposite)) return false;
-    if (!fragments_ok(fr, 1, num_vertices, num_channels, m) || m.aa) return false;
-    if ((unsigned long long)m.B * m.S * m.S > (1ull << 32)) return false;
+    if (!fragments_ok(fr, 1, num_vertices, num_channels, m) || m.aa || !pixel_lanes_ok(m.B, m.S)) return false;
     sc = AaScene{screen_vertices, side_opposite, num_vertices};
     return true;
 }
@@ -3174,15 +3178,12 @@ D3M_EXPORT int d3m_antialias_geometry_backward(const d3m_fragments* fragments, c
                                                const d3m_csr* adjacency, float* scratch, size_t scratch_floats,
                                                float* grad_screen_vertices, int num_vertices, d3m_stream_t stream) {
     AttrMaps m;
+    VisibilityView vis;
     if (!pair_grads || !scratch || !grad_screen_vertices) return D3M_ERR_INVALID;
     if (misaligned4(pair_grads) || misaligned4(scratch) || misaligned4(grad_screen_vertices)) return D3M_ERR_INVALID;
     if (!fragment_geometry_ok(fragments, num_vertices, m) || m.aa) return D3M_ERR_INVALID;
-    if ((long)m.Ft * 3 > 0x7FFFFFFFl) return D3M_ERR_INVALID;          // items are int32
-    const long nf = (long)m.B * m.Fp;
-    if (!fragments->visibility || fragments->visibility_size < visibility_bytes(nf)) return D3M_ERR_INVALID;
-    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if (!gather_ok(fragments, (long)m.B * m.Fp, m.Ft, adjacency, num_vertices, scratch, vis)) return D3M_ERR_INVALID;
     if (scratch_floats < d3m_antialias_scratch_floats(m.B, m.Fp, m.S, adjacency, 0)) return D3M_ERR_WORKSPACE;
-    const VisibilityView vis = visibility_view(const_cast<void*>(fragments->visibility), nf);
     // Gv has G's layout with C = 3, and the result is per view: stage 2 is d3m_fragment_geometry_backward's
     return face_sums_gather(
         m, vis, *adjacency, scratch, num_vertices, 3, false, grad_screen_vertices, (hipStream_t)stream,
@@ -3249,19 +3250,13 @@ D3M_EXPORT int d3m_uv_bake_images_backward(const d3m_fragments* layout, const d3
     if (scratch_bytes < need) return D3M_ERR_WORKSPACE;
     const long T2 = (long)uv.S * uv.S;
     const long n_acc = (long)vw.B * num_channels * image_height * image_width, n_g = (long)vw.B * T2 * num_channels;
-    const int frac = 62 - ceil_log2((unsigned long long)T2);          // a view's image receives from its own T^2 texels only
-    unsigned long long* acc = (unsigned long long*)scratch;
-    unsigned* block_max = (unsigned*)(acc + n_acc);
-    const int n_max = (int)std::min(blocks_for(std::max(n_acc, n_g), 256), (unsigned)UVT_MAX_BLOCKS);
     hipStream_t st = (hipStream_t)stream;
-    LAUNCH("k_uv_texture_images_clear_max", k_uv_texture_images_clear_max, dim3(n_max), dim3(256), st, grad_texture, n_g, 1.0f, acc,
-           n_acc, block_max);
+    // a view's image receives from its own T^2 texels only
+    const UvAdjoint a = uv_adjoint_clear_max(grad_texture, n_g, 1.0f, 62 - ceil_log2((unsigned long long)T2), scratch, n_acc, st);
     LAUNCH("k_uv_bake_images_scatter", k_uv_bake_images_scatter,
            dim3(std::min(blocks_for(T2, 256), (unsigned)UVT_SCATTER_BLOCKS), vw.B), dim3(256), st, uv, vm, bk, grad_texture,
-           (const unsigned*)block_max, n_max, frac, acc);
-    LAUNCH("k_uv_texture_images_convert", k_uv_texture_images_convert,
-           dim3(std::min(blocks_for(n_acc, 256), (unsigned)UVT_SCATTER_BLOCKS)), dim3(256), st, (const long long*)acc, n_acc,
-           (const unsigned*)block_max, n_max, frac, grad_images);
+           (const unsigned*)a.block_max, a.n_max, a.frac, a.acc);
+    uv_adjoint_convert(a, n_acc, grad_images, st);
     return check_launch();
 }
 
@@ -3280,18 +3275,18 @@ D3M_EXPORT int d3m_uv_bake_vertices_backward(const d3m_fragments* layout, const 
     AttrMaps uv, vw;
     UbView vm;
     UvBake bk;
+    VisibilityView layout_vis;
     if (!images || !grad_texture || !scratch || !grad_screen_vertices) return D3M_ERR_INVALID;
     if (misaligned4(images) || misaligned4(grad_texture) || misaligned4(scratch) || misaligned4(grad_screen_vertices))
         return D3M_ERR_INVALID;
     if (!uv_bake_ok(layout, view, num_channels, image_height, image_width, screen_vertices, num_vertices, perspective,
                     depth_tolerance, uv, vw, vm, bk))
         return D3M_ERR_INVALID;
-    if ((long)uv.Ft * 3 > 0x7FFFFFFFl || (long)vw.B * uv.Fp > 0x7FFFFFFFl) return D3M_ERR_INVALID;
-    if (!layout->visibility || layout->visibility_size < visibility_bytes(uv.Fp)) return D3M_ERR_INVALID;
-    if (!csr_ok(adjacency, num_vertices, scratch) || !adjacency->items) return D3M_ERR_INVALID;
+    if ((long)vw.B * uv.Fp > 0x7FFFFFFFl) return D3M_ERR_INVALID;     // (the gather's own bound: B views of the layout's F')
+    // the layout's list is walked, once per view
+    if (!gather_ok(layout, uv.Fp, uv.Ft, adjacency, num_vertices, scratch, layout_vis)) return D3M_ERR_INVALID;
     if (scratch_floats < d3m_uv_bake_scratch_floats(vw.B, uv.Fp, adjacency)) return D3M_ERR_WORKSPACE;
     bk.images = images;
-    const VisibilityView layout_vis = visibility_view(const_cast<void*>(layout->visibility), uv.Fp);
     int* view_flags = (int*)(scratch + d3m_vertex_attribute_scratch_floats(vw.B, uv.Fp, 3, adjacency));
     VisibilityView vis = layout_vis;
     vis.flags = view_flags;

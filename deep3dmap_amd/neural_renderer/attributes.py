@@ -177,6 +177,13 @@ def _attribute_images_adjoint(fr, A, g, batched, sizes):
 MAX_PIXEL_TERMS = 1 << 32  # B S S: one lane per internal pixel
 
 
+def _checked_pixel_lanes(fragments, who):
+    """What every node with one lane per internal pixel refuses: a record with B S S beyond 2^32."""
+    n = fragments.face_index_map.shape[0] * fragments.raster_size ** 2
+    if n > MAX_PIXEL_TERMS:
+        raise ValueError(f"{who}: B S S = {n} is beyond 2^32")
+
+
 def _checked_screen_vertices(screen_vertices, fragments, who):
     """The screen vertices a node differentiates in: [B,V,3] f32 on the record's device, V the record's.  That they are the
     vertices the record was rasterised from cannot be checked: the caller's business."""
@@ -192,8 +199,7 @@ def _checked_screen_vertices(screen_vertices, fragments, who):
                          f"from {fragments.num_vertices}")
     if screen_vertices.device != fragments.face_index_map.device:
         raise ValueError(f"{who}: screen_vertices must be on the fragments' device")
-    if B * fragments.raster_size ** 2 > MAX_PIXEL_TERMS:
-        raise ValueError(f"{who}: B S S = {B * fragments.raster_size ** 2} is beyond 2^32")
+    _checked_pixel_lanes(fragments, who)
 
 
 def _geometry_scratch(fr, A, with_pixel_grads):

@@ -28,8 +28,8 @@ import ctypes
 import torch
 
 from .. import _lib
-from .attributes import (_checked_background, _checked_fragments, _checked_screen_vertices, _geometry_adjoint,
-                         _geometry_scratch, _node_geometry_adjoint)
+from .attributes import (_checked_background, _checked_fragments, _checked_pixel_lanes, _checked_screen_vertices,
+                         _geometry_adjoint, _geometry_scratch, _node_geometry_adjoint)
 from .row_gather import vertex_adjacency
 
 
@@ -115,6 +115,18 @@ def _checked_per_vertex(t, name, B, V, device):
         raise ValueError(f"{name} must be on the fragments' device")
 
 
+def _checked_sh(sh, B, device):
+    """The 9-term light of the per-pixel shading nodes: f32 [3,9] or [B,3,9] on the record's device."""
+    if not torch.is_tensor(sh) or sh.dim() not in (2, 3) or tuple(sh.shape[-2:]) != (3, 9):
+        raise ValueError("sh must be [3, 9] or [B, 3, 9]")
+    if sh.dtype != torch.float32:
+        raise ValueError("sh must be float32")
+    if sh.dim() == 3 and sh.shape[0] != B:
+        raise ValueError(f"sh must be [3, 9] or [{B}, 3, 9] for fragments of {B} views")
+    if sh.device != device:
+        raise ValueError("sh must be on the fragments' device")
+
+
 def shade_fragments(normals, sh, fragments, colors=None, background=None, cache=None, screen_vertices=None):
     """(images [B,3,s,s], alpha [B,s,s]): per-vertex `normals` f32 [V,3] (shared by the views) or [B,V,3] -- one per vertex
     of the record's topology, any length, in whatever frame the light lives in -- interpolated over the Fragments record,
@@ -136,20 +148,12 @@ def shade_fragments(normals, sh, fragments, colors=None, background=None, cache=
     B, Ft, Fp = _checked_fragments(fragments)
     V, device = fragments.num_vertices, fragments.face_index_map.device
     _checked_per_vertex(normals, "normals", B, V, device)
-    if not torch.is_tensor(sh) or sh.dim() not in (2, 3) or tuple(sh.shape[-2:]) != (3, 9):
-        raise ValueError("sh must be [3, 9] or [B, 3, 9]")
-    if sh.dtype != torch.float32:
-        raise ValueError("sh must be float32")
-    if sh.dim() == 3 and sh.shape[0] != B:
-        raise ValueError(f"sh must be [3, 9] or [{B}, 3, 9] for fragments of {B} views")
-    if sh.device != device:
-        raise ValueError("sh must be on the fragments' device")
+    _checked_sh(sh, B, device)
     if colors is not None:
         _checked_per_vertex(colors, "colors", B, V, device)
     if screen_vertices is not None:
         _checked_screen_vertices(screen_vertices, fragments, "shade_fragments")
-    if B * fragments.raster_size ** 2 > 1 << 32:
-        raise ValueError(f"shade_fragments: B S S = {B * fragments.raster_size ** 2} is beyond 2^32")
+    _checked_pixel_lanes(fragments, "shade_fragments")
     background = _checked_background(background, 3, normals)
     adjacency = vertex_adjacency(fragments.tri, V, cache)          # (where tri's indices are checked against V)
     if not normals.is_cuda:

@@ -31,12 +31,11 @@ import ctypes
 import torch
 
 from .. import _lib
-from .attributes import (_checked_background, _checked_fragments, _checked_screen_vertices, _geometry_adjoint,
-                         _geometry_scratch, _node_geometry_adjoint)
+from .attributes import (_checked_background, _checked_screen_vertices, _geometry_adjoint, _geometry_scratch,
+                         _node_geometry_adjoint)
 from .row_gather import vertex_adjacency
-from .sh_fragments import _batch_of, _checked_per_vertex
-from .uv_texture_images import CLAMP_TO_BORDER, MAX_IMAGE_SIZE, uv_adjoint_fraction_bits
-from .uv_textures import _wrapping_code
+from .sh_fragments import _batch_of, _checked_per_vertex, _checked_sh
+from .uv_texture_images import _checked_uv_image
 
 
 class _ShadeUvTexture(torch.autograd.Function):
@@ -120,42 +119,10 @@ def shade_uv_texture(image, faces_uv, normals, sh, fragments, texture_wrapping='
     per-vertex colors together with an image.  faces_uv that requires grad raises NotImplementedError.  ValueError /
     TypeError, before the device is touched, for a wrong rank, dtype, device, a channel count other than 3, F, V, batch,
     wrapping, a background that requires grad, B S S beyond 2^32, H or W beyond 32768."""
-    if not torch.is_tensor(image) or not torch.is_tensor(faces_uv):
-        raise TypeError("image and faces_uv must be tensors")
-    if image.dtype != torch.float32 or faces_uv.dtype != torch.float32:
-        raise TypeError("image and faces_uv must be float32")
-    if image.dim() not in (3, 4) or image.shape[-3] < 1 or image.shape[-2] < 1:
-        raise ValueError("image must be [H, W, 3] or [B, H, W, 3]")
-    H, W, C = image.shape[-3:]
-    if C != 3:
-        raise ValueError(f"image: an albedo has 3 channels, not {C}")
-    if H > MAX_IMAGE_SIZE or W > MAX_IMAGE_SIZE:
-        raise ValueError(f"image: at most {MAX_IMAGE_SIZE} rows and columns")
-    wrapping = _wrapping_code(texture_wrapping)
-    if wrapping == CLAMP_TO_BORDER:
-        raise ValueError("shade_uv_texture: CLAMP_TO_BORDER is not offered (REPEAT, MIRRORED_REPEAT or CLAMP_TO_EDGE)")
-    B, Ft, Fp = _checked_fragments(fragments)
+    B, Ft, H, W, C, wrapping = _checked_uv_image(image, faces_uv, texture_wrapping, fragments, "shade_uv_texture", channels=3)
     V, device = fragments.num_vertices, fragments.face_index_map.device
-    if faces_uv.dim() != 3 or tuple(faces_uv.shape) != (Ft, 3, 2):
-        raise ValueError(f"faces_uv must be [{Ft}, 3, 2] for fragments of {Ft} faces")
-    if image.dim() == 4 and image.shape[0] != B:
-        raise ValueError(f"image must be [H, W, 3] or [{B}, H, W, 3] for fragments of {B} views")
-    if B * fragments.raster_size ** 2 > 1 << 32:
-        raise ValueError(f"shade_uv_texture: B S S = {B * fragments.raster_size ** 2} is beyond 2^32")
-    uv_adjoint_fraction_bits(B, fragments.raster_size)
-    if faces_uv.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("shade_uv_texture: no gradient with respect to faces_uv (it is a constant; detach it)")
-    if image.device != device or faces_uv.device != device:
-        raise ValueError("image and faces_uv must be on the fragments' device")
     _checked_per_vertex(normals, "normals", B, V, device)
-    if not torch.is_tensor(sh) or sh.dim() not in (2, 3) or tuple(sh.shape[-2:]) != (3, 9):
-        raise ValueError("sh must be [3, 9] or [B, 3, 9]")
-    if sh.dtype != torch.float32:
-        raise ValueError("sh must be float32")
-    if sh.dim() == 3 and sh.shape[0] != B:
-        raise ValueError(f"sh must be [3, 9] or [{B}, 3, 9] for fragments of {B} views")
-    if sh.device != device:
-        raise ValueError("sh must be on the fragments' device")
+    _checked_sh(sh, B, device)
     if screen_vertices is not None:
         _checked_screen_vertices(screen_vertices, fragments, "shade_uv_texture")
     background = _checked_background(background, 3, image)

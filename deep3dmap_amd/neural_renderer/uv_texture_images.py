@@ -26,7 +26,8 @@ import ctypes
 import torch
 
 from .. import _lib
-from .attributes import _checked_background, _checked_fragments, _checked_screen_vertices, _node_geometry_adjoint
+from .attributes import (_checked_background, _checked_fragments, _checked_pixel_lanes, _checked_screen_vertices,
+                         _node_geometry_adjoint)
 from .row_gather import vertex_adjacency
 from .uv_textures import _wrapping_code
 
@@ -46,6 +47,50 @@ def uv_adjoint_fraction_bits(B, S):
     if n > MAX_PIXEL_TERMS:
         raise ValueError(f"sample_uv_texture: B S S = {n} is beyond 2^32 (fewer than 30 fraction bits in the adjoint)")
     return 62 - (n - 1).bit_length()
+
+
+def _checked_faces_uv(faces_uv, texture_wrapping, fragments, who):
+    """(B, Ft, the wrapping's code) of a record and the faces_uv [Ft,3,2] that belong to its faces"""
+    wrapping = _wrapping_code(texture_wrapping)
+    if wrapping == CLAMP_TO_BORDER:
+        raise ValueError(f"{who}: CLAMP_TO_BORDER is not offered (REPEAT, MIRRORED_REPEAT or CLAMP_TO_EDGE)")
+    B, Ft, Fp = _checked_fragments(fragments)
+    if faces_uv.dim() != 3 or tuple(faces_uv.shape) != (Ft, 3, 2):
+        raise ValueError(f"faces_uv must be [{Ft}, 3, 2] for fragments of {Ft} faces")
+    return B, Ft, wrapping
+
+
+def _checked_uv_image(image, faces_uv, texture_wrapping, fragments, who, channels=None):
+    """(B, Ft, H, W, C, the wrapping's code) of what every node that looks a texture image up over a record takes: the image
+    [H,W,C] or [B,H,W,C] -- channels None: 1 <= C <= 64, else exactly `channels` --, faces_uv, the wrapping, the record with
+    B S S within 2^32, all on the record's device.  The errors, in the order the nodes document."""
+    if not torch.is_tensor(image) or not torch.is_tensor(faces_uv):
+        raise TypeError("image and faces_uv must be tensors")
+    if image.dtype != torch.float32 or faces_uv.dtype != torch.float32:
+        raise TypeError("image and faces_uv must be float32")
+    c = "C" if channels is None else channels
+    if image.dim() not in (3, 4) or image.shape[-3] < 1 or image.shape[-2] < 1:
+        raise ValueError(f"image must be [H, W, {c}] or [B, H, W, {c}]")
+    H, W, C = image.shape[-3:]
+    if channels is None and not 1 <= C <= MAX_CHANNELS:
+        raise ValueError(f"image: 1 to {MAX_CHANNELS} channels")
+    if channels is not None and C != channels:
+        raise ValueError(f"image: an albedo has {channels} channels, not {C}")
+    if H > MAX_IMAGE_SIZE or W > MAX_IMAGE_SIZE:
+        raise ValueError(f"image: at most {MAX_IMAGE_SIZE} rows and columns")
+    B, Ft, wrapping = _checked_faces_uv(faces_uv, texture_wrapping, fragments, who)
+    if image.dim() == 4 and image.shape[0] != B:
+        raise ValueError(f"image must be [H, W, {c}] or [{B}, H, W, {c}] for fragments of {B} views")
+    if channels is None:
+        uv_adjoint_fraction_bits(B, fragments.raster_size)            # (sample_uv_texture's own wording of the bound)
+    else:
+        _checked_pixel_lanes(fragments, who)
+    if faces_uv.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(f"{who}: no gradient with respect to faces_uv (it is a constant; detach it)")
+    dev = fragments.face_index_map.device
+    if image.device != dev or faces_uv.device != dev:
+        raise ValueError("image and faces_uv must be on the fragments' device")
+    return B, Ft, H, W, C, wrapping
 
 
 def _uv_outputs(fr, img):
@@ -228,31 +273,7 @@ def sample_uv_texture(image, faces_uv, fragments, texture_wrapping='REPEAT', bac
 
     ValueError / TypeError, before anything is launched, for a wrong rank, dtype, device, C, F, batch, wrapping, background,
     mipmap, lod_bias or screen_vertices, and for a record with B S S beyond 2^32."""
-    if not torch.is_tensor(image) or not torch.is_tensor(faces_uv):
-        raise TypeError("image and faces_uv must be tensors")
-    if image.dtype != torch.float32 or faces_uv.dtype != torch.float32:
-        raise TypeError("image and faces_uv must be float32")
-    if image.dim() not in (3, 4) or image.shape[-3] < 1 or image.shape[-2] < 1:
-        raise ValueError("image must be [H, W, C] or [B, H, W, C]")
-    H, W, C = image.shape[-3:]
-    if not 1 <= C <= MAX_CHANNELS:
-        raise ValueError(f"image: 1 to {MAX_CHANNELS} channels")
-    if H > MAX_IMAGE_SIZE or W > MAX_IMAGE_SIZE:
-        raise ValueError(f"image: at most {MAX_IMAGE_SIZE} rows and columns")
-    wrapping = _wrapping_code(texture_wrapping)
-    if wrapping == CLAMP_TO_BORDER:
-        raise ValueError("sample_uv_texture: CLAMP_TO_BORDER is not offered (REPEAT, MIRRORED_REPEAT or CLAMP_TO_EDGE)")
-    B, Ft, Fp = _checked_fragments(fragments)
-    if faces_uv.dim() != 3 or tuple(faces_uv.shape) != (Ft, 3, 2):
-        raise ValueError(f"faces_uv must be [{Ft}, 3, 2] for fragments of {Ft} faces")
-    if image.dim() == 4 and image.shape[0] != B:
-        raise ValueError(f"image must be [H, W, C] or [{B}, H, W, C] for fragments of {B} views")
-    uv_adjoint_fraction_bits(B, fragments.raster_size)
-    if faces_uv.requires_grad and torch.is_grad_enabled():
-        raise NotImplementedError("sample_uv_texture: no gradient with respect to faces_uv (it is a constant; detach it)")
-    dev = fragments.face_index_map.device
-    if image.device != dev or faces_uv.device != dev:
-        raise ValueError("image and faces_uv must be on the fragments' device")
+    B, Ft, H, W, C, wrapping = _checked_uv_image(image, faces_uv, texture_wrapping, fragments, "sample_uv_texture")
     levels = mip_levels(H, W, mipmap)
     lod_bias = _checked_lod_bias(lod_bias)
     adjacency = None
@@ -317,12 +338,7 @@ def uv_texture_lod(faces_uv, fragments, size, texture_wrapping='REPEAT', lod_bia
         raise ValueError("size must be (H, W)")
     if not (1 <= H <= MAX_IMAGE_SIZE and 1 <= W <= MAX_IMAGE_SIZE):
         raise ValueError(f"size: 1 to {MAX_IMAGE_SIZE} rows and columns")
-    wrapping = _wrapping_code(texture_wrapping)
-    if wrapping == CLAMP_TO_BORDER:
-        raise ValueError("uv_texture_lod: CLAMP_TO_BORDER is not offered (REPEAT, MIRRORED_REPEAT or CLAMP_TO_EDGE)")
-    B, Ft, Fp = _checked_fragments(fragments)
-    if faces_uv.dim() != 3 or tuple(faces_uv.shape) != (Ft, 3, 2):
-        raise ValueError(f"faces_uv must be [{Ft}, 3, 2] for fragments of {Ft} faces")
+    B, Ft, wrapping = _checked_faces_uv(faces_uv, texture_wrapping, fragments, "uv_texture_lod")
     L = mip_levels(H, W, True if levels is None else levels)
     if L < 1:
         raise ValueError(f"levels: 1 to {MAX_LEVEL}")
