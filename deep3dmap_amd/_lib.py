@@ -5,284 +5,27 @@ import os
 
 import torch
 
-from .build import LOAD_PATH as LIB_PATH
+from . import _abi
+from .build import LOAD_PATH as LIB_PATH, _headers
 
-_c_f32p = ctypes.c_void_p      # device pointers travel as integers
-_I, _F, _SZ, _L = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_long
-_P = ctypes.c_void_p
+_I, _F, _SZ, _P = ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_void_p
 
+# The header is the binding: the structs (D3MCamera, D3MCsr, D3MG2SBlock, ...: _abi.class_name), every entry point's
+# restype / argtypes and the constants are read from include/d3m_raster.h, once per process, here.  Only the host arrays
+# whose C type does not tell them from device pointers are named by hand.
+_HOST_ARRAYS = {("d3m_timing_collect", "counts"): ctypes.POINTER(_I), ("d3m_timing_collect", "total_ms"): ctypes.POINTER(_F),
+                ("d3m_pose_tree_constants", "out4"): ctypes.POINTER(_I)}
+HEADER = _headers()[-1]      # include/d3m_raster.h, where the build looks for it
+with open(HEADER) as _header:
+    _ABI = _abi.read_header(_header.read(), _HOST_ARRAYS)
+globals().update({cls.__name__: cls for cls in _ABI.structs.values()})
+_SIGNATURES = {name: (res, [t for _, t in params]) for name, (res, params) in _ABI.functions.items()}
 
-class D3MCamera(ctypes.Structure):
-    _fields_ = [("mode", _I), ("perspective", _I), ("tan_half_width", _F), ("orig_size", _F),
-                ("rot", _P), ("eye_or_t", _P), ("K", _P), ("dist", _P),
-                ("rot_batch", _I), ("eye_batch", _I), ("K_batch", _I), ("dist_batch", _I)]
-
-
-class D3MBasis(ctypes.Structure):
-    _fields_ = [("eye", _P), ("at_or_direction", _P), ("up", _P), ("eye_batch", _I), ("at_batch", _I), ("up_batch", _I),
-                ("is_look_at", _I)]
-
-
-class D3MCameraGrad(ctypes.Structure):
-    """d3m_camera_grad (include/d3m_raster.h): where d3m_camera_params_backward writes each parameter's gradient (NULL: skipped)."""
-    _fields_ = [("eye_or_t", _P), ("at_or_direction", _P), ("up", _P), ("rot", _P), ("K", _P), ("dist", _P)]
-
-
-class D3MVertexTarget(ctypes.Structure):
-    _fields_ = [("grad_vertices", _P), ("tri", _P), ("num_vertices", _I), ("num_tri", _I), ("tri_batch", _I),
-                ("fill_back", _I)]
-
-
-class D3MLight(ctypes.Structure):
-    """d3m_light (include/d3m_raster.h): the light's five parameters as device arrays of batch 1 or B."""
-    _fields_ = [("intensity_ambient", _P), ("intensity_directional", _P), ("color_ambient", _P), ("color_directional", _P),
-                ("direction", _P), ("ia_batch", _I), ("id_batch", _I), ("ca_batch", _I), ("cd_batch", _I), ("dir_batch", _I)]
-
-
-class D3MCsr(ctypes.Structure):
-    """d3m_csr (include/d3m_raster.h): a gathered CSR with its long-row tables (neural_renderer/row_gather.py builds it)."""
-    _fields_ = ([(n, _P) for n in ("offsets", "items", "chunks", "long_rows", "long_chunk_ptr")] +
-                [(n, _I) for n in ("num_rows", "num_chunks", "num_long_rows", "long_row")])
-
-
-class D3MFragments(ctypes.Structure):
-    """d3m_fragments (include/d3m_raster.h): a coverage record as the attribute-image entry points read it."""
-    _fields_ = ([(n, _P) for n in ("face_index_map", "weight_map", "depth_map", "faces", "tri", "visibility")] +
-                [("visibility_size", _SZ)] +
-                [(n, _I) for n in ("batch_size", "num_tri", "fill_back", "image_size", "anti_aliasing")])
-
-
-class D3MMeshTopology(ctypes.Structure):
-    """d3m_mesh_topology (include/d3m_raster.h): the neighbour CSR, the wing CSR and the wing records of a faces tensor."""
-    _fields_ = [("nbr", D3MCsr), ("wing", D3MCsr), ("wings", _P), ("num_edges", _I), ("num_wings", _I)]
-
-
-class D3MFitTargets(ctypes.Structure):
-    _fields_ = [("rgb_target", _P), ("depth_target", _P), ("alpha_target", _P), ("mask", _P), ("scratch", _P),
-                ("loss", _P), ("grad_rgb_map", _P), ("grad_alpha_map", _P), ("grad_depth_map", _P), ("grad_loss", _P),
-                ("mask_sum", _P), ("edge_grad", _P), ("edge_dot", _P), ("edge_nz_lo_inv", _P), ("edge_nz_hi1", _P), ("flags", _I),
-                ("tile_void", _P)]
-
-
-class D3MG2SBlock(ctypes.Structure):
-    """d3m_g2s_block (include/d3m_raster.h, section D), field for field."""
-    _fields_ = ([("batch_size", _I), ("height", _I), ("width", _I), ("image_size", _I), ("anti_aliasing", _I), ("flip", _I),
-                 ("inv_K", _P), ("inv_K_batch", _I), ("K", _P), ("K_batch", _I),
-                 ("rot_center_depth", _F), ("depth_min", _F), ("depth_max", _F), ("near", _F), ("far", _F),
-                 ("camera", ctypes.POINTER(D3MCamera)), ("view", _P), ("view_components", _I)] +
-                [(n, _P) for n in ("rot", "trans", "depth", "albedo", "light_a", "light_b", "light_d", "target", "extra_mask",
-                                   "normal", "diffuse_shading", "texture", "recon_depth", "recon_im", "recon_im_mask",
-                                   "losses")] +
-                [("lam_smooth", _F), ("with_smooth", _I)] +
-                [(n, _P) for n in ("screen_vertices", "zbuffer", "scratch",
-                                   "grad_recon_im", "grad_l1", "grad_l1_flip", "grad_smooth", "grad_total",
-                                   "grad_texture", "grad_tri", "grad_depth_map", "grad_normal", "grad_depth_mesh",
-                                   "grad_depth", "grad_albedo", "grad_light_a", "grad_light_b", "grad_light_d", "grad_rot",
-                                   "grad_trans", "grad_view")])
-
-
-CAMERA_NONE, CAMERA_LOOK_AT, CAMERA_LOOK, CAMERA_PROJECTION = 0, 1, 2, 3
-PRECLEARED = 1            # D3M_PRECLEARED: the caller has zeroed what the operator would clear (include/d3m_raster.h, "Clears")
-FIT_FINISH_DEFERRED = 2   # D3M_FIT_FINISH_DEFERRED: the fused objective's finish is left to d3m_backward_textures_lit
-FIT_POOLED = 4            # D3M_FIT_POOLED: records of an objective on the 2x2-pooled images (anti-aliasing)
-GRAD_OF_OUTPUT_IMAGE = 32   # D3M_GRAD_OF_OUTPUT_IMAGE (d3m_backward_depth_map_mesh)
+CAMERA_NONE, CAMERA_LOOK_AT, CAMERA_LOOK, CAMERA_PROJECTION = (
+    _ABI.constants["D3M_CAMERA_" + n] for n in ("NONE", "LOOK_AT", "LOOK", "PROJECTION"))
+PRECLEARED, FIT_FINISH_DEFERRED, FIT_POOLED, GRAD_OF_OUTPUT_IMAGE = (     # the flags: what each means is in the header
+    _ABI.constants["D3M_" + n] for n in ("PRECLEARED", "FIT_FINISH_DEFERRED", "FIT_POOLED", "GRAD_OF_OUTPUT_IMAGE"))
 FRONT_RANGES = 10         # clears d3m_lit_front takes
-
-_SIGNATURES = {
-    "d3m_version": (ctypes.c_char_p, []),
-    "d3m_last_hip_error": (_I, []),
-    "d3m_zero_ranges": (_I, [ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P]),
-    "d3m_error_string": (ctypes.c_char_p, [_I]),
-    "d3m_timing_enable": (None, [_I]),
-    "d3m_timing_collect": (_I, [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(_I), ctypes.POINTER(_F), _I]),
-    "d3m_forward_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_forward_workspace_min_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_set_coverage_form": (_I, [_I]),
-    "d3m_get_coverage_form": (_I, []),
-    "d3m_set_deterministic": (_I, [_I]),
-    "d3m_get_deterministic": (_I, []),
-    "d3m_set_edge_plan_form": (_I, [_I]),
-    "d3m_get_edge_plan_form": (_I, []),
-    "d3m_vertex_gather": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
-    "d3m_face_light_backward_gather": (_I, [_P, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _I, _I, _I, _P]),
-    "d3m_forward_coverage_form": (_I, [_I, _I, _I]),
-    "d3m_forward_big_batch": (_I, [_I, _I, _I]),
-    "d3m_forward_face_index_map": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _I, _P, _SZ, _P]),
-    "d3m_forward_face_index_map_mesh": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _SZ, _P, _SZ, _I, _P]),
-    "d3m_forward_face_index_map_mesh_modes": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _I, _I, _F, _F, _P, _SZ, _P, _SZ,
-                                                   _P, _P, _P, _I, _P]),
-    "d3m_forward_clear_bytes": (_SZ, [_I, _I, _I, _I, _SZ]),
-    "d3m_forward_texture_sampling": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
-    "d3m_backward_pixel_map_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_backward_pixel_map_workspace_min_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_backward_depth_map_mesh": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P]),
-    "d3m_backward_pixel_map": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _I, _P, _SZ, _P, _P, _P, _SZ, _P, _P]),
-    "d3m_edge_plan_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_edge_plan_min_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_edge_plan_extents_offset": (_SZ, [_I, _I, _I, ctypes.POINTER(_SZ)]),
-    "d3m_edge_plan": (_I, [_P, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
-    "d3m_edge_plan_clear_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_visibility_bytes": (_SZ, [_I, _I]),
-    "d3m_visibility": (_I, [_P, _P, _SZ, _I, _I, _I, _P]),
-    "d3m_backward_faces_workspace_bytes": (_SZ, [_I, _I]),
-    "d3m_backward_textures": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _SZ, _P]),
-    "d3m_backward_depth_map": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _SZ, _P]),
-    "d3m_camera_basis": (_I, [_P, _I, _P, _I, _P, _I, _I, _P, _I, _P]),
-    "d3m_camera_forward": (_I, [_P, _I, ctypes.POINTER(D3MCamera), _P, _I, _I, _P]),
-    "d3m_camera_backward": (_I, [_P, _I, ctypes.POINTER(D3MCamera), _P, _P, _I, _I, _P]),
-    "d3m_camera_backward_add": (_I, [_P, _I, ctypes.POINTER(D3MCamera), _P, _P, _I, _I, _P]),
-    "d3m_camera_params_backward_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_camera_params_backward": (_I, [_P, _I, ctypes.POINTER(D3MCamera), ctypes.POINTER(D3MBasis), _P,
-                                        ctypes.POINTER(D3MCameraGrad), _I, _I, _P, _SZ, _P]),
-    "d3m_gather_faces": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
-    "d3m_scatter_face_grads": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _P]),
-    "d3m_lighting_forward": (_I, [_P, _P, _P, _F, _F, _P, _P, _P, _L, _I, _P]),
-    "d3m_lighting_backward": (_I, [_P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _L, _I, _P]),
-    "d3m_view_transform": (_I, [_P, _I, _P, _P, _I, _P]),
-    "d3m_view_transform_backward": (_I, [_P, _I, _P, _P, _P, _I, _P]),
-    "d3m_grid_warp": (_I, [_P, _P, _I, _P, _P, _F, _P, _I, _P, _P, _I, _I, _I, _P]),
-    "d3m_grid_warp_backward": (_I, [_P, _P, _I, _P, _P, _F, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "d3m_depth_normals": (_I, [_P, _P, _I, _P, _I, _I, _I, _P]),
-    "d3m_depth_normals_backward": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P]),
-    "d3m_textures_from_im": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
-    "d3m_textures_from_im_backward": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
-    "d3m_uv_unwrap": (_I, [_P] * 11 + [_I] * 8 + [_P]),
-    "d3m_uv_unwrap_backward": (_I, [_P] * 12 + [_I] * 8 + [_P]),
-    "d3m_face_light": (_I, [_P, _I, _P, _I, _P, _F, _F, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "d3m_face_light_backward": (_I, [_P, _I, _P, _I, _P, _P, _F, _F, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "d3m_face_light_dev": (_I, [_P, _I, _P, _I, _P, ctypes.POINTER(D3MLight), _I, _I, _I, _I, _P]),
-    "d3m_face_light_backward_dev": (_I, [_P, _I, _P, _I, _P, _P, ctypes.POINTER(D3MLight), _I, _I, _I, _I, _P]),
-    "d3m_face_light_backward_gather_dev": (_I, [_P, _P, _P, _P, _P, _P, ctypes.POINTER(D3MLight), _I, _I, _I, _P]),
-    "d3m_light_params_backward_workspace_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_light_params_backward": (_I, [_P, _I, _P, _I, _P, _I, ctypes.POINTER(D3MLight), ctypes.POINTER(D3MLight), _I, _I, _I,
-                                       _P, _SZ, _P]),
-    "d3m_forward_texture_sampling_lit": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
-    "d3m_backward_textures_lit_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
-    "d3m_render_lit_epilogue": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I,
-                                     _P, _P]),
-    "d3m_render_fit_scratch_floats": (_SZ, [_I, _I]),
-    "d3m_render_fit_scratch_clear_range": (_SZ, [_I, _I, ctypes.POINTER(_SZ)]),
-    "d3m_fit_finish": (_I, [ctypes.POINTER(D3MFitTargets), _I, _I, _P]),
-    "d3m_render_fit_scratch_tile_void_offset": (_SZ, [_I, _I]),
-    "d3m_fit_target_summary": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
-    "d3m_set_fit_tile_form": (_I, [_I]),
-    "d3m_get_fit_tile_form": (_I, []),
-    "d3m_fit_loss_records": (_I, [_P, _P, _P, _P, ctypes.POINTER(D3MFitTargets), _I, _I, _P]),
-    "d3m_backward_textures_lit": (_I, [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _SZ,
-                                       _P, _P, _P, _I, _P]),
-    "d3m_backward_textures_lit_clear_ranges": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, ctypes.POINTER(_P),
-                                                    ctypes.POINTER(_SZ)]),
-    "d3m_lit_back": (_I, [_P, _I, ctypes.POINTER(D3MCamera), _P, _P, _I, _I, _P, _I, _I, _I, _P, _I, _F, _F, _P, _P, _P, _P]),
-    "d3m_lit_back_dev": (_I, [_P, _I, ctypes.POINTER(D3MCamera), _P, _P, _I, _I, _P, _I, _I, _I, _P, _I, ctypes.POINTER(D3MLight),
-                              _P]),
-    "d3m_lit_front_dev": (_I, [_P, _I, ctypes.POINTER(D3MCamera), ctypes.POINTER(D3MBasis), _P, _I, _I, _P, _I, _I, _I, _P, _I,
-                               ctypes.POINTER(D3MLight), ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P]),
-    "d3m_lit_front": (_I, [_P, _I, ctypes.POINTER(D3MCamera), ctypes.POINTER(D3MBasis), _P, _I, _I, _P, _I, _I, _I, _P, _I,
-                           _F, _F, _P, _P, _P, ctypes.POINTER(_P), ctypes.POINTER(_SZ), _I, _P]),
-    "d3m_output_epilogue": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "d3m_output_epilogue_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "d3m_output_epilogue_backward_records": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "d3m_photometric_loss": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
-    "d3m_sum_squared_error": (_I, [_P, _P, _P, _P, _P, _L, _P]),
-    "d3m_smooth_loss_forward": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "d3m_smooth_loss_backward": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "d3m_fit_loss_forward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "d3m_fit_loss_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "d3m_warp_resample": (_I, [_P, _P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "d3m_warp_resample_partials": (_I, [_I, _I]),
-    "d3m_warp_resample_backward": (_I, [_P, _P, _I, _P, _I, _P, _P, _F, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
-    "d3m_g2s_scratch_floats": (_SZ, [_I, _I, _I, _I]),
-    "d3m_g2s_forward": (_I, [ctypes.POINTER(D3MG2SBlock), _P]),
-    "d3m_g2s_backward": (_I, [ctypes.POINTER(D3MG2SBlock), _P]),
-    "d3m_mesh_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
-    "d3m_mesh_render_colors": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P]),
-    "d3m_mesh_render_texture": (_I, [_P] * 8 + [_I] * 10 + [_P, _SZ, _P]),
-    "d3m_mesh_map_texture": (_I, [_P] * 6 + [_I] * 8 + [_P]),
-    "d3m_mesh_vis_of_vertices": (_I, [_P] * 6 + [_I] * 4 + [_P, _SZ, _P]),
-    "d3m_mesh_get_triangle_buffer": (_I, [_P] * 5 + [_I] * 4 + [_P, _SZ, _P]),
-    "d3m_mesh_get_norm_direction": (_I, [_P, _P, _P, _I, _I, _P, _SZ, _P]),
-    "d3m_mesh_triangle_mean": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "d3m_mesh_triangle_normals": (_I, [_P, _P, _P, _I, _I, _P]),
-    "d3m_mesh_normalize": (_I, [_P, _I, _P]),
-    "d3m_mesh_get_correspondence": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _SZ, _P]),
-    "d3m_load_textures": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "d3m_create_texture_image": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P]),
-    "d3m_textures_from_image": (_I, [_P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
-    "d3m_uv_texture_taps": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "d3m_uv_texture_adjoint": (_I, [ctypes.POINTER(D3MCsr), _I, _P, _P, _P, _I, _L, _I, _I, _P]),
-    "d3m_vertex_color_textures": (_I, [_P, _I, _P, _P, _I, _I, _P]),
-    "d3m_vertex_color_textures_backward": (_I, [_P, ctypes.POINTER(D3MCsr), _P, _P, _I, _I, _I, _P]),
-    "d3m_vertex_attribute_images": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _I, _I, _P, _P, _P, _P]),
-    "d3m_vertex_attribute_scratch_floats": (_SZ, [_I, _I, _I, ctypes.POINTER(D3MCsr)]),
-    "d3m_vertex_attribute_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, ctypes.POINTER(D3MCsr), _P, _SZ, _P, _I, _I,
-                                                  _I, _P]),
-    "d3m_uv_texture_images": (_I, [ctypes.POINTER(D3MFragments), _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "d3m_uv_texture_images_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I, _I]),
-    "d3m_uv_texture_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
-    "d3m_texture_mip_pyramid": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    "d3m_uv_texture_lod": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _I, _I, _I, _F, _P, _P]),
-    "d3m_uv_texture_mip_images": (_I, [ctypes.POINTER(D3MFragments), _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P]),
-    "d3m_uv_texture_mip_images_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, _I]),
-    "d3m_uv_texture_mip_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, _P, _I, _I, _I, _I, _I, _I, _F, _P, _SZ, _P,
-                                                _P]),
-    "d3m_fragment_weights": (_I, [ctypes.POINTER(D3MFragments), _P, _P]),
-    "d3m_fragment_geometry_scratch_floats": (_SZ, [_I, _I, _I, ctypes.POINTER(D3MCsr), _I]),
-    "d3m_vertex_attribute_pixel_grads": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _I, _I, _P, _P, _P]),
-    "d3m_uv_texture_pixel_grads": (_I, [ctypes.POINTER(D3MFragments), _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
-    "d3m_fragment_geometry_backward": (_I, [ctypes.POINTER(D3MFragments), _P, ctypes.POINTER(D3MCsr), _P, _SZ, _P, _I, _P]),
-    "d3m_sh_fragment_images": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P]),
-    "d3m_sh_fragment_scratch_floats": (_SZ, [_I, _I, _I, _I, ctypes.POINTER(D3MCsr)]),
-    "d3m_sh_fragment_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _I, _I, _P, ctypes.POINTER(D3MCsr),
-                                             _P, _SZ, _P, _I, _P, _P, _P]),
-    "d3m_sh_fragment_pixel_grads": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _I, _I, _P, _P, _P]),
-    "d3m_sh_uv_fragment_images": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "d3m_sh_uv_fragment_scratch_bytes": (_SZ, [_I, _I, _I, _I, _I, _I, ctypes.POINTER(D3MCsr)]),
-    "d3m_sh_uv_fragment_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P,
-                                                ctypes.POINTER(D3MCsr), _P, _SZ, _P, _P, _P, _P, _P]),
-    "d3m_sh_uv_fragment_pixel_grads": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _I, _P, _P, _I, _I, _I, _I, _P, _P,
-                                            _P]),
-    "d3m_antialias_images": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _P, _P]),
-    "d3m_antialias_images_backward": (_I, [ctypes.POINTER(D3MFragments), _P, _I, _P, _I, _P, _P, _P, _P, _P]),
-    "d3m_antialias_scratch_floats": (_SZ, [_I, _I, _I, ctypes.POINTER(D3MCsr), _I]),
-    "d3m_antialias_geometry_backward": (_I, [ctypes.POINTER(D3MFragments), _P, ctypes.POINTER(D3MCsr), _P, _SZ, _P, _I, _P]),
-    "d3m_uv_bake_texture": (_I, [ctypes.POINTER(D3MFragments), ctypes.POINTER(D3MFragments), _P, _I, _I, _I, _P, _I, _I, _F, _P,
-                                 _P, _P, _P]),
-    "d3m_uv_bake_images_scratch_bytes": (_SZ, [_I, _I, _I, _I]),
-    "d3m_uv_bake_images_backward": (_I, [ctypes.POINTER(D3MFragments), ctypes.POINTER(D3MFragments), _I, _I, _I, _P, _I, _I, _F,
-                                         _P, _P, _SZ, _P, _P]),
-    "d3m_uv_bake_scratch_floats": (_SZ, [_I, _I, ctypes.POINTER(D3MCsr)]),
-    "d3m_uv_bake_vertices_backward": (_I, [ctypes.POINTER(D3MFragments), ctypes.POINTER(D3MFragments), _P, _I, _I, _I, _P, _I,
-                                           _I, _F, _P, ctypes.POINTER(D3MCsr), _P, _SZ, _P, _P]),
-    "d3m_uv_fill_pyramid_texels": (_SZ, [_I, _I]),
-    "d3m_uv_fill_scratch_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_uv_fill_backward_scratch_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_uv_fill_textures": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _SZ, _P, _SZ, _P, _P, _P]),
-    "d3m_uv_fill_textures_backward": (_I, [_P, _P, _P, _SZ, _P, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
-    "d3m_uv_texture_regularizer_scratch_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_uv_texture_regularizer": (_I, [_P, _I, _I, _I, _I, _P, _I, _F, _F, _F, _F, _F, _P, _I, _P, _I, _P, _SZ, _P, _P, _P]),
-    "d3m_uv_texture_regularizer_grad": (_I, [_P, _I, _I, _I, _I, _P, _I, _F, _F, _F, _F, _F, _P, _I, _P, _I, _P, _P, _P, _SZ, _P,
-                                             _P, _P]),
-    "d3m_chamfer_distance_scratch_bytes": (_SZ, [_I, _I, _I]),
-    "d3m_point_set_tile": (_I, []),
-    "d3m_point_set_queries_per_lane": (_I, []),
-    "d3m_point_set_splits": (_I, [_I, _I, _I]),
-    "d3m_nearest_points": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _SZ, _P, _P, _P]),
-    "d3m_chamfer_distance": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _F, _F, _F, _I, _P, _SZ, _P, _P, _P, _P, _P, _P, _P]),
-    "d3m_chamfer_distance_backward": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _P, _SZ, _P, _P, _P]),
-    "d3m_mesh_regularizer_scratch_floats": (_SZ, [_I, ctypes.POINTER(D3MMeshTopology)]),
-    "d3m_mesh_regularizer": (_I, [_P, _I, ctypes.POINTER(D3MMeshTopology), _F, _F, _F, _F, _P, _SZ, _P, _P, _P, _I, _P]),
-    "d3m_morphable_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
-    "d3m_morphable_scratch_floats": (_SZ, [_I, _I, _I]),
-    "d3m_morphable_backward": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _I, _I, _I, _I, _P]),
-    "d3m_pose_forward": (_I, [_P, _I, _P, _I, _F, _F, _F, _P, _I, _P, _P, _P, _I, _I, _P]),
-    "d3m_pose_scratch_floats": (_SZ, [_I, _I]),
-    "d3m_pose_tree_constants": (None, [ctypes.POINTER(_I)]),
-    "d3m_pose_backward": (_I, [_P, _I, _P, _I, _F, _F, _F, _P, _I, _P, _P, _P, _P, _SZ, _P, _P, _I, _I, _P]),
-    "d3m_smooth_shade_forward": (_I, [_P, _I, _P, _I, _P, _I, _P, ctypes.POINTER(D3MCsr), _P, _SZ, _P, _P, _P, _I, _I, _I, _P]),
-    "d3m_smooth_shade_scratch_floats": (_SZ, [_I, _I, _I, _I, _I]),
-    "d3m_smooth_shade_backward": (_I, [_P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, ctypes.POINTER(D3MCsr), _P, _SZ, _P, _P, _P,
-                                       _I, _I, _I, _P]),
-}
 
 _lib = None
 
